@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: MiB/s of plaintext through encode + decode of 4 MiB independent
 LZ4 blocks (level 1, block checksum on, content checksum off: configs[1]/[2]), with the % of the HBM roofline of
-the dominant kernel and plz4's CPU path timed beside it.
+the dominant kernel and (--full) plz4's CPU path timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--kind T|R|Z|M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--kind T|R|Z|M] [--full] [--dump-outputs DIR]
     N > 1 is launched by torch.distributed.run, one rank per GPU (RCCL), see the contract in the task statement.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what the headline does not need:
+the serial steps beside the duplex ones (`serial_step`), the check of the last frame body after the timed region, and the CPU
+path timed on the host (`cpu_baseline`, which also compares two of the GPU's records with the reference encoder).
+`--dump-outputs DIR` writes what the last timed step handed its caller to DIR/*.npy (dump_outputs below).
 
 One step = one pass of the hot path, both directions, over one batch that is already resident in HBM:
     ONE duplex call (plz4hip_dev_duplex_records): the level-1 encode of this step's B blocks (-> staged records + xxh32)
@@ -12,9 +17,9 @@ One step = one pass of the hot path, both directions, over one batch that is alr
     verified) -- a writer's next batch beside a reader's; the records land back to back in the frame body (plz4hip_dev_duplex_body:
     no staging area, no compaction pass since round 4)  [N > 1: RCCL gather of the bodies to rank 0 + interleave into the final
     frame body, or --gather none].
-Every step is one full encode and one full decode of B blocks; the body the last step produced is decoded and compared
-after the timed region.  `--duplex 0` (and every HC level) runs the step as encode -> frame body -> decode of the same
-batch, one call after the other; at N = 1 the default run times those K steps as well and reports them as `serial_step`.
+Every step is one full encode and one full decode of B blocks; with --full the body the last step produced is decoded and
+compared after the timed region.  `--duplex 0` (and every HC level) runs the step as encode -> frame body -> decode of the same
+batch, one call after the other; at N = 1 a --full run times those K steps as well and reports them as `serial_step`.
 Blocks are independent, so ranks share nothing on the data path (weak scaling: B blocks per GPU); block i of the
 global stream lives on rank i mod N.
 """
@@ -227,6 +232,51 @@ def same_bytes(a, b, chunk: int = 1 << 30) -> bool:
     return True
 
 
+DUMP_SAMPLE = 1 << 22      # bytes of the frame body and of the plaintext sampled by --dump-outputs (16 MiB apiece as float32)
+
+
+def dump_outputs(path: str, last: list, decode_only: bool):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files (about 34 MB at 6144 blocks).  Exact, per block:
+    the frame body's offsets, each record's size word and xxh32 word, the decoded size and status, and the byte sum and a
+    position-weighted byte sum of the decoded block (float64 holds them exactly).  Sampled: the same seeded positions of the frame
+    body and of the plaintext in every run (float32).  The step's parts follow each other in block order; decode-only steps write
+    the decode side alone (their frame bodies are inputs)."""
+    import torch
+    out = {}
+
+    def put(name, a, dtype=np.float64):
+        out.setdefault(name, []).append(np.asarray(a).astype(dtype))
+
+    def sample(buf, n, seed):
+        pos = np.sort(np.random.default_rng(seed).integers(0, n, size=min(n, DUMP_SAMPLE // len(last))))
+        return buf[torch.from_numpy(pos).to(buf.device)].cpu().numpy()
+
+    for i, pt in enumerate(last):
+        nb = pt["nb"]
+        dev = pt["out"].device
+        if not decode_only:
+            body = pt["body"]
+            off = pt["off"][:nb + 1].cpu().numpy()
+            # (the gathers below index the body on the device: every record has to lie inside it, size word and xxh32 included)
+            assert off[0] == 0 and np.all(np.diff(off) >= 8) and off[-1] <= body.numel(), "frame body offsets out of range"
+            put("frame_offsets", off)
+            heads = np.concatenate([off[:-1, None] + np.arange(4), off[1:, None] - 4 + np.arange(4)], axis=1)
+            words = body[torch.from_numpy(heads).to(dev)].cpu().numpy().view("<u4")          # (nb, 2): size word, xxh32
+            put("record_size_words", words[:, 0]); put("record_xxh32", words[:, 1])
+            put("frame_body_sample", sample(body, int(off[-1]), [0x504C5A34, i, 0]), np.float32)
+        put("decoded_sizes", pt["res"][:nb].cpu().numpy()); put("decode_status", pt["st"][:nb].cpu().numpy())
+        w = torch.arange(BSZ, dtype=torch.int64, device=dev) % 251 + 1                        # (255 * 251 * 4 MiB < 2**53)
+        for lo in range(0, nb, 32):
+            blk = pt["out"][lo * BSZ:min(nb, lo + 32) * BSZ].view(-1, BSZ).to(torch.int64)
+            put("plaintext_block_sums", torch.stack([blk.sum(1), (blk * w).sum(1)], 1).cpu().numpy())
+            del blk
+        put("plaintext_sample", sample(pt["out"], nb * BSZ, [0x504C5A34, i, 1]), np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, parts in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.concatenate(parts))
+    log("outputs of the last step written to %s: %s" % (path, ", ".join(sorted(out))))
+
+
 def memory_plan(B: int, world: int, gather_rank0: bool, duplex: bool, ratio: float, level: int = 1, pipelines: int = 1):
     """GiB this bench holds on the busiest rank (rank 0) for B blocks per GPU: its own buffers, the library's level-1 workspace
     (9 bytes per possible sequence -- a sequence takes at least 4 input bytes -- plus the chunk tables: launch_l1 in plz4hip.hip) and,
@@ -268,7 +318,12 @@ def main():
     ap.add_argument("--level", type=int, default=1, help="1 (configs[1]/[2], the headline) or 2..12 (LZ4_compress_HC; configs[3] is level 12)")
     ap.add_argument("--pipe", type=int, default=int(os.environ.get("PLZ4_BENCH_PIPE", "1")),
                     help="parts per step; decode of part p overlaps encode of part p+1 on a second stream (1 = serial)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the serial steps (serial_step), the check of the last frame body after the timed "
+                         "region and the CPU path (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, about 34 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU path")
     ap.add_argument("--duplex", type=int, default=int(os.environ.get("PLZ4_BENCH_DUPLEX", "1")),
                     help="level 1 only.  1 (default): a step is ONE duplex call (plz4hip_dev_duplex_records): the level-1 encode of this step's batch beside the "
                          "decode of the frame body the previous step produced (the decoder's waves share every CU with the parser's), "
@@ -445,6 +500,7 @@ def main():
         previous call wrote (one pipeline: the previous step's).  Calls alternate over the pipelines, each on its own stream."""
         gather["live"] = []
         done = [duplex_call(ev[h] if ev else None) for h in range(len(pipes) if SPLIT else 1)]
+        last_parts[:] = [d[0] for d in done]
         # The exchanges of the step BEFORE run now, behind this step's calls: sizing an exchange reads the body's length on the
         # host, which waits for that call's emit kernels -- with this step's calls already enqueued the GPU has work meanwhile, and
         # the next parse starts beside the last emit.  (A body is not written again before the exchange that read it is over:
@@ -455,6 +511,7 @@ def main():
             pending_gathers.extend(done); flush_gathers()                   # (no exchange: only the step's events to record)
 
     pending_gathers = []
+    last_parts = list(parts)                                                 # the parts the latest step wrote (duplex: its calls')
 
     def flush_gathers():
         todo = list(pending_gathers); del pending_gathers[:]
@@ -555,10 +612,11 @@ def main():
     d_off, d_body = parts[0]["off"], parts[0]["body"]
     check_pairs = []
     if rank == 0:
-        offs = d_off[:3].cpu().tolist()
-        check_pairs = [(d_src[i * BSZ:(i + 1) * BSZ].cpu().numpy().copy(), d_body[offs[i]:offs[i + 1]].cpu().numpy().copy()) for i in range(2)]
-        log("parity gate ok: round trip exact, every block status OK, stored/plain ratio %.4f "
-            "(two records are compared with the reference encoder in the cpu_baseline leg)" % (C_bytes / S))
+        if args.full:
+            offs = d_off[:3].cpu().tolist()
+            check_pairs = [(d_src[i * BSZ:(i + 1) * BSZ].cpu().numpy().copy(), d_body[offs[i]:offs[i + 1]].cpu().numpy().copy()) for i in range(2)]
+        log("parity gate ok: round trip exact, every block status OK, stored/plain ratio %.4f%s"
+            % (C_bytes / S, " (two records are compared with the reference encoder in the cpu_baseline leg)" if args.full else ""))
 
     for pt in parts:                                                         # the gate has told how large a body is: keep that + 2 %
         c_pt = int(pt["off"][-1].item())
@@ -652,7 +710,10 @@ def main():
     elapsed = time.perf_counter() - t0
     free_t, total_t = torch.cuda.mem_get_info(dev)
     held_timed = round((total_t - free_t) / 2**30, 1)
-    if duplex:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_parts, args.decode_only)
+        torch.cuda.empty_cache()
+    if duplex and args.full:
         # every timed step decoded the body its pipeline's previous call wrote (the first ones the warm-up's or the gate's): the
         # plaintext must be back, and so must the plaintext of each pipeline's last body, decoded here outside the timed region
         for pt in pipes:
@@ -668,7 +729,7 @@ def main():
             pt = q = None
             torch.cuda.synchronize(); torch.cuda.empty_cache()
     serial_leg = None
-    if duplex and not multi:
+    if duplex and not multi and args.full:
         # beside the headline: the same K steps as encode -> frame body -> decode of the same batch, one call after the other (the
         # step of rounds 1-2), which is also where the encode call and k_decode_rec are timed by themselves
         evs2 = [[[torch.cuda.Event(enable_timing=True) for _ in range(6)] for _ in parts] for _ in range(args.steps)]
@@ -762,7 +823,8 @@ def main():
             out["config"]["workload"] = out["config"]["workload"].replace(
                 "step = encode->frame body->decode",
                 "step = ONE duplex call (encode of this step's batch beside the decode of the frame body the previous step produced; every "
-                "step is one full encode and one full decode, the last body is decoded and checked after the timed region) -> frame body")
+                "step is one full encode and one full decode%s) -> frame body"
+                % (", the last body is decoded and checked after the timed region" if args.full else ""))
             out["config"]["duplex"] = True
             out["config"]["pipelines"] = NPIPE
             if SPLIT:
@@ -805,7 +867,7 @@ def main():
         free1, total1 = torch.cuda.mem_get_info(dev)
         out["config"]["gather"] = (args.gather if multi else None)
         out["memory_gib"] = {"plan": plan, "held_in_timed_region": held_timed, "held_at_end": round((total1 - free1) / 2**30, 1), "device": round(total1 / 2**30, 1)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pool, level=args.level, check=check_pairs)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if multi:

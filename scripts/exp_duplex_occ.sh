@@ -5,6 +5,6 @@ O=$R/gpurun_out/exp_duplex_occ
 mkdir -p $O
 for LIB in "$@"; do
   T=$(basename $LIB .so)
-  PLZ4HIP_LIB=$R/$LIB timeout -k 10 300 python3 $R/scripts/bench_lib.py --no-cpu-baseline --steps 3 --warmup 1 > $O/$T.json 2> $O/$T.log || exit 1
+  PLZ4HIP_LIB=$R/$LIB timeout -k 10 300 python3 $R/scripts/bench_lib.py --full --no-cpu-baseline --steps 3 --warmup 1 > $O/$T.json 2> $O/$T.log || exit 1
   python3 -c "import json;d=json.load(open('$O/$T.json'));print('$T', d['value'], d['ms'], d['serial_step']['ms'])"
 done

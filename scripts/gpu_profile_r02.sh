@@ -16,7 +16,7 @@ prof() {  # tag, then the command
     tail -1 $O/trace.log | cut -c1-200
 }
 case $W in
-l1) prof r02 python3 $R/bench.py --blocks 6144 --steps 2 --warmup 1 --no-cpu-baseline ;;
+l1) prof r02 python3 $R/bench.py --blocks 6144 --steps 2 --warmup 1 --full --no-cpu-baseline ;;
 c4) prof r02_config4_level12 python3 $R/bench.py --level 12 --blocks 1024 --steps 1 --warmup 1 --no-cpu-baseline
     prof r02_level3 python3 $R/bench.py --level 3 --blocks 1024 --steps 1 --warmup 1 --no-cpu-baseline ;;
 hc) prof r02_level9_lists python3 $R/bench.py --level 9 --blocks 1024 --steps 1 --warmup 0 --no-cpu-baseline

@@ -687,9 +687,10 @@ def test_gpu_bench_modes_run_on_one_gpu():
         line = json.loads(out.stdout.strip().splitlines()[-1])
         assert line["value"] > 0 and ("k_l1_duplex" in line["roofline"]["kernel"]) == (dup == "1")
     # one GPU, no gather: the duplex steps alternate over two streams by default (two record workspaces inside the library), three
-    # when asked, one when asked; an odd number of steps leaves the pipelines with different numbers of calls
+    # when asked, one when asked; an odd number of steps leaves the pipelines with different numbers of calls (--full: the serial
+    # steps and the check of every pipeline's last body after the timed region as well)
     for pipes, want in (((), 2), (("--pipelines", "3"), 3), (("--pipelines", "1"), 1)):
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--blocks", "64", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--blocks", "64", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                               *pipes], env=dict(os.environ, PLZ4_BENCH_NO_PIPE_CHECK="1"), capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -705,3 +706,36 @@ def test_gpu_bench_modes_run_on_one_gpu():
         # (64 blocks per step: whether two streams beat one here is noise, so a forced first failure may be followed by a real one)
         rep = line["config"]["pipeline_check"]["streams_replaced"]
         assert rep >= int(forced) and line["config"]["pipelines"] == (2 if rep < 2 else 1) and (forced != "2" or line["config"]["pipelines"] == want)
+
+
+@pytest.mark.gpu
+def test_gpu_bench_plain_run_and_its_outputs(orc, tmp_path):
+    """A plain bench.py run (no --full): the headline fields and nothing of what --full adds; --dump-outputs writes what the last
+    timed step computed, which is the oracle's records of the bench's input and that input decoded back."""
+    import json, os, subprocess, sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--blocks", "64", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "MiB/s" and line["higher_is_better"]
+    assert "serial_step" not in line and "cpu_baseline" not in line
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64e6
+    # the bench's input: the T pool tiled into rotated replicas (bench.py main)
+    B, BSZ = 64, bench.BSZ
+    pool = synth.make("T", bench.POOL_BLOCKS * BSZ, BSZ)
+    src = np.concatenate([np.roll(pool, -((r * 1000003) % pool.size)) for r in range(B * BSZ // pool.size)])
+    recs = [orc.block_record(src[i * BSZ:(i + 1) * BSZ], BSZ, True) for i in range(B)]
+    assert np.array_equal(got["decode_status"], np.zeros(B)) and np.array_equal(got["decoded_sizes"], np.full(B, BSZ))
+    assert np.array_equal(got["frame_offsets"], np.concatenate([[0], np.cumsum([r.size for r in recs])]))
+    assert np.array_equal(got["record_size_words"], [int(r[:4].view("<u4")[0]) for r in recs])
+    assert np.array_equal(got["record_xxh32"], [int(r[-4:].view("<u4")[0]) for r in recs])
+    w = np.arange(BSZ, dtype=np.int64) % 251 + 1
+    want = [(int(b.sum(dtype=np.int64)), int((b.astype(np.int64) * w).sum())) for b in src.reshape(B, BSZ)]
+    assert np.array_equal(got["plaintext_block_sums"], np.array(want, dtype=np.float64))
+    body = np.concatenate(recs)
+    for name, buf, seed in (("frame_body_sample", body, [0x504C5A34, 0, 0]), ("plaintext_sample", src, [0x504C5A34, 0, 1])):
+        pos = np.sort(np.random.default_rng(seed).integers(0, buf.size, size=min(buf.size, bench.DUMP_SAMPLE)))
+        assert np.array_equal(got[name], buf[pos].astype(np.float32)), name
