@@ -36,6 +36,13 @@
  * to 4 MiB + 8 of output; 0 turns it off) is cut across the whole chip and keeps 8 bytes per input byte + 4 per output byte of
  * the call's blocks (about 50 MiB per 4 MiB block) until plz4hip_ctx_trim; results and error codes are LZ4_decompress_safe's
  * either way (a block that path will not answer for is decoded by the one-wavefront decoder inside the call).
+ * An ENCODE call of few blocks at level 1 (compress_batch, encode_records, dev_compress with maxLen > 0, dev_encode_records,
+ * dev_encode_body; up to PLZ4HIP_FX_MAX_BLOCKS = 128 blocks, 0 turns it off) whose largest block is 65 547 bytes .. 4 MiB (liblz4's
+ * byU32 tables) has its parse cut across the whole chip: pieces of PLZ4HIP_FX_PIECE_KIB (64) parsed by a wave each, in rounds
+ * until every piece starts from the exact state its predecessor ends in; a guessed start begins PLZ4HIP_FX_WARMUP_KIB (64) early.
+ * Output, results and error codes are exactly those of the one-wave parse; smaller blocks of such a call are parsed whole.
+ * Duplex calls and level 2 keep their kernels.  It keeps about 3 bytes per input byte of the call's blocks (the pieces' tables
+ * and records) until plz4hip_ctx_trim.  plz4hip_ctx_counters reports what these two few-block paths did.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
  * calls, rounds 1-3), PLZ4HIP_HC12_LAZY (level 12 with its searches made on demand), PLZ4HIP_HC_OVERLAP_OFF / _MIN / _GROUPS (levels 3..11: a call of 2048
  * blocks or more runs in four or more groups, the list builder of the next group on a second stream of the ctx beside the walk
@@ -80,6 +87,10 @@ int         plz4hip_ctx_create(int device, plz4hip_ctx** out);
 void        plz4hip_ctx_destroy(plz4hip_ctx* ctx);
 const char* plz4hip_last_error(const plz4hip_ctx* ctx);       /* text of the last PLZ4HIP_E_* on this ctx */
 int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release staging buffers and HC workspaces (waits for work in flight) */
+/* Waits for the ctx's work, then writes up to n counters to out: [0] blocks encoded by the few-block level-1 path, [1] its rounds
+ * in the last such call, [2] pieces it parsed more than once, [3] blocks answered by the few-block decoder.  Returns how many
+ * counters there are (4), or PLZ4HIP_E_*. */
+int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */
 int plz4hip_compress_bound(int n);

@@ -19,6 +19,7 @@ SYMBOLS = [
     "plz4hip_xxh32_batch", "plz4hip_encode_records", "plz4hip_decode_records", "plz4hip_dev_stage_stride",
     "plz4hip_dev_encode_records", "plz4hip_dev_compact_records", "plz4hip_dev_scatter_records",
     "plz4hip_dev_decode_records", "plz4hip_dev_duplex_records", "plz4hip_dev_encode_body", "plz4hip_dev_duplex_body", "plz4hip_dev_compress", "plz4hip_dev_decompress", "plz4hip_ctx_trim",
+    "plz4hip_ctx_counters",
     "plz4hip_dev_resident_waves", "plz4hip_dict_create", "plz4hip_dict_destroy", "plz4hip_compress_batch_dict", "plz4hip_decode_records_chains",
     "plz4hip_decompress_batch_dict", "plz4hip_encode_records_ex", "plz4hip_decode_records_ex",
     "plz4hip_xxh32_stream_create", "plz4hip_xxh32_stream_destroy", "plz4hip_xxh32_stream_reset", "plz4hip_xxh32_stream_update",
@@ -131,6 +132,8 @@ def load():
     L.plz4hip_ctx_set_content_hash.argtypes = [vp, vp]
     L.plz4hip_ctx_trim.restype = C.c_int
     L.plz4hip_ctx_trim.argtypes = [vp]
+    L.plz4hip_ctx_counters.restype = C.c_int
+    L.plz4hip_ctx_counters.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     L.plz4hip_mgpu_create.restype = C.c_int
     L.plz4hip_mgpu_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
     L.plz4hip_mgpu_destroy.restype = None
@@ -390,6 +393,17 @@ class Engine:
 
     def trim(self):
         self._chk(self.L.plz4hip_ctx_trim(self.h))
+
+    COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks")
+
+    def counters(self) -> dict:
+        """plz4hip_ctx_counters (waits for the ctx's work): blocks encoded by the few-block level-1 path, its rounds in the last
+        such call, pieces it parsed more than once, blocks answered by the few-block decoder."""
+        out = (C.c_int64 * 4)()
+        rc = int(self.L.plz4hip_ctx_counters(self.h, out, 4))
+        if rc < 0:
+            self._chk(rc)
+        return {k: int(out[i]) for i, k in enumerate(self.COUNTERS)}
 
 
 class MultiEngine:

@@ -1,0 +1,139 @@
+// lz4_fx_device.inl -- the level-1 parse (lz4_seq_device.inl) of a call of few blocks cut across the whole chip.
+//
+// A level-1 block is one serial chain: one wave parses it, however empty the chip is (1 x 4 MiB: ~70 ms).  Here a block of
+// kFxMinLen..4 MiB (liblz4's byU32 tables, lz4.c:1389) is cut into pieces of `pb` bytes and every piece gets a wave of its own.
+//
+// Why a piece can be parsed on its own: right after a match (anchor = the match's end, lz4.c:1230-1233) the rest of liblz4's parse
+// depends on the anchor, the LIVE part of the table -- an entry is live iff index + 65535 >= current (lz4.c:1090, :1274), and a dead
+// entry never comes back -- and the input.  The catch-up stops at the anchor (lz4.c:1107-1109) and limitedOutput never feeds back.
+// So a parse restarted from such a post-match state (anchor + table) gives exactly the records of the unbroken parse.  Piece k's
+// entry state is the first post-match state at or beyond its start; its exit state the first one at or beyond its end -- which is
+// piece k+1's entry state.
+//
+// Rounds (one launch each, grid (pieces, blocks)):
+//   round 1   piece 0 parses from the block's start (exact).  Piece k > 0 starts `warm` bytes early from a guessed state (every
+//             slot "position 0"), records the state it reaches at its start (inAnchor / tabIn) and keeps the records from there.
+//   round r   piece k runs again iff piece k-1 ran in round r-1, did not reach the block's end, and its exit state differs from
+//             piece k's recorded entry state (same anchor, same live entries); it then starts from that exit state.
+// Exit states are kept per round parity (tabOut[r & 1]): round r reads r-1's and writes r's, so no piece waits for another.
+// Piece 0 is exact after round 1 and, by induction, piece i after round i + 1: P rounds are always enough, and a piece that is
+// exact never runs again.  The gather (one wave per piece) lays the records of the chain 0, 1, ... up to the piece that reached the
+// block's end out as the block's records; the emit kernels of lz4_seq_device.inl run unchanged behind it.
+// A piece whose search runs past its end simply goes on to the next post-match state (or the block's end): the worst case is one
+// exact walk of the rest of the block, as with one wave per block.
+#pragma once
+#include "lz4_seq_device.inl"
+
+namespace plz4 {
+
+enum : int { kFxTab = kHashBytes / 4, kFxMinLen = k64KLimit };
+
+// per piece; fields [r & 1] belong to the round that wrote them
+struct FxPiece {
+    int32_t inAnchor;          // the entry state the records are from (-1: none)
+    int32_t nseq, fin, lastAnchor;      // last run: records, reached the block's end, where its last literals start
+    int32_t runs, lastRound;
+    int32_t ran[2], outAnchor[2], outFin[2];
+};
+
+DEV int fx_pieces(int n, int pb) { return (n + pb - 1) / pb; }
+// records a piece has room for (+ the dump entry): those of its own bytes, one that crosses its end, a batch of warm-up records
+static inline int fx_rec_stride_host(int pb) { return ((pb / 4 + 80) + 7) & ~7; }
+
+// two states at one anchor: same live entries (dead ones never matter again)
+DEV bool fx_same_state(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B, int anchor)
+{
+    LV(int, bad);
+    LANES({
+        int b = 0;
+        for (int i = LANE; i < kFxTab; i += 64) {
+            const uint32_t x = A[i], y = B[i];
+            const bool lx = (x >> 10) + kMaxDist >= (uint32_t)anchor, ly = (y >> 10) + kMaxDist >= (uint32_t)anchor;
+            b |= (int)((lx != ly) | (lx & (x != y)));
+        }
+        bad[I_] = b;
+    })
+    return BALLOT(bad[I_] != 0) == 0;
+}
+
+// One wave: piece k of a block of n bytes in round `round` (1, 2, ...).  meta / tabIn: P entries of the block; tabOut: 2 x P
+// tables (parity major); rec: P x recStride records.  Returns 1 when it parsed.
+DEV int fx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int pb, int warm, FxPiece* meta, uint32_t* tabIn, uint32_t* tabOut,
+                 uint64_t* rec, int recStride, uint32_t* lds)
+{
+    const int P = fx_pieces(n, pb);
+    if (k >= P) return 0;
+    const int par = round & 1, start = k * pb;
+    FxPiece* const me = meta + k;
+    uint32_t* const myIn = tabIn + (int64_t)k * kFxTab;
+    FxRun run;
+    run.entryAnchor = -1; run.entryTab = nullptr; run.cp = -1; run.cpTab = myIn; run.cpAnchor = -1;
+    run.end = min_(n, start + pb); run.outTab = tabOut + ((int64_t)par * P + k) * kFxTab; run.outAnchor = -1;
+    run.seqCap = recStride - 1; run.fin = 0;
+    if (round == 1) {
+        if (k > 0) {
+            run.cp = start;
+            const int p0 = start - warm;
+            if (p0 >= 64) run.entryAnchor = p0;                      // (else from the block's start: exact)
+        }
+    } else {
+        bool go = false;
+        if (k > 0 && meta[k - 1].ran[par ^ 1] && !meta[k - 1].outFin[par ^ 1]) {
+            const int a = meta[k - 1].outAnchor[par ^ 1];
+            const uint32_t* T = tabOut + ((int64_t)(par ^ 1) * P + k - 1) * kFxTab;
+            if (a != me->inAnchor || !fx_same_state(T, myIn, a)) {
+                go = true;
+                run.entryAnchor = a; run.entryTab = T;
+                LANES({ for (int i = LANE; i < kFxTab; i += 64) myIn[i] = T[i]; })
+            }
+        }
+        if (!go) {
+            LANES({ if (LANE == 0) me->ran[par] = 0; })
+            return 0;
+        }
+    }
+    int lastAnchor = 0;
+    const int ns = wave_parse_l1_tt<false, 2, true>(src, n, lds, rec + (int64_t)k * recStride, &lastAnchor, nullptr, &run);
+    const int inA = round == 1 ? (k > 0 ? run.cpAnchor : 0) : run.entryAnchor;
+    const int runs = round == 1 ? 1 : me->runs + 1;
+    WAVE_FENCE();
+    LANES({
+        if (LANE == 0) {
+            me->inAnchor = inA; me->nseq = ns; me->fin = run.fin; me->lastAnchor = lastAnchor;
+            me->runs = runs; me->lastRound = round;
+            me->ran[par] = 1; me->outAnchor[par] = run.outAnchor; me->outFin[par] = run.fin;
+        }
+    })
+    return 1;
+}
+
+// One wave: piece k's records into the block's record array, if the block's chain reaches it; the piece that reached the block's
+// end writes the block's SeqInfo.  Returns 0: not in the chain, 1: in it, 2: the last of it.  (Counts beyond the room of a piece
+// or of the block cannot come out of an exact parse; they would fail the block -- kSeqEngineFailed -- rather than be written.)
+DEV int fx_gather(int n, int k, int pb, const FxPiece* __restrict__ meta, const uint64_t* __restrict__ rec, int recStride,
+                  uint64_t* __restrict__ seq, int seqCap, SeqInfo* info)
+{
+    const int P = fx_pieces(n, pb);
+    if (k >= P) return 0;
+    int off = 0;
+    bool over = false;
+    for (int j0 = 0; j0 < k; j0 += 64) {
+        LV(int, c); LV(int, f);
+        LANES({ const int j = j0 + LANE; c[I_] = j < k ? meta[j].nseq : 0; f[I_] = j < k ? meta[j].fin : 0; })
+        if (BALLOT(f[I_] != 0)) return 0;
+        over |= BALLOT(c[I_] >= recStride) != 0;
+        SCAN_INCL(c);
+        off += RL(c, 63);
+    }
+    const int ns = meta[k].nseq, fin = meta[k].fin;
+    const bool room = !over && ns < recStride && off + ns <= seqCap;
+    const uint64_t* r = rec + (int64_t)k * recStride;
+    if (room) LANES({ for (int j = LANE; j < ns; j += 64) seq[off + j] = r[j]; })
+    if (fin) {
+        const int la = meta[k].lastAnchor;
+        LANES({ if (LANE == 0) { SeqInfo inf; inf.nseq = room ? off + ns : kSeqEngineFailed; inf.lastAnchor = la; inf.total = 0; inf.stored = 0; *info = inf; } })
+    }
+    return fin ? 2 : 1;
+}
+
+}  // namespace plz4

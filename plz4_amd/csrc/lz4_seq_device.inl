@@ -125,26 +125,49 @@ struct GStage { Win20 P; Win20 C; uint32_t h, ent, pk; };     // window, candida
 #endif
 enum { P_BATCH = 0, P_CYC_MEM, P_CYC_LDS, P_CYC_REFRESH, P_CYC_CMP, P_CYC_WALK, P_CYC_TAIL, P_REPAIR, P_PRIME, P_GENERIC, P_CYC_TOTAL, P_BLOCKS, P_SEQ, P_CYC_GEN, P_CYC_NH, P_CYC_HOP, P_CYC_E, P_CYC_SLOW, P_HOPS };
 
+// kPiece: one piece of a block (lz4_fx_device.inl).  The parse starts from a given state -- the block's start, or the state right after
+// a match (anchor = the match's end, before the insert at anchor - 2 and the re-test at anchor, lz4.c:1230-1294) with a given table
+// (or a guessed one) -- and stops at the first such post-match state whose anchor is at or beyond `end`.  That state (anchor + table)
+// is written to outTab; `cp`, when set, is an earlier boundary of the same kind at which the state is written to cpTab and the
+// records written so far are dropped (a guessed start's warm-up).  Records of a run that reaches the block's end: fin = 1.
+struct FxRun {
+    int             entryAnchor;      // -1: the block's start; else a post-match state at this anchor
+    const uint32_t* entryTab;         // its table (16 KiB); null: every slot "position 0" (a guess)
+    int             cp;               // -1: none
+    uint32_t*       cpTab;  int cpAnchor;      // out: the state at cp (cpAnchor -1: not reached)
+    int             end;
+    uint32_t*       outTab; int outAnchor;     // out: the state at end
+    int             seqCap;           // records the piece has room for; seq[seqCap] is the dump entry
+    int             fin;              // out
+};
+DEV void fx_save_table(const void* tab, uint32_t* g)
+{
+    const uint32_t* t = (const uint32_t*)tab;
+    LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) g[i] = t[i]; })
+}
+
 // kLdsWin: the windows of the batches ahead come through `scr` (256 bytes of LDS owned by this wave) instead of one 20-byte load per
 // lane: the 64 windows of a batch are 83 consecutive bytes, but 64 overlapping per-lane loads are 128 accesses to the CU's vector
 // cache for them (its tag pipeline is what ten parser waves per CU saturate: TA busy 65 %, TCP stalled on pending misses 46 % of
 // the time, profiles/r04b_ta_counters.txt).  The lanes fetch consecutive dwords a batch earlier (one coalesced load), park them in
 // LDS and every lane reads its 20 bytes back from its byte offset.
-template <bool U16, int kLdsWin = 0>
-DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab, uint64_t* __restrict__ seq, int* lastAnchor, uint8_t* scr = nullptr)
+template <bool U16, int kLdsWin = 0, bool kPiece = false>
+DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab, uint64_t* __restrict__ seq, int* lastAnchor, uint8_t* scr = nullptr,
+                         FxRun* run = nullptr)
 {
     const int      sh      = U16 ? 0 : 10;
     const uint32_t tagMask = (1u << sh) - 1u;
     {   // fresh table per block (LZ4_initStream, lz4.c:1384): every slot = "position 0"
         const uint32_t e0 = (sh && n >= 4) ? (seq_tag(UNI(ld32u(src))) & tagMask) : 0u;
         uint32_t* t = (uint32_t*)tab;
-        LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) t[i] = e0; })
+        if (kPiece && run->entryTab) { const uint32_t* g = run->entryTab; LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) t[i] = g[i]; }) }
+        else LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) t[i] = e0; })
     }
     LDS_FENCE();
 
     const int lastProbe  = n - kMfLimit + 1;      // mflimitPlusOne (lz4.c:963)
     const int matchLimit = n - kLastLiterals;     // lz4.c:964
-    const int seqDump    = seq_capacity(n);       // one entry behind the records: where lanes without a record store
+    const int seqDump    = kPiece ? run->seqCap : seq_capacity(n);    // one entry behind the records: where lanes without a record store
     int nseq = 0, anchor = 0;
     STAT_DECL;
     const unsigned long long tBlock0 = STAT_NOW(); (void)tBlock0;
@@ -160,6 +183,31 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         LANES({ pf[I_] = 0; })
         LANES({ for (int k = 0; k < 5; ++k) { S0[I_].P.w[k] = 0; S0[I_].C.w[k] = 0; } S0[I_].h = 0; S0[I_].ent = 0; S0[I_].pk = 0; S1[I_] = S0[I_]; S2[I_] = S0[I_]; })
         enum { kGridNext = 0, kGridDone = 1, kGridGeneric = 2, kGridStop = 3 };
+        // kPiece: the next boundary and whether records are kept (not before cp).  A grid batch runs only where none of its executed
+        // lanes can lie behind the boundary's post-match state: every match of it that ends at or beyond fxB ends at or beyond
+        // base + 66, so its insert (anchor - 2) and re-test stay pending, and the state after the batch is that post-match state.
+        int  fxB = 0x7FFFFFFF; bool fxRec = true, fxStop = false;
+        if (kPiece) {
+            if (run->entryAnchor >= 0) {
+                const int a0 = run->entryAnchor;
+                anchor = a0; hasIns = true; insPos = a0 - 2; hasRe = true; rePos = a0; sBase = a0 + 1; sIter = 0;
+            }
+            fxRec = run->cp < 0; fxB = fxRec ? run->end : run->cp;
+        }
+        const bool fxDead = kPiece && anchor >= lastProbe;        // (a guessed start too close to the end: no parse at all)
+        auto fx_boundary = [&]() -> bool {
+            if (!fxRec) nseq = 0;                                  // (warm-up records are dropped as they come)
+            if (anchor < fxB) return false;
+            LDS_FENCE();
+            if (!fxRec) {
+                fx_save_table(tab, run->cpTab); run->cpAnchor = anchor;
+                fxRec = true; nseq = 0; fxB = run->end;
+                if (anchor < fxB) return false;
+            }
+            fx_save_table(tab, run->outTab); run->outAnchor = anchor;
+            fxStop = true;
+            return true;
+        };
 
         // One batch of the steady state: WALK, then COMMIT, then VERIFY.  On entry: cur.P = the window of `base`, cur.h / ent = its
         // slot and entry, cur.pk = what the slot held at the top of the previous batch, cur.C = the window at that entry's position
@@ -184,6 +232,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             const int probeStart = hasRe ? rePos : sBase + sIter;
             const int firstPos   = hasIns ? insPos : probeStart;
             if ((sIter > 64) | ((firstPos & ~63) != base) | (base + 224 > n)) return kGridStop;
+            if (kPiece && ((base + 66 > fxB) | (anchor >= fxB))) return kGridStop;
+            if (kPiece && !fxRec) nseq = 0;
             uint32_t* T = (uint32_t*)tab;
             EMU_CNT(0, 1); STAT(P_BATCH, 1);
             const unsigned long long ts0 = STAT_NOW(); (void)ts0;
@@ -478,7 +528,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 // (every lane stores: the ones without a match into the dump entry behind the block's last possible record)
                 const uint64_t mmL = mm; const int at = nseq;
                 LANES({
-                    const int slot = LANE_IN(mmL) ? at + LANE_RANK(mmL) : seqDump;
+                    const int slot = LANE_IN(mmL) ? (kPiece ? min_(at + LANE_RANK(mmL), seqDump) : at + LANE_RANK(mmL)) : seqDump;
                     seq[slot] = seq_pack((uint32_t)(base + LANE), (uint32_t)fwd[I_], (uint32_t)(base + LANE) - (ce[I_] >> sh));
                 })
                 nseq += __builtin_popcountll(mm);
@@ -504,12 +554,13 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         };
 
         for (;;) {
+            if (kPiece && (fxDead || fx_boundary())) break;
             // ================================================================ GRID batch
             if (!U16 && sIter <= 64) {
                 const int probeStart = hasRe ? rePos : sBase + sIter;
                 const int firstPos   = hasIns ? insPos : probeStart;
                 int base = firstPos & ~63;
-                if (base >= 64 && base + 224 <= n) {
+                if (base >= 64 && base + 224 <= n && (!kPiece || base + 66 <= fxB)) {
                     // prime the pipeline (the table is exact here): windows of this batch and the next, this batch's slots
                     // peeked, its candidates requested.  The memory round trips of this start are the only ones the grid
                     // batches ever wait for.
@@ -539,11 +590,12 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         if (sIter <= 64) {
                             const int ps = hasRe ? rePos : sBase + sIter;
                             const int nb = (hasIns ? insPos : ps) & ~63;
-                            if (nb >= 64 && nb + 224 <= n) continue;
+                            if (nb >= 64 && nb + 224 <= n && (!kPiece || nb + 66 <= fxB)) continue;
                         }
                     }
                 }
             }
+            if (kPiece && fx_boundary()) break;
             // ================================================================ GENERIC batch: one lane per probe of the search loop
             {
             STAT(P_GENERIC, 1);
@@ -619,7 +671,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             const int mc = wave_common_len(src, p + kMinMatch, c + kMinMatch, matchLimit);
             {
                 const int at = nseq;
-                LANES({ if (LANE == 0) seq[at] = seq_pack((uint32_t)p, (uint32_t)mc, (uint32_t)(p - c)); })
+                LANES({ if (LANE == 0) seq[kPiece ? min_(at, seqDump) : at] = seq_pack((uint32_t)p, (uint32_t)mc, (uint32_t)(p - c)); })
             }
             nseq++;
             const int ip = p + kMinMatch + mc;
@@ -632,6 +684,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             sBase = ip + 1; sIter = 0; width = 16;
             }
         }
+        if (kPiece) run->fin = !fxStop;
     }
     *lastAnchor = anchor;
     STAT(P_CYC_TOTAL, STAT_NOW() - tBlock0); STAT(P_BLOCKS, 1); STAT(P_SEQ, nseq);

@@ -25,6 +25,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4hc12_device.inl"
 #include "lz4hc_lazy_device.inl"
 #include "lz4_dx_device.inl"
+#include "lz4_fx_device.inl"
 
 namespace {
 
@@ -188,6 +189,44 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_l1_parse(CodecArgs 
     ENC_WAVE_TABLE(lds);
     l1_parse_loop<2>(a, lds);                  // (ten tables fill the CU's LDS: the windows through the lane exchange, lz4_seq_device.inl)
 }
+
+// ---- the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): grid (pieces, blocks of the group), one wave each,
+// one launch per round, then the gather into the staged path's records (l1Seq / l1Info) -- the emit kernels below run unchanged.
+// Workspace per block: P pieces x (meta, entry table, two exit tables, records).  cnt: the ctx's counters (plz4hip_ctx_counters).
+struct FxArgs { FxPiece* meta; uint32_t* tabIn; uint32_t* tabOut; uint64_t* rec; int P, pb, warm, recStride; unsigned long long* cnt; };
+__global__ __launch_bounds__(64) void k_fx_piece(CodecArgs a, FxArgs f, int round)
+{
+    __shared__ uint32_t lds[kHashBytes / 4];
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    if (n < kFxMinLen || n > a.l1MaxLen) {
+        // outside the path's scope (byU16 blocks, lengths the workspace was not sized for): the block as k_l1_parse does it
+        if (round != 1 || k != 0) return;
+        int lastAnchor = 0, nseq = -1;
+        if (n >= 0 && n <= a.l1MaxLen) nseq = wave_parse_l1<2>(a.src + (int64_t)gi * a.srcStride, n, lds, a.l1Seq + (int64_t)i * a.l1SeqStride, &lastAnchor);
+        if ((threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = nseq; inf.lastAnchor = lastAnchor; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
+        return;
+    }
+    const int64_t pb0 = (int64_t)i * f.P;
+    fx_piece(a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * kFxTab, f.tabOut + pb0 * 2 * kFxTab,
+             f.rec + pb0 * f.recStride, f.recStride, lds);
+}
+__global__ __launch_bounds__(64) void k_fx_gather(CodecArgs a, FxArgs f)
+{
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    if (n < kFxMinLen || n > a.l1MaxLen || k >= fx_pieces(n, f.pb)) return;
+    const int64_t pb0 = (int64_t)i * f.P;
+    const FxPiece* m = f.meta + pb0;
+    const int g = fx_gather(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
+                          (int)a.l1SeqStride - 1, a.l1Info + i);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicMax(&f.cnt[1], (unsigned long long)m[k].lastRound);
+        if (m[k].runs > 1) atomicAdd(&f.cnt[2], 1ull);
+        if (g == 2) atomicAdd(&f.cnt[0], 1ull);
+    }
+}
+__global__ __launch_bounds__(64) void k_fx_begin(unsigned long long* cnt) { if (threadIdx.x == 0) cnt[1] = 0; }
 
 // grid (waves per block / 4, blocks of the group): bytes of every chunk of 1024 sequences.  kBack: the level-1 parser's records
 // (their catch-up is measured here); false: the HC parsers' records, which carry the final match.
@@ -1018,13 +1057,14 @@ __global__ __launch_bounds__(256) void k_dx_jump(CodecArgs a)
     if (p0 >= outLen) return;
     if (dx_jump(a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen) && (threadIdx.x & 63u) == 0) inf->moved[r] = 1u;
 }
-__global__ __launch_bounds__(256) void k_dx_gather(CodecArgs a)
+__global__ __launch_bounds__(256) void k_dx_gather(CodecArgs a, unsigned long long* cnt)
 {
     const int b = blockIdx.y;
     const DxInfo* const inf = a.dxInfo + b;
     if (inf->bad) return;
     const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicAdd(&cnt[3], 1ull);                                           // (plz4hip_ctx_counters: blocks this path answered)
         // (records: the payload's checksum is verified beside this path, k_dx_rec_hash; frame.go:114-127 rejects before it decodes)
         const bool hashBad = a.dxHashBad && a.dxHashBad[b];
         a.result[b] = hashBad ? 0 : outLen;
@@ -1314,6 +1354,13 @@ struct plz4hip_ctx {
     uint8_t*     d_dx = nullptr; size_t dxBytes = 0;
     hipEvent_t   dxDone = nullptr; hipStream_t dxStream = nullptr; bool dxPending = false;
     hipStream_t  dxHashStream = nullptr; hipEvent_t evDxFork = nullptr, evDxHash = nullptr;   // records: the block checksums beside the decode
+    // the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): pieces' states and records of one job at a time,
+    // sized per call, ordered across streams like the dx tables
+    uint8_t*     d_fx = nullptr; size_t fxBytes = 0;
+    hipEvent_t   fxDone = nullptr; hipStream_t fxStream = nullptr; bool fxPending = false;
+    // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
+    // parsed more than once, [3] blocks answered by the few-block decoder
+    unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call.  One job at a time like the workspaces: a call on another
     // stream waits (on the device) for the event behind the last job's kernels before it overwrites the copy.
     int32_t*     d_lenCopy = nullptr; int lenCopyCap = 0;
@@ -1333,7 +1380,8 @@ struct plz4hip_dict {
 
 namespace {
 
-constexpr int kQueueSlots = 4096;         // work-queue counters, reused round-robin: far more than launches that can be in flight
+constexpr int kQueueSlots = 4096;
+constexpr int kFxMaxBlocks = 128;         // PLZ4HIP_FX_MAX_BLOCKS: the few-block level-1 parse up to this many blocks (launch_l1; profiles/fx_rate.json)
 
 // LZ4_loadDict_internal(_ld_slow) on the host (lz4.c:1587-1646): the table a dictionary context carries.
 void build_dict_table_slow(const uint8_t* p, int n, uint32_t* tab)
@@ -1985,12 +2033,45 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     a.l1ChunkOff   = (uint32_t*)((uint8_t*)a.l1ChunkBytes + round_up((size_t)per * maxChunks * 4, 256));
     a.l1Seq        = (uint64_t*)((uint8_t*)a.l1ChunkOff + round_up((size_t)per * maxChunks * 4, 256));
     a.l1Bk         = (uint8_t*)(a.l1Seq + (size_t)per * seqStride);
+    // A call of at most PLZ4HIP_FX_MAX_BLOCKS blocks (0: off) whose blocks may take liblz4's byU32 tables has its parse cut across the
+    // chip (lz4_fx_device.inl) in pieces of PLZ4HIP_FX_PIECE_KIB, guessed starts PLZ4HIP_FX_WARMUP_KIB early.  Its workspace is sized
+    // per call (a group of `per` blocks); when it cannot be had, the call parses as below.
+    FxArgs fx{};
+    bool useFx = false;
+    {
+        int fxMax = kFxMaxBlocks;
+        if (const char* v = getenv("PLZ4HIP_FX_MAX_BLOCKS")) fxMax = atoi(v);
+        if (!mid && !rider && nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock) {
+            int pk = 64, wk = 64;
+            if (const char* v = getenv("PLZ4HIP_FX_PIECE_KIB")) { const int x = atoi(v); if (x >= 1 && x <= 4096) pk = x; }
+            if (const char* v = getenv("PLZ4HIP_FX_WARMUP_KIB")) { const int x = atoi(v); if (x >= 0 && x <= 4096) wk = x; }
+            fx.pb = pk << 10; fx.warm = wk << 10;
+            fx.P = (maxLen + fx.pb - 1) / fx.pb; fx.recStride = fx_rec_stride_host(fx.pb); fx.cnt = c->d_counters;
+            const size_t nP = (size_t)per * fx.P;
+            const size_t offIn = round_up(nP * sizeof(FxPiece), 256), offOut = offIn + nP * kFxTab * 4, offRec = offOut + 2 * nP * kFxTab * 4;
+            const size_t need = offRec + nP * (size_t)fx.recStride * 8;
+            if (c->fxPending && c->fxStream != s) HIPCHK(c, hipStreamWaitEvent(s, c->fxDone, 0));
+            if (need > c->fxBytes) {
+                if (c->fxPending) HIPCHK(c, hipEventSynchronize(c->fxDone));
+                if (c->d_fx) hipFree(c->d_fx);
+                c->d_fx = nullptr; c->fxBytes = 0;
+                if (hipMalloc((void**)&c->d_fx, need) != hipSuccess) { (void)hipGetLastError(); c->d_fx = nullptr; }
+                else c->fxBytes = need;
+            }
+            if (c->d_fx) {
+                fx.meta = (FxPiece*)c->d_fx; fx.tabIn = (uint32_t*)(c->d_fx + offIn); fx.tabOut = (uint32_t*)(c->d_fx + offOut);
+                fx.rec = (uint64_t*)(c->d_fx + offRec);
+                useFx = true;
+            }
+        }
+    }
     for (int g0 = 0; g0 < nb; g0 += per) {
         const int ng = nb - g0 < per ? nb - g0 : per;
         a.blk0 = g0; a.nBlocks = ng;
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         const bool signals = !mid && !getenv("PLZ4HIP_EXP_NO_GATE");            // (the level-1 parse and the duplex launch)
-        if (signals) {
+        if (useFx) a.gate = nullptr;                                            // (neither waits for nor signals the gate)
+        else if (signals) {
             // (only behind a launch that fills the device: the parse launches of the host-buffer calls' chunks -- a third of the
             // wave slots each -- are meant to share it, and behind the gate they would run one after the other: 2560 blocks through
             // host memory 470 -> 680 ms)
@@ -2006,6 +2087,12 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         }
         if (mid && a.hcPfx) hipLaunchKernelGGL(k_hc_mid<true>, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
         else if (mid) hipLaunchKernelGGL(k_hc_mid<false>, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
+        else if (useFx) {
+            // P rounds are always enough (lz4_fx_device.inl); the rounds after the last change find nothing to do
+            if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
+            for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fx_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, r);
+            hipLaunchKernelGGL(k_fx_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx);
+        }
         else if (rider && g0 == 0) {
             // workgroups: what the device holds at once, unless neither role has that much to do
             int P = 1, D = 1, prio = 3;
@@ -2055,6 +2142,11 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         if (!c->l1Done[wsi]) HIPCHK(c, hipEventCreateWithFlags(&c->l1Done[wsi], hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->l1Done[wsi], s));
         c->l1Pending[wsi] = true; c->l1Stream[wsi] = s;
+    }
+    if (useFx) {
+        if (!c->fxDone) HIPCHK(c, hipEventCreateWithFlags(&c->fxDone, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->fxDone, s));
+        c->fxPending = true; c->fxStream = s;
     }
     return PLZ4HIP_OK;
 }
@@ -2118,7 +2210,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
             hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
             for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
             if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-            hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
             HIPCHK(c, hipGetLastError());
         }
     }
@@ -2182,6 +2274,8 @@ int plz4hip_ctx_create(int device, plz4hip_ctx** out)
     // four hardware queues -- the staging slots of the host-buffer calls end up sharing queues and their chunks stop overlapping:
     // 2560 blocks 470 -> 790 ms, found with scripts/host_rate_ab.py)
     if (e == hipSuccess) e = zero_sync(c, c->d_gate, 256);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, 64);
+    if (e == hipSuccess) e = zero_sync(c, c->d_counters, 64);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device);
     int encPer = 0, decPer = 0;
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&encPer, k_encode_rec<kEncWavesPerWg>, 64 * kEncWavesPerWg, 0);
@@ -2223,6 +2317,10 @@ void plz4hip_ctx_destroy(plz4hip_ctx* c)
         if (c->l1[i].d) hipFree(c->l1[i].d);
         if (c->l1Done[i]) hipEventDestroy(c->l1Done[i]);
     }
+    if (c->fxPending) hipEventSynchronize(c->fxDone);
+    if (c->d_fx) hipFree(c->d_fx);
+    if (c->fxDone) hipEventDestroy(c->fxDone);
+    if (c->d_counters) hipFree(c->d_counters);
     if (c->d_lenCopy) hipFree(c->d_lenCopy);
     if (c->d_hcPfx) hipFree(c->d_hcPfx);
     if (c->lenDone) hipEventDestroy(c->lenDone);
@@ -2256,7 +2354,21 @@ int plz4hip_ctx_trim(plz4hip_ctx* c)
     if (c->d_h12) { hipFree(c->d_h12); c->d_h12 = nullptr; c->h12Bytes = 0; }
     if (c->dxPending) { HIPCHK(c, hipEventSynchronize(c->dxDone)); c->dxPending = false; }
     if (c->d_dx) { hipFree(c->d_dx); c->d_dx = nullptr; c->dxBytes = 0; }
+    if (c->fxPending) { HIPCHK(c, hipEventSynchronize(c->fxDone)); c->fxPending = false; }
+    if (c->d_fx) { hipFree(c->d_fx); c->d_fx = nullptr; c->fxBytes = 0; }
     return PLZ4HIP_OK;
+}
+
+int plz4hip_ctx_counters(plz4hip_ctx* c, int64_t* out, int n)
+{
+    if (!c || n < 0 || (n > 0 && !out)) return PLZ4HIP_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    unsigned long long v[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipDeviceSynchronize());                                      // (the ctx's work runs on the callers' streams)
+    HIPCHK(c, copy_sync(c, v, c->d_counters, sizeof v, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n && i < 4; ++i) out[i] = (int64_t)v[i];
+    return 4;
 }
 
 const char* plz4hip_last_error(const plz4hip_ctx* c)
