@@ -88,6 +88,15 @@ DEV int win20_fwd(const Win20& p, const Win20& c)
     return (int)(b1 + (m1 ? b2 : 0u) + (m2 ? b3 : 0u) + (m3 ? b4 : 0u));
 }
 
+// 16 bytes more of a window, [x+20, x+36): see take36 in the grid batch
+struct Ext16 { uint32_t w[4]; };
+DEV int ext16_fwd(const Ext16& p, const Ext16& c)                       // equal leading bytes: 0..16
+{
+    const uint32_t b0 = eq_bytes(p.w[0] ^ c.w[0]), b1 = eq_bytes(p.w[1] ^ c.w[1]), b2 = eq_bytes(p.w[2] ^ c.w[2]), b3 = eq_bytes(p.w[3] ^ c.w[3]);
+    const uint32_t m0 = (b0 == 4u), m1 = m0 & (b1 == 4u), m2 = m1 & (b2 == 4u);
+    return (int)(b0 + (m0 ? b1 : 0u) + (m1 ? b2 : 0u) + (m2 ? b3 : 0u));
+}
+
 // ------------------------------------------------------------------------------------------ PARSE
 // Plays LZ4_compress_generic(noDict, byU16 / byU32, accel 1) over src[0, n), n <= 4 MiB, and writes one record per sequence to
 // seq[] (at most seq_capacity(n)).  Returns their number; *lastAnchor = where the last literals start (lz4.c:1302).
@@ -106,13 +115,75 @@ DEV int win20_fwd(const Win20& p, const Win20& c)
 // by unrolling (grid(S2,S0,S1), grid(S0,S1,S2), grid(S1,S2,S0)), not by copies.
 #if defined(PLZ4_EMU)
 #define SHFLF(x, f, l) ((x)[(l) & 63].f)
-unsigned long long plz4_emu_cnt[8];               // test diagnostics: [0] grid batches, [1] primes, [2] atomics out of order, [3] second rounds for a long match alone, [4] long matches measured, [5] batches whose commit
-                                                  // returned another entry to a probe, [6] batches with a second round, [7] entries outside the registers
+unsigned long long plz4_emu_cnt[16];              // test diagnostics: [0] grid batches, [1] primes, [2] atomics out of order, [3] second rounds for a long match alone, [4] long matches measured, [5] batches whose commit
+                                                  // returned another entry to a probe, [6] batches with a second round, [7] entries outside the registers,
+                                                  // [8] lanes that loaded a candidate window, [9] lanes whose peeked entry passed the position + tag test,
+                                                  // [10] 16-byte loads of the 36-byte window, [11] batches whose first walk executed a match that fills the 20-byte window
 #define EMU_CNT(i, v) (plz4_emu_cnt[(i)] += (unsigned long long)(v))
 #else
 #define SHFLF(x, f, l) plz4_bpermute((x)[0].f, (l))
 #define EMU_CNT(i, v) do {} while (0)
 #endif
+// The block as a bounds-checked buffer, for the loads that only some lanes of a wave need (a candidate's window: 28.6 of 64 lanes on
+// text).  The number of load INSTRUCTIONS a batch issues stays fixed -- the pipeline's waits count instructions -- but a lane that is
+// switched off gets an offset beyond the buffer's end: the range check answers it with zeros and nothing of it reaches the
+// vector cache's address / tag pipeline, which is what the parser waves of a CU saturate (no branch, no exec mask either: a
+// divergent `if` costs 45-58 cycles here).  One descriptor per block, from wave-uniform values, four scalar registers.
+// The lane-emulated build hands a switched-off lane POISON (a pattern that depends on the lane and is neither zero nor the lane's
+// own bytes; plz4_emu_poison = 0: zeros, what the hardware returns), so that the CPU tests show that no result depends on those bytes.
+// PLZ4_PW: compile-time A/B of the parser's window handling (bit 0: candidate loads only for lanes that have a candidate; bit 1: the
+// 36-byte window, take36 in the grid batch); the product is built with both, -DPLZ4_PW=0 is the parser as it was.
+#if !defined(PLZ4_PW)
+#define PLZ4_PW 3
+#endif
+enum : uint32_t { kBufOff = 0x80000000u };                 // beyond any block (<= 4 MiB), and + 36 does not wrap
+#if defined(PLZ4_EMU)
+int plz4_emu_poison = 1;
+struct SrcBuf { const uint8_t* p; };
+DEV SrcBuf src_buf(const uint8_t* src, int n) { (void)n; SrcBuf b; b.p = src; return b; }
+DEV uint32_t emu_poison(int lane, int k) { return plz4_emu_poison ? (0xA5C3960Fu ^ (0x01010101u * (uint32_t)(lane + 1)) ^ (0x10204080u * (uint32_t)k)) : 0u; }
+#else
+struct SrcBuf { __amdgpu_buffer_rsrc_t rs; };
+DEV SrcBuf src_buf(const uint8_t* src, int n)
+{
+    // (uniform by construction, and said so: a descriptor the compiler cannot prove uniform is rebuilt in a loop around every load)
+    const uint64_t a = plz4_readfirstlane((uint64_t)(uintptr_t)src);
+    SrcBuf b; b.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)a, 0, plz4_readfirstlane(n), 0x00020000);
+    return b;
+}
+#endif
+// [x, x+20) for the lanes with `on`; the others issue no access (zeros; poison in the emulation)
+DEV Win20 load_win20_if(const SrcBuf& b, int x, bool on, int lane)
+{
+    Win20 w;
+#if defined(PLZ4_EMU)
+    if (on) { w = load_win20(b.p, x); EMU_CNT(8, 1); }
+    else for (int k = 0; k < 5; ++k) w.w[k] = emu_poison(lane, k);
+#else
+    (void)lane;
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const uint32_t off = on ? (uint32_t)x : (uint32_t)kBufOff;
+    const u32x4_t a = __builtin_amdgcn_raw_buffer_load_b128(b.rs, (int)off, 0, 0);
+    w.w[0] = a.x; w.w[1] = a.y; w.w[2] = a.z; w.w[3] = a.w;
+    w.w[4] = __builtin_amdgcn_raw_buffer_load_b32(b.rs, (int)(off + 16u), 0, 0);
+#endif
+    return w;
+}
+// [x, x+16) likewise
+DEV Ext16 load_ext16_if(const SrcBuf& b, int x, bool on, int lane)
+{
+    Ext16 w;
+#if defined(PLZ4_EMU)
+    if (on) { const v16u_t a = *(const v16u_t*)(b.p + x); w.w[0] = a.w[0]; w.w[1] = a.w[1]; w.w[2] = a.w[2]; w.w[3] = a.w[3]; EMU_CNT(10, 1); }
+    else for (int k = 0; k < 4; ++k) w.w[k] = emu_poison(lane, k + 5);
+#else
+    (void)lane;
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const u32x4_t a = __builtin_amdgcn_raw_buffer_load_b128(b.rs, (int)(on ? (uint32_t)x : (uint32_t)kBufOff), 0, 0);
+    w.w[0] = a.x; w.w[1] = a.y; w.w[2] = a.z; w.w[3] = a.w;
+#endif
+    return w;
+}
 struct GStage { Win20 P; Win20 C; uint32_t h, ent, pk; };     // window, candidate window, slot, own entry, peeked entry
 // diagnostics build (-DPLZ4_STATS, scripts/stats_probe_l1.py): cycle stamps around the sections of a grid batch, each section
 // closed by an explicit wait so that its stamp owns the latency it exposes
@@ -168,6 +239,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
     const int lastProbe  = n - kMfLimit + 1;      // mflimitPlusOne (lz4.c:963)
     const int matchLimit = n - kLastLiterals;     // lz4.c:964
     const int seqDump    = kPiece ? run->seqCap : seq_capacity(n);    // one entry behind the records: where lanes without a record store
+    const SrcBuf sbuf    = src_buf(src, n);       // the block as a buffer (the candidate loads)
     int nseq = 0, anchor = 0;
     STAT_DECL;
     const unsigned long long tBlock0 = STAT_NOW(); (void)tBlock0;
@@ -227,7 +299,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         //           candidates.  The sequential parse is the one consistent outcome (a lane depends on lower lanes only), so the
         //           first round that verifies is it.  Four rounds without agreement, or an entry whose window is not in the
         //           registers: commits taken back, the generic batch takes over.
-        // The loads are unconditional, so the number of memory operations in flight at any point of the loop is fixed.
+        // The loads are unconditional, so the number of memory operations in flight at any point of the loop is fixed (but for the two
+        // of take36, which the rare batch that issues them waits for on the spot).
         auto grid = [&](LVREF(GStage, prev), LVREF(GStage, cur), LVREF(GStage, next), const int base) -> int {
             const int probeStart = hasRe ? rePos : sBase + sIter;
             const int firstPos   = hasIns ? insPos : probeStart;
@@ -262,15 +335,21 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             LANES({ ce[I_] = cur[I_].pk; rent[I_] = 0; W[I_] = cur[I_].C; })
             compare(W, hit, fwd);
             LANES({ eLane[I_] = LANE + kMinMatch + fwd[I_]; })    // lane index just past a match that starts here
+            // (the hits that fill their 20-byte window, 0.44 lanes of a batch on text: if the first walk executes one of them, take36
+            // gives them 16 bytes more)
+            const uint64_t full20 = BALLOT(hit[I_] & (fwd[I_] == 16));
+            const uint64_t x36 = (PLZ4_PW & 2) ? full20 : 0;
             STAT_WAIT_LGKM();
             const unsigned long long ts2 = STAT_NOW(); (void)ts2;
             STAT(P_CYC_LDS, ts2 - ts1);
-            // ---- 3. requests for the batches to come: the peeked candidates of batch k+1 (every lane loads: its candidate, or
-            // its own position when it has none), the window of batch k+2 into the stage batch k-1 is done with
+            // ---- 3. requests for the batches to come: the peeked candidates of batch k+1 (every lane takes part in the load
+            // instructions, only the lanes that have a candidate fetch: load_win20_if), the window of batch k+2 into the stage
+            // batch k-1 is done with
             LANES({
                 const uint32_t q1 = (uint32_t)(base + 64 + LANE), pr = next[I_].pk >> sh;
                 const bool pc = (pr < q1) & (pr + kMaxDist >= q1) & (((next[I_].pk ^ next[I_].ent) & tagMask) == 0);
-                next[I_].C = load_win20(src, (int)(pc ? pr : q1));
+                EMU_CNT(9, pc);
+                next[I_].C = (PLZ4_PW & 1) ? load_win20_if(sbuf, (int)pr, pc, LANE) : load_win20(src, (int)(pc ? pr : q1));
                 if (!kLdsWin) prev[I_].P = load_win20(src, base + 128 + LANE);
             })
             if (kLdsWin == 2) {
@@ -300,6 +379,34 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             const unsigned long long ts3 = STAT_NOW(); (void)ts3;
             STAT(P_CYC_CMP, ts3 - ts2);
 
+            // ---- the 36-byte window.  A match that fills its 20-byte window is not known to the hop: 8.0 % of the batches on text took a
+            // second round for nothing else -- a branchy walk, the commits taken back and put again, and a cold load in the middle
+            // of it -- and 98.5 % of those matches end within 16 bytes more.  So when the first walk has executed such a lane, BEFORE
+            // anything is committed, the lanes of x36 fetch [p + 20, p + 36) and [c + 20, c + 36) (two masked loads: the lines are in
+            // the cache, the candidate's bytes follow bytes that came a batch ago), take 16 + the equal bytes as their length and
+            // the branch-free walk runs once more.  w36 = the lanes whose fwd stands for a 36-byte window: "runs past its window" is
+            // fwd == 32 for them and fwd == 16 for every other lane, among them the ones the verify compares again on a 20-byte
+            // window out of registers.  A match that fills 36 bytes too is measured in a second round as before.
+            // No clamp to matchLimit (n - 5): a grid batch runs only while base + 224 <= n, so p + 36 <= base + 99 <= n - 125; the
+            // piece boundaries (kPiece) and any other value of the 224 have to keep base + 99 + 5 <= n.
+            // (Measured and dropped, DESIGN 3.1: the same loads requested right after step 2 and taken before the first walk --
+            // every batch then waits for a load in the middle of its chain.)
+            uint64_t w36 = 0;
+            auto take36 = [&]() {
+                LV(Ext16, XP); LV(Ext16, XC);
+                LANES({
+                    const bool on = LANE_IN(x36);
+                    XC[I_] = load_ext16_if(sbuf, (int)(ce[I_] >> sh) + 20, on, LANE);
+                    XP[I_] = load_ext16_if(sbuf, base + LANE + 20, on, LANE);
+                })
+                LANES({
+                    const int f = 16 + ext16_fwd(XP[I_], XC[I_]);
+                    fwd[I_] = LANE_IN(x36) ? f : fwd[I_];
+                    eLane[I_] = LANE + kMinMatch + fwd[I_];
+                })
+                w36 = x36;
+            };
+#define PAST_WINDOW() ((BALLOT(fwd[I_] == 16) & ~w36) | (BALLOT(fwd[I_] == 32) & w36))
             const int  cur0 = probeStart - base;                  // first probe lane (>= 64: none in this batch, only the pending insert)
             const bool re0  = hasRe;
             const uint64_t insBit0 = hasIns ? (1ull << (insPos - base)) : 0;
@@ -313,7 +420,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             // the parser over this batch's hits: scalar hop over the recorded matches only, everything else derived per lane
             auto walk = [&]() {
                 const uint64_t hits = BALLOT(hit[I_]);
-                uint64_t specialLeft = hits & BALLOT(fwd[I_] == 16);    // longer than the speculative window: the hop needs its end
+                uint64_t specialLeft = hits & PAST_WINDOW();            // longer than the speculative window: the hop needs its end
                 LV(int, nextHit);      // first recorded match at or after the end of the match that starts here (64: none)
                 LANES({
                     const uint64_t ah = (eLane[I_] < 64) ? (hits >> eLane[I_]) : 0;
@@ -346,7 +453,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         const int ws = ctz64(sp);
                         mm &= (2ull << ws) - 1;                       // what the walk did after it is void
                         const int p0 = base + ws, c0 = (int)(RL(ce, ws) >> sh);
-                        const int mc0 = 16 + wave_common_len(src, p0 + 20, c0 + 20, matchLimit);
+                        const int f0 = RL(fwd, ws);                   // 16 or 32: what its window holds
+                        const int mc0 = f0 + wave_common_len(src, p0 + kMinMatch + f0, c0 + kMinMatch + f0, matchLimit);
                         WL(fwd, ws, mc0);
                         specialLeft &= ~(1ull << ws);
                         const int e1 = ws + kMinMatch + mc0;
@@ -425,8 +533,10 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             bool giveUp = false;
             {
                 const uint64_t hits1 = BALLOT(hit[I_]);
-                const uint64_t special1 = hits1 & BALLOT(fwd[I_] == 16);
                 walk_fast(hits1);
+                EMU_CNT(11, (mm & full20) != 0);
+                if (mm & x36) { take36(); walk_fast(hits1); }
+                const uint64_t special1 = hits1 & PAST_WINDOW();
                 const unsigned long long tc0 = STAT_NOW(); (void)tc0;
                 const uint64_t EL = E;
                 // (a lane that is not executed exchanges a 0: the slot stays as it is)
@@ -457,6 +567,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         const bool u = LANE_IN(upd);
                         hit[I_] = u ? hitN[I_] : hit[I_]; fwd[I_] = u ? fwdN[I_] : fwd[I_]; eLane[I_] = LANE + kMinMatch + fwd[I_];
                     })
+                    w36 &= ~upd;                 // (their lengths are the 20-byte register window's now)
                 }
                 STAT(P_CYC_REFRESH, STAT_NOW() - tc0);
                 EMU_CNT(5, upd != 0);
@@ -495,9 +606,11 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         const uint64_t diff2 = upd2 & BALLOT(hitN[I_] != hit[I_] || fwdN[I_] != fwd[I_] || fwdN[I_] == 16);
                         if (!diff2) break;                                     // same walk, same executed set: only offsets moved
                         LANES({ if (LANE_IN(upd2)) { hit[I_] = hitN[I_]; fwd[I_] = fwdN[I_]; eLane[I_] = LANE + kMinMatch + fwdN[I_]; } })
+                        w36 &= ~upd2;
                     }
                 }
             }
+#undef PAST_WINDOW
             if (giveUp) {
                 if (committed) {
                     const uint64_t cm = committed;
@@ -573,7 +686,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         S0[I_].pk  = ((const uint32_t*)tab)[S0[I_].h];
                         const uint32_t q0 = (uint32_t)(base + LANE), pr = S0[I_].pk >> sh;
                         const bool pc = pr < q0 && pr + kMaxDist >= q0 && ((S0[I_].pk ^ S0[I_].ent) & tagMask) == 0;
-                        S0[I_].C = load_win20(src, (int)(pc ? pr : q0));
+                        EMU_CNT(9, pc);
+                        S0[I_].C = (PLZ4_PW & 1) ? load_win20_if(sbuf, (int)pr, pc, LANE) : load_win20(src, (int)(pc ? pr : q0));
                         if (kLdsWin) pf[I_] = ld32u(src + min_(base + 128 + 4 * LANE, n - 4));
                     })
                     LDS_ORDER();

@@ -1,5 +1,6 @@
 """Diagnostics: build the engine with -DPLZ4_STATS into scripts/_build/libplz4hip_stats.so, run a level-1 encode over B blocks
-of T text and print the parse kernel's per-section cycle counters (lz4_seq_device.inl).  Not part of the product or the tests."""
+of T text and print the parse kernel's per-section cycle counters (lz4_seq_device.inl).  Not part of the product or the tests.
+stats_probe_l1.py [B [lib.so]]: with a library given (a -DPLZ4_STATS build made elsewhere, e.g. of another commit) nothing is compiled."""
 import ctypes as C, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,10 +9,11 @@ import torch
 from plz4_amd import synth, _native, build as B_
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 2560
-so = os.path.join(ROOT, "scripts", "_build", "libplz4hip_stats.so")
+so = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.join(ROOT, "scripts", "_build", "libplz4hip_stats.so")
 os.makedirs(os.path.dirname(so), exist_ok=True)
-subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-shared", "-DPLZ4_STATS",
-                       "-Wno-unused-value", "-I", os.path.join(ROOT, "include"), "-o", so] + B_.sources())
+if len(sys.argv) <= 2:
+    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-shared", "-DPLZ4_STATS",
+                           "-Wno-unused-value", "-I", os.path.join(ROOT, "include"), "-o", so] + B_.sources())
 _native.LIB_PATH = so
 eng = _native.Engine(0)
 L = eng.L
