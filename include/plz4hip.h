@@ -36,13 +36,19 @@
  * to 4 MiB + 8 of output; 0 turns it off) is cut across the whole chip and keeps 8 bytes per input byte + 4 per output byte of
  * the call's blocks (about 50 MiB per 4 MiB block) until plz4hip_ctx_trim; results and error codes are LZ4_decompress_safe's
  * either way (a block that path will not answer for is decoded by the one-wavefront decoder inside the call).
+ * Blocks with history outside the block take the same path under the same conditions (decompress_batch_dict, decode_records_ex
+ * with a dictionary and / or linked = 1, decode_records_chains): the call has one pointer space, a match that starts in front of
+ * its block points into an earlier block's output, the window the call came in with or the dictionary, and the jump rounds follow
+ * the call's total output (up to 32).  A chain is answered up to its first block that is not plainly good; the one-wavefront chain
+ * walk goes on from there inside the call, from the window the good blocks leave.  PLZ4HIP_DX_LINKED=0 keeps such calls on the
+ * one-wavefront kernels (a switch for tests and A/B runs; PLZ4HIP_DX_MAX_BLOCKS=0 does so too).
  * An ENCODE call of few blocks at level 1 (compress_batch, encode_records, dev_compress with maxLen > 0, dev_encode_records,
  * dev_encode_body; up to PLZ4HIP_FX_MAX_BLOCKS = 128 blocks, 0 turns it off) whose largest block is 65 547 bytes .. 4 MiB (liblz4's
  * byU32 tables) has its parse cut across the whole chip: pieces of PLZ4HIP_FX_PIECE_KIB (64) parsed by a wave each, in rounds
  * until every piece starts from the exact state its predecessor ends in; a guessed start begins PLZ4HIP_FX_WARMUP_KIB (64) early.
  * Output, results and error codes are exactly those of the one-wave parse; smaller blocks of such a call are parsed whole.
  * Duplex calls and level 2 keep their kernels.  It keeps about 3 bytes per input byte of the call's blocks (the pieces' tables
- * and records) until plz4hip_ctx_trim.  plz4hip_ctx_counters reports what these two few-block paths did.
+ * and records) until plz4hip_ctx_trim.  plz4hip_ctx_counters reports what these few-block paths did.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
  * calls, rounds 1-3), PLZ4HIP_HC12_LAZY (level 12 with its searches made on demand), PLZ4HIP_HC_OVERLAP_OFF / _MIN / _GROUPS (levels 3..11: a call of 2048
  * blocks or more runs in four or more groups, the list builder of the next group on a second stream of the ctx beside the walk
@@ -88,8 +94,9 @@ void        plz4hip_ctx_destroy(plz4hip_ctx* ctx);
 const char* plz4hip_last_error(const plz4hip_ctx* ctx);       /* text of the last PLZ4HIP_E_* on this ctx */
 int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release staging buffers and HC workspaces (waits for work in flight) */
 /* Waits for the ctx's work, then writes up to n counters to out: [0] blocks encoded by the few-block level-1 path, [1] its rounds
- * in the last such call, [2] pieces it parsed more than once, [3] blocks answered by the few-block decoder.  Returns how many
- * counters there are (4), or PLZ4HIP_E_*. */
+ * in the last such call, [2] pieces it parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history
+ * outside the block (dictionary, linked) answered by it, [5] its jump rounds in the last such call.  Returns how many counters
+ * there are (6), or PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */
@@ -154,9 +161,12 @@ int plz4hip_decode_records(plz4hip_ctx* ctx, int nBlocks,
  *                   blk.CompressToBlk takes no fallback) -- a drop-in caller checks the stored bit of rec[i] for
  *                   linked && level > 1 and reports the error (the host layer and the Go shim do).
  *    decode_records_ex: independent blocks + dict: every block against `dict` (compress/decompress.go:42-58);
- *                   linked: a serial chain over the batch; `window` (64 KiB, caller-owned) / `*windowLen` carry
+ *                   linked: the batch is one chain; `window` (64 KiB, caller-owned) / `*windowLen` carry
  *                   compress.DictT (compress/dict.go:5-56) across calls: initialise with the dictionary's last 64 KiB
  *                   (or length 0).  As in the reference, a stored block does not update the window.
+ *                   A call of few blocks (see DECODE above) decodes all of them at once across the chip -- a block's
+ *                   history is the output of the blocks before it -- and hands back the same results, status and
+ *                   window as the walk of one wavefront that calls of many blocks run.
  * ------------------------------------------------------------------------------------------------------- */
 typedef struct plz4hip_dict plz4hip_dict;
 int  plz4hip_dict_create(plz4hip_ctx* ctx, const void* dict, int dictLen, plz4hip_dict** out);
@@ -175,7 +185,7 @@ int plz4hip_decode_records_ex(plz4hip_ctx* ctx, int nBlocks, const void* const* 
                               void* window, int* windowLen, void* const* dst, int32_t* result, int32_t* status);
 /* Linked decode of SEVERAL frames in one call.  The blocks of one linked frame are a serial chain ("replicas
  * only"), chains of different frames share nothing: chain k = records [chainFirst[k], chainFirst[k+1]) (chainFirst[0] == 0,
- * nChains + 1 entries), one wavefront each.  windows = nChains x 64 KiB, windowLen[nChains]: the compress.DictT state of every
+ * nChains + 1 entries): the few-block path over all chains at once, or (many blocks) one wavefront per chain.  windows = nChains x 64 KiB, windowLen[nChains]: the compress.DictT state of every
  * chain, in/out, exactly as `window` / `windowLen` of plz4hip_decode_records_ex(linked = 1); per-block result / status likewise
  * (a chain stops at its first bad block, the other chains go on).  No counterpart in the reference: a server that decodes
  * many linked frames (rdr.go:339-341 runs each one on a single goroutine) hands them over together. */

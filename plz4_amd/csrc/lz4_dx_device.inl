@@ -152,9 +152,18 @@ DEV int dx_stitch(const uint8_t* __restrict__ in, const int n, const int cap, co
 
 // a match as pointers: ptr[op + i] = op + i - offset.  An overlapping match (offset < len) points into itself, which is what
 // its bytes are (lz4.c:2406-2414).
+// kHist (blocks with history outside the block, see dxl_* below): a source before the block's start is written down as the distance
+// in front of the block, tagged -- kDxlTag | (distance - 1) -- and resolved once every block's output length is known (dxl_resolve).
+enum : uint32_t { kDxlTag = 0x80000000u };
+template <bool kHist = false>
 DEV void dx_fill_match(uint32_t* __restrict__ ptr, const int64_t op, const int offset, const int len)
 {
-    LANES({ for (int i = LANE; i < len; i += 64) ptr[op + i] = (uint32_t)(op + i - offset); })
+    LANES({
+        for (int i = LANE; i < len; i += 64) {
+            const int sp = (int)op + i - offset;                             // (sp < 0: tag | (-sp - 1), which is sp with its low 31 bits flipped)
+            ptr[op + i] = kHist ? (uint32_t)(sp ^ ((sp >> 31) & 0x7FFFFFFF)) : (uint32_t)sp;
+        }
+    })
 }
 
 // The vector path of the one-wave decoder (wave_decode_plain_batch, lz4_device.inl) with the copies taken out: 64 lanes look at
@@ -251,6 +260,11 @@ DEV int dx_plain_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ ds
 // (lz4.c:2083-2209) up to ipStop and returns -1 for anything that loop would hand to the safe loop or reject; the tail unit walks to
 // the end of the block under both loops' rules (:2215-2435).  Returns the output position reached, or -1: the block is left to the
 // one-wave decoder, whose verdict is the reference's.  An offset of 0 (liblz4 zero-fills, :499-507) is left to it as well.
+// kHist: the block has history in front of it (LZ4_decompress_safe_usingDict's external-dictionary form, lz4.c:2166-2196, :2358-2384):
+// a match may start up to 65535 bytes before the block.  Its end-of-output test (op + length > oend - LASTLITERALS) is the one the
+// safe loop makes for every match, and the fast loop only sees matches that end 64 bytes before oend; whether the history is long
+// enough for the offset (checkOffset, :2161, :2356) is told by dxl_resolve.
+template <bool kHist = false>
 DEV int64_t wave_dx_fill(const uint8_t* __restrict__ src, const int n, uint8_t* __restrict__ dst, const int cap, uint32_t* __restrict__ ptr,
                          const int ip0, const int64_t op0, const int ipStop, const bool tail)
 {
@@ -291,8 +305,8 @@ DEV int64_t wave_dx_fill(const uint8_t* __restrict__ src, const int n, uint8_t* 
                 ml += a + kMinMatch;
             } else ml += kMinMatch;
             if (op + ml >= oend - 64) { if (!tail) return -1; fast = false; goto safe_match; }
-            if (mpos < 0 || offset == 0) return -1;                            // lz4.c:2161
-            dx_fill_match(ptr, op, offset, (int)ml);
+            if ((!kHist && mpos < 0) || offset == 0) return -1;                // lz4.c:2161
+            dx_fill_match<kHist>(ptr, op, offset, (int)ml);
             op += ml;
             continue;
         }
@@ -334,9 +348,9 @@ match_len:
         }
         ml += kMinMatch;
 safe_match:
-        if (mpos < 0 || offset == 0) return -1;                                // lz4.c:2356
-        if (op + ml > oend - kLastLiterals) return -1;                         // lz4.c:2421-2423
-        dx_fill_match(ptr, op, offset, (int)ml);
+        if ((!kHist && mpos < 0) || offset == 0) return -1;                    // lz4.c:2356
+        if (op + ml > oend - kLastLiterals) return -1;                         // lz4.c:2421-2423 (== :2360-2363 for a match out of the history)
+        dx_fill_match<kHist>(ptr, op, offset, (int)ml);
         op += ml;
     }
     return op;
@@ -367,6 +381,130 @@ DEV void dx_gather(uint8_t* __restrict__ out, const uint32_t* __restrict__ ptr, 
             if (p < outLen) { const uint32_t q = ptr[p]; if (q != (uint32_t)p) out[p] = out[q]; }
         }
     })
+}
+
+// ---- Blocks with history outside the block: linked blocks (a chain: block i's window is the tail of what the blocks before it
+// produced, compress/dict.go:28-41) and independent blocks under a dictionary (chains of one).  The token chain needs no history,
+// so stages A and B run on every block of the call at once; the copy chain simply crosses the blocks' borders.  The call has ONE
+// pointer space: byte pos of block b is b * P + pos, and behind the last block (from nb * P on) lie 64 Ki indices per chain for
+// the history the call came in with (the chain's window, or the dictionary), which like the literals are fixed points.
+//   C' wave_dx_fill<true>  as C; a source in front of the block is written down as a tagged distance
+//   R  dxl_resolve         once the fill has told every block's output length: block-relative pointers become global ones, tagged
+//                          distances the byte they mean -- walking back over the outputs of the chain's earlier compressed blocks
+//                          (stored blocks do not enter the window: sync/reader.go:75-78), then into the incoming history.  A
+//                          distance beyond all of that flags the block (checkOffset).
+//   D' dxl_jump, E' dxl_gather   as D and E over global pointers; the rounds follow the call's total output.
+// A chain is answered up to its first block that is not plainly good; from there on the one-wave chain walk takes over, starting
+// from the window the good blocks leave (dxl_window).
+enum : int { kDxlMaxRounds = 32, kDxlHist = 65536 };
+
+struct DxlCall {
+    uint32_t*       ptr;   int64_t P;   int nb;                 // ptr[b * P + pos]
+    const DxInfo*   info;                                       // per block: bad, outLen
+    const int32_t*  len;                                        // per block: < 0: not a compressed block (stored / not sane); null: all are
+    const int32_t*  first;                                      // per block: the first block of its chain (null: its own)
+    const int32_t*  chain;                                      // per block: its chain's number (null: 0, one history for all)
+    const uint8_t*  hist;  int64_t histStride;                  // chain ch's incoming history: hist + ch * histStride, histLen bytes
+    const int*      histLen;  int histLenAll;
+    uint8_t*        dst;   int64_t dstStride;
+};
+DEV uint32_t dxl_hist0(const DxlCall& c) { return (uint32_t)((int64_t)c.nb * c.P); }
+
+// the byte d (1 .. 65535) in front of block b's start; ~0u: the history is shorter than that
+DEV uint32_t dxl_source(const DxlCall& c, const int b, uint32_t d)
+{
+    const int first = c.first ? c.first[b] : b;
+    for (int j = b - 1; j >= first; --j) {
+        if (c.len && c.len[j] < 0) continue;
+        const uint32_t o = (uint32_t)c.info[j].outLen;
+        if (d <= o) return (uint32_t)((int64_t)j * c.P + o - d);
+        d -= o;
+    }
+    const int ch = c.chain ? c.chain[b] : 0;
+    const int w = c.histLen ? c.histLen[ch] : c.histLenAll;
+    if (w > 0 && d <= (uint32_t)w) return dxl_hist0(c) + (uint32_t)ch * kDxlHist + ((uint32_t)w - d);
+    return ~0u;
+}
+// R.  The 64 x 4 entries of block b from p0 on, up to lim; false: a match reaches behind the history.  Run over ALL P entries of
+// EVERY block, flagged ones included: whatever a later block's pointers lead to is then an index of the call's space.
+DEV bool dxl_resolve(const DxlCall& c, const int b, const int p0, const int lim)
+{
+    LV(int, no);
+    const uint32_t base = (uint32_t)((int64_t)b * c.P);
+    LANES({
+        no[I_] = 0;
+        for (int k = 0; k < 4; ++k) {
+            const int p = p0 + 4 * LANE + k;
+            if (p < lim) {
+                const uint32_t v = c.ptr[base + p];
+                uint32_t g = base + v;
+                if (v & kDxlTag) { g = dxl_source(c, b, (v & ~kDxlTag) + 1u); if (g == ~0u) { g = base + (uint32_t)p; no[I_] = 1; } }
+                c.ptr[base + p] = g;
+            }
+        }
+    })
+    return BALLOT(no[I_]) == 0;
+}
+// D'.  As dx_jump; indices from hist0 on (the incoming history) are fixed points without an entry of their own.  All of a lane's
+// loads come before its stores (the four gathers are in flight together, and no pointer sees one moved by the same step).
+DEV bool dxl_jump(uint32_t* __restrict__ ptr, const uint32_t hist0, const uint32_t base, const int p0, const int outLen)
+{
+    LV(v16u_t, nv); LV(int, mv);
+    LANES({
+        mv[I_] = 0;
+        for (int k = 0; k < 4; ++k) {
+            const int p = p0 + 4 * LANE + k;
+            nv[I_].w[k] = 0;
+            if (p < outLen) {
+                const uint32_t g = base + (uint32_t)p, q = ptr[g];
+                if (q != g && q < hist0) { const uint32_t r = ptr[q]; if (r != q) { nv[I_].w[k] = r; mv[I_] |= 1 << k; } }
+            }
+        }
+    })
+    LANES({
+        for (int k = 0; k < 4; ++k) if ((mv[I_] >> k) & 1) ptr[base + (uint32_t)(p0 + 4 * LANE + k)] = nv[I_].w[k];
+    })
+    return BALLOT(mv[I_]) != 0;
+}
+// E'.  The literal is in the output of the block that owns it, or in the incoming history.
+DEV void dxl_gather(const DxlCall& c, const int b, const int p0, const int outLen)
+{
+    const uint32_t base = (uint32_t)((int64_t)b * c.P), hist0 = dxl_hist0(c);
+    uint8_t* const out = c.dst + (int64_t)b * c.dstStride;
+    LANES({
+        for (int k = 0; k < 4; ++k) {
+            const int p = p0 + 4 * LANE + k;
+            if (p < outLen) {
+                const uint32_t g = base + (uint32_t)p, q = c.ptr[g];
+                if (q != g) {
+                    if (q >= hist0) { const uint32_t h = q - hist0; out[p] = c.hist[(int64_t)(h >> 16) * c.histStride + (h & 65535u)]; }
+                    else { const uint32_t jb = q / (uint32_t)c.P; out[p] = c.dst[(int64_t)jb * c.dstStride + (q - jb * (uint32_t)c.P)]; }
+                }
+            }
+        }
+    })
+}
+// a block's row of moved[] (kDxlMaxRounds + 1 entries, `rounds` of them launched): has it come to rest, and after how many rounds
+DEV bool dxl_converged(const uint32_t* moved, const int rounds) { return rounds > 0 && moved[rounds - 1] == 0u; }
+DEV int  dxl_rounds_of(const uint32_t* moved, const int rounds) { int r = 0; while (r < rounds && moved[r]) ++r; return r < rounds ? r + 1 : rounds; }
+
+// The window a chain's blocks [first, cut) leave: compress.DictT.Update block by block gives the last 64 KiB of (incoming window,
+// outputs of the compressed blocks).  Written to winB (winA is read); returns its length, or -1: nothing was produced, the window stays.
+DEV int dxl_window(const DxlCall& c, const int first, const int cut, const uint8_t* winA, const int winLen, uint8_t* winB)
+{
+    int64_t sum = 0;
+    for (int j = cut - 1; j >= first && sum < kDxlHist; --j) if (!(c.len && c.len[j] < 0)) sum += c.info[j].outLen;
+    if (sum == 0) return -1;
+    const int s = (int)min_(sum, (int64_t)kDxlHist), keep = min_(winLen, kDxlHist - s);
+    wave_copy(winB, winA + (winLen - keep), keep);
+    int pos = keep + s;
+    for (int j = cut - 1; j >= first && pos > keep; --j) {
+        if (c.len && c.len[j] < 0) continue;
+        const int o = c.info[j].outLen, take = min_(o, pos - keep);
+        wave_copy(winB + (pos - take), c.dst + (int64_t)j * c.dstStride + (o - take), take);
+        pos -= take;
+    }
+    return keep + s;
 }
 
 }  // namespace plz4

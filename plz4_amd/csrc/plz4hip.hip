@@ -92,6 +92,9 @@ struct CodecArgs {
     uint32_t*       gate;       uint32_t gateSeq;
     const int64_t*  dxSrcOff;   const int32_t* dxLen;                       // records: where a block's payload starts in src and its size (-1: not this path's)
     int32_t*        dxHashBad;                                              // records: the payload's xxh32 does not match (k_dx_rec_hash)
+    // ... with history outside the block (dxl_*, lz4_dx_device.inl): per block the first block and the number of its chain, its row
+    // of moved flags (kDxlMaxRounds + 1), whether the path has answered it; the jump rounds launched
+    int32_t*        dxlFirst;   int32_t* dxlChain;   uint32_t* dxlMoved;   int32_t* dxlGood;   int dxlRounds;
 };
 
 __device__ __forceinline__ int next_block(uint32_t* q)
@@ -426,6 +429,7 @@ __global__ __launch_bounds__(64) void k_decode_rec_dict(CodecArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t dl[kDecLdsBytes];
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
+        if (a.dxlGood && a.dxlGood[i]) continue;                             // (answered by the few-block path)
         int r, st; bool stored;
         decode_one_record(a, i, a.dict, a.dictLen, &r, &st, &stored, dl);
         if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
@@ -434,6 +438,33 @@ __global__ __launch_bounds__(64) void k_decode_rec_dict(CodecArgs a)
 
 // Linked blocks: a serial chain, one wave.  The window follows compress.DictT.Update (compress/dict.go:28-41) and is
 // NOT updated by stored blocks (sync/reader.go:75-78, async/reader.go:149-163) -- the reference's behaviour, kept.
+// The records [first, last) of chain ch from the window (winA, winLen) on; dead: an earlier record of the chain has failed.
+__device__ __forceinline__ void linked_walk(const CodecArgs& a, const int ch, const int first, const int last, uint8_t* const win0,
+                                            uint8_t* winA, uint8_t* winB, int winLen, bool dead, uint8_t* dl)
+{
+    for (int i = first; i < last; ++i) {
+        int r = 0, st = PLZ4HIP_BLK_CORRUPT; bool stored = false;
+        if (!dead) decode_one_record(a, i, winA, winLen, &r, &st, &stored, dl);
+        if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
+        if (st != PLZ4HIP_BLK_OK) { dead = true; continue; }             // first error ends the stream
+        if (stored) continue;
+        const uint8_t* out = a.dst + (int64_t)i * a.dstStride;
+        WAVE_FENCE();
+        if (r >= 65536) { wave_copy(winB, out + (r - 65536), 65536); winLen = 65536; }
+        else {
+            int keep = winLen;
+            if (winLen + r > 65536) keep = 65536 - r;
+            wave_copy(winB, winA + (winLen - keep), keep);
+            wave_copy(winB + keep, out, r);
+            winLen = keep + r;
+        }
+        WAVE_FENCE();
+        uint8_t* t = winA; winA = winB; winB = t;
+    }
+    // leave the live window in the first half for the next call
+    if (winA != win0) { WAVE_FENCE(); wave_copy(win0, winA, winLen); }
+    if ((threadIdx.x & 63u) == 0) a.windowLen[ch] = winLen;
+}
 __global__ __launch_bounds__(64) void k_decode_rec_linked(CodecArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t dl[kDecLdsBytes];
@@ -442,37 +473,14 @@ __global__ __launch_bounds__(64) void k_decode_rec_linked(CodecArgs a)
         const int first = a.chainFirst ? a.chainFirst[ch] : 0;
         const int last  = a.chainFirst ? a.chainFirst[ch + 1] : a.nBlocks;
         uint8_t* const win0 = a.window + (size_t)ch * 131072;
-        uint8_t* winA = win0; uint8_t* winB = win0 + 65536;
-        int winLen = a.windowLen[ch];
-        bool dead = false;
-        for (int i = first; i < last; ++i) {
-            int r = 0, st = PLZ4HIP_BLK_CORRUPT; bool stored = false;
-            if (!dead) decode_one_record(a, i, winA, winLen, &r, &st, &stored, dl);
-            if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
-            if (st != PLZ4HIP_BLK_OK) { dead = true; continue; }             // first error ends the stream
-            if (stored) continue;
-            const uint8_t* out = a.dst + (int64_t)i * a.dstStride;
-            WAVE_FENCE();
-            if (r >= 65536) { wave_copy(winB, out + (r - 65536), 65536); winLen = 65536; }
-            else {
-                int keep = winLen;
-                if (winLen + r > 65536) keep = 65536 - r;
-                wave_copy(winB, winA + (winLen - keep), keep);
-                wave_copy(winB + keep, out, r);
-                winLen = keep + r;
-            }
-            WAVE_FENCE();
-            uint8_t* t = winA; winA = winB; winB = t;
-        }
-        // leave the live window in the first half for the next call
-        if (winA != win0) { WAVE_FENCE(); wave_copy(win0, winA, winLen); }
-        if ((threadIdx.x & 63u) == 0) a.windowLen[ch] = winLen;
+        linked_walk(a, ch, first, last, win0, win0, win0 + 65536, a.windowLen[ch], false, dl);
     }
 }
 
 __global__ __launch_bounds__(64) void k_decode_raw_dict(CodecArgs a)
 {
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
+        if (a.dxlGood && a.dxlGood[i]) continue;                             // (answered by the few-block path)
         const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
         const int r = wave_decode_block(a.src + (int64_t)i * a.srcStride, a.srcLen[i], a.dst + (int64_t)i * a.dstStride, cap, a.dict, a.dictLen);
         if ((threadIdx.x & 63u) == 0) a.result[i] = r;
@@ -1104,6 +1112,127 @@ __global__ __launch_bounds__(64) void k_dx_rec_hash(CodecArgs a)
     if ((threadIdx.x & 63u) == 0) a.dxHashBad[b] = bad;
 }
 
+// ---- ... of blocks with history outside the block (dxl_*, lz4_dx_device.inl): k_dx_rec_prep / k_dx_rec_hash / k_dx_tables /
+// k_dx_stitch as above, then k_dxl_link, k_dxl_fill, k_dxl_resolve, the jump rounds, k_dxl_gather and, per chain, k_dxl_finish
+// (linked) or, per block, k_dxl_verdict (independent blocks under a dictionary; the flagged ones run k_decode_*_dict behind).
+__device__ __forceinline__ DxlCall dxl_call(const CodecArgs& a)
+{
+    DxlCall c;
+    c.ptr = a.dxPtr; c.P = a.dxPtrStride; c.nb = a.nBlocks; c.info = a.dxInfo; c.len = a.dxLen; c.first = a.dxlFirst; c.chain = a.dxlChain;
+    if (a.linked) { c.hist = a.window; c.histStride = 131072; c.histLen = a.windowLen; c.histLenAll = 0; }
+    else { c.hist = a.dict; c.histStride = 0; c.histLen = nullptr; c.histLenAll = (a.dict && a.dictLen > 0) ? a.dictLen : 0; }
+    c.dst = a.dst; c.dstStride = a.dstStride;
+    return c;
+}
+__device__ __forceinline__ bool dxl_good(const CodecArgs& a, int b)
+{
+    return dx_len(a, b) >= 0 && !a.dxInfo[b].bad && !(a.dxHashBad && a.dxHashBad[b])
+        && dxl_converged(a.dxlMoved + (int64_t)b * (kDxlMaxRounds + 1), a.dxlRounds);
+}
+__global__ __launch_bounds__(256) void k_dxl_link(CodecArgs a, unsigned long long* cnt)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) cnt[5] = 0;                                                 // (plz4hip_ctx_counters: jump rounds of the last such call)
+    if (i >= a.nBlocks) return;
+    int first = i, ch = 0;
+    if (a.linked) {
+        first = 0;
+        if (a.chainFirst) { while (ch + 1 < a.nChains && a.chainFirst[ch + 1] <= i) ++ch; first = a.chainFirst[ch]; }
+    }
+    a.dxlFirst[i] = first; a.dxlChain[i] = ch; a.dxlGood[i] = 0;
+    for (int r = 0; r <= kDxlMaxRounds; ++r) a.dxlMoved[(int64_t)i * (kDxlMaxRounds + 1) + r] = 0;
+}
+__global__ __launch_bounds__(64) void k_dxl_fill(CodecArgs a)
+{
+    const int j = blockIdx.x, b = blockIdx.y;
+    DxInfo* const inf = a.dxInfo + b;
+    if (inf->bad || j > inf->tailFrom) return;
+    const int jt = inf->tailFrom;
+    const DxUnit* const units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
+    const DxUnit u = units[j];
+    if (j < jt && u.ip < 0) return;
+    const int64_t r = wave_dx_fill<true>(dx_src(a, b), dx_len(a, b), a.dst + (int64_t)b * a.dstStride, dx_cap(a, b),
+                                         a.dxPtr + (int64_t)b * a.dxPtrStride, u.ip, u.op, u.stop, j == jt);
+    bool ok = r >= 0;
+    if (ok && j < jt) {
+        int k = j + 1; while (k < jt && units[k].ip < 0) ++k;
+        ok = units[k].op == (int)r;
+    }
+    if ((threadIdx.x & 63u) == 0) { if (!ok) atomicOr(&inf->bad, 1); else if (j == jt) inf->outLen = (int)r; }
+}
+__global__ __launch_bounds__(256) void k_dxl_resolve(CodecArgs a)
+{
+    const int b = blockIdx.y, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    if (p0 >= a.dxPtrStride) return;
+    if (!dxl_resolve(dxl_call(a), b, p0, (int)a.dxPtrStride) && (threadIdx.x & 63u) == 0) atomicOr(&a.dxInfo[b].bad, 1);
+}
+__global__ __launch_bounds__(256) void k_dxl_jump(CodecArgs a)
+{
+    const int b = blockIdx.y, r = a.dxRound;
+    const DxInfo* const inf = a.dxInfo + b;
+    uint32_t* const moved = a.dxlMoved + (int64_t)b * (kDxlMaxRounds + 1);
+    if (inf->bad || (r > 0 && !moved[r - 1])) return;
+    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    if (p0 >= outLen) return;
+    if (dxl_jump(a.dxPtr, (uint32_t)((int64_t)a.nBlocks * a.dxPtrStride), (uint32_t)((int64_t)b * a.dxPtrStride), p0, outLen) && (threadIdx.x & 63u) == 0) moved[r] = 1u;
+}
+__global__ __launch_bounds__(256) void k_dxl_gather(CodecArgs a)
+{
+    const int b = blockIdx.y;
+    const DxInfo* const inf = a.dxInfo + b;
+    if (inf->bad) return;
+    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    if (p0 >= outLen) return;
+    dxl_gather(dxl_call(a), b, p0, outLen);
+}
+// independent blocks under a dictionary: which blocks the path answers
+__global__ __launch_bounds__(256) void k_dxl_verdict(CodecArgs a, unsigned long long* cnt)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.nBlocks || !dxl_good(a, i)) return;
+    a.dxlGood[i] = 1;
+    a.result[i] = a.dxInfo[i].outLen;
+    if (a.status) a.status[i] = PLZ4HIP_BLK_OK;
+    atomicAdd(&cnt[4], 1ull);                                               // (plz4hip_ctx_counters: blocks this path answered)
+    atomicMax(&cnt[5], (unsigned long long)dxl_rounds_of(a.dxlMoved + (int64_t)i * (kDxlMaxRounds + 1), a.dxlRounds));
+}
+// linked blocks, one wave per chain: the chain's good blocks are answered (a stored block among them is copied out here and does
+// not enter the window), the window they leave is laid down, and from the first block that is not plainly good the one-wave walk
+// goes on (linked_walk: its own verdict for that block, CORRUPT for what follows, the window as it was in front of it).
+__global__ __launch_bounds__(64) void k_dxl_finish(CodecArgs a, unsigned long long* cnt)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t dl[kDecLdsBytes];
+    const int ch = blockIdx.x;
+    const int first = a.chainFirst ? a.chainFirst[ch] : 0;
+    const int last  = a.chainFirst ? a.chainFirst[ch + 1] : a.nBlocks;
+    const DxlCall c = dxl_call(a);
+    uint8_t* const win0 = a.window + (size_t)ch * 131072;
+    uint8_t* winA = win0; uint8_t* winB = win0 + 65536;
+    int winLen = plz4_readfirstlane(a.windowLen[ch]);
+    bool dead = false;
+    int i = first, taken = 0, rounds = 0;
+    for (; i < last; ++i) {
+        if (plz4_readfirstlane(a.dxLen[i]) >= 0) {
+            if (!plz4_readfirstlane((int)dxl_good(a, i))) break;
+            if ((threadIdx.x & 63u) == 0) { a.result[i] = a.dxInfo[i].outLen; a.status[i] = PLZ4HIP_BLK_OK; }
+            ++taken;
+            const int rr = plz4_readfirstlane(dxl_rounds_of(a.dxlMoved + (int64_t)i * (kDxlMaxRounds + 1), a.dxlRounds));
+            if (rr > rounds) rounds = rr;
+        } else {
+            int r, st; bool stored;
+            decode_one_record(a, i, nullptr, 0, &r, &st, &stored, dl);      // a stored block, or a record that fails the frame reader's checks
+            if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
+            if (st != PLZ4HIP_BLK_OK) { dead = true; ++i; break; }
+        }
+    }
+    WAVE_FENCE();
+    const int t = dxl_window(c, first, i, winA, winLen, winB);
+    WAVE_FENCE();
+    if (t >= 0) { uint8_t* x = winA; winA = winB; winB = x; winLen = t; }
+    if (taken && (threadIdx.x & 63u) == 0) { atomicAdd(&cnt[4], (unsigned long long)taken); atomicMax(&cnt[5], (unsigned long long)rounds); }
+    linked_walk(a, ch, i, last, win0, winA, winB, winLen, dead, dl);
+}
+
 __global__ __launch_bounds__(64) void k_decode_raw(CodecArgs a)
 {
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
@@ -1359,7 +1488,8 @@ struct plz4hip_ctx {
     uint8_t*     d_fx = nullptr; size_t fxBytes = 0;
     hipEvent_t   fxDone = nullptr; hipStream_t fxStream = nullptr; bool fxPending = false;
     // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
-    // parsed more than once, [3] blocks answered by the few-block decoder
+    // parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history outside the block (dictionary,
+    // linked) answered by it, [5] its jump rounds in the last such call
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call.  One job at a time like the workspaces: a call on another
     // stream waits (on the device) for the event behind the last job's kernels before it overwrites the copy.
@@ -1644,11 +1774,6 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         if (nb > c->hcPfxCap) {
             if (c->hcPending) HIPCHK(c, hipEventSynchronize(c->hcDone));
             if (c->d_hcPfx) hipFree(c->d_hcPfx);
-    if (c->dxPending) hipEventSynchronize(c->dxDone);
-    if (c->d_dx) hipFree(c->d_dx);
-    if (c->dxDone) hipEventDestroy(c->dxDone);
-    if (c->evDxFork) hipEventDestroy(c->evDxFork);
-    if (c->evDxHash) hipEventDestroy(c->evDxHash);
             c->d_hcPfx = nullptr; c->hcPfxCap = 0;
             if (hipMalloc((void**)&c->d_hcPfx, (size_t)nb * 4 + 1024) != hipSuccess) return fail(c, PLZ4HIP_E_NOMEM, "HC segment lengths");
             c->hcPfxCap = nb + 256;
@@ -2158,20 +2283,32 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
 // 66 ms one wavefront needs; the records' block checksums are verified beside it on a stream of their own); blocks that path will
 // not answer for -- anything but a plainly valid compressed block -- and calls of many blocks, where one wave per block is the
 // better use of the chip, run the one-wave kernels.  PLZ4HIP_DX_MAX_BLOCKS (default 128; 0: off).
-int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t maxIn, int64_t maxOut, bool records)
+// hist: the blocks have history outside the block -- kHistDict: independent blocks under a.dict; kHistLinked: the chains of a.window /
+// a.chainFirst.  Few blocks of that kind take the same path with one pointer space for the whole call (dxl_*, lz4_dx_device.inl;
+// PLZ4HIP_DX_LINKED=0: they do not); a chain is answered up to its first block that is not plainly good, and the one-wave walk goes
+// on from there inside k_dxl_finish.
+enum { kHistNone = 0, kHistDict = 1, kHistLinked = 2 };
+int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t maxIn, int64_t maxOut, bool records, int hist = kHistNone)
 {
     hipError_t e;
     int dxMax = 128;
     if (const char* v = getenv("PLZ4HIP_DX_MAX_BLOCKS")) dxMax = atoi(v);
     bool dx = nb <= dxMax && maxIn >= 16384 && maxIn <= (int64_t)(6 << 20) && maxOut >= 1;
-    a.dxInfo = nullptr; a.dxSrcOff = nullptr; a.dxLen = nullptr; a.dxHashBad = nullptr;
+    if (hist) {
+        const char* v = getenv("PLZ4HIP_DX_LINKED");
+        if (v && atoi(v) == 0) dx = false;
+        if (hist == kHistLinked && (!records || !a.window || a.nChains < 1)) dx = false;
+    }
+    const int nCh = hist == kHistLinked ? a.nChains : 0;
+    a.dxInfo = nullptr; a.dxSrcOff = nullptr; a.dxLen = nullptr; a.dxHashBad = nullptr; a.dxlGood = nullptr;
     if (dx) {
         const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
         const size_t tStride = round_up((size_t)maxIn + 64, 64), pStride = round_up((size_t)outB + 64, 1024);
         const int maxSeg = (int)((maxIn + kDxSeg - 1) / kDxSeg);
         const size_t offPtr = round_up((size_t)nb * tStride * 8, 256), offUnits = offPtr + round_up((size_t)nb * pStride * 4, 256);
         const size_t offInfo = offUnits + round_up((size_t)nb * maxSeg * sizeof(DxUnit), 256), offRec = offInfo + round_up((size_t)nb * sizeof(DxInfo), 256);
-        const size_t need = offRec + round_up((size_t)nb * 16, 256);
+        const size_t offLink = offRec + round_up((size_t)nb * 16, 256);
+        const size_t need = offLink + (hist ? round_up((size_t)nb * (12 + 4 * (kDxlMaxRounds + 1)), 256) : 0);
         if (c->dxPending && c->dxStream != s) HIPCHK(c, hipStreamWaitEvent(s, c->dxDone, 0));
         if (need > c->dxBytes) {
             if (c->dxPending) HIPCHK(c, hipEventSynchronize(c->dxDone));
@@ -2207,15 +2344,35 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
             const int chunks = (int)((outB + 1023) / 1024);
             hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
             hipLaunchKernelGGL(k_dx_stitch, dim3(nb), dim3(64), 0, s, a);
-            hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-            for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-            if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-            hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+            if (!hist) {
+                hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+                if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
+                hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+            } else {
+                a.dxlFirst = (int32_t*)(c->d_dx + offLink); a.dxlChain = a.dxlFirst + nb; a.dxlGood = a.dxlChain + nb;
+                a.dxlMoved = (uint32_t*)(a.dxlGood + nb);
+                // the copy chain of a call can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
+                int rounds = 1;
+                while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
+                a.dxlRounds = rounds;
+                hipLaunchKernelGGL(k_dxl_link, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
+                hipLaunchKernelGGL(k_dxl_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_dxl_resolve, dim3((int)(pStride / 1024), nb), dim3(256), 0, s, a);
+                for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxl_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+                hipLaunchKernelGGL(k_dxl_gather, dim3(chunks, nb), dim3(256), 0, s, a);
+                if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
+                if (hist == kHistLinked) hipLaunchKernelGGL(k_dxl_finish, dim3(nCh), dim3(64), 0, s, a, c->d_counters);
+                else                     hipLaunchKernelGGL(k_dxl_verdict, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
+            }
             HIPCHK(c, hipGetLastError());
         }
     }
     a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-    if (records && dx) hipLaunchKernelGGL(k_decode_rec_dx, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
+    if (hist == kHistLinked) { if (!dx) hipLaunchKernelGGL(k_decode_rec_linked, dim3(grid_for(a.nChains, c->decWaves)), dim3(64), 0, s, a); }
+    else if (hist && records) hipLaunchKernelGGL(k_decode_rec_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
+    else if (hist)            hipLaunchKernelGGL(k_decode_raw_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
+    else if (records && dx) hipLaunchKernelGGL(k_decode_rec_dx, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     else if (records)  hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     else               hipLaunchKernelGGL(k_decode_raw, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     HIPCHK(c, hipGetLastError());
@@ -2320,6 +2477,11 @@ void plz4hip_ctx_destroy(plz4hip_ctx* c)
     if (c->fxPending) hipEventSynchronize(c->fxDone);
     if (c->d_fx) hipFree(c->d_fx);
     if (c->fxDone) hipEventDestroy(c->fxDone);
+    if (c->dxPending) { hipEventSynchronize(c->dxDone); c->dxPending = false; }
+    if (c->d_dx) { hipFree(c->d_dx); c->d_dx = nullptr; c->dxBytes = 0; }
+    if (c->dxDone) { hipEventDestroy(c->dxDone); c->dxDone = nullptr; }
+    if (c->evDxFork) { hipEventDestroy(c->evDxFork); c->evDxFork = nullptr; }
+    if (c->evDxHash) { hipEventDestroy(c->evDxHash); c->evDxHash = nullptr; }
     if (c->d_counters) hipFree(c->d_counters);
     if (c->d_lenCopy) hipFree(c->d_lenCopy);
     if (c->d_hcPfx) hipFree(c->d_hcPfx);
@@ -2364,11 +2526,11 @@ int plz4hip_ctx_counters(plz4hip_ctx* c, int64_t* out, int n)
     if (!c || n < 0 || (n > 0 && !out)) return PLZ4HIP_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
-    unsigned long long v[4] = {0, 0, 0, 0};
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipDeviceSynchronize());                                      // (the ctx's work runs on the callers' streams)
     HIPCHK(c, copy_sync(c, v, c->d_counters, sizeof v, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n && i < 4; ++i) out[i] = (int64_t)v[i];
-    return 4;
+    for (int i = 0; i < n && i < 6; ++i) out[i] = (int64_t)v[i];
+    return 6;
 }
 
 const char* plz4hip_last_error(const plz4hip_ctx* c)
@@ -2756,16 +2918,15 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
         case 0: if (hcMode) { if (int rc = launch_hc(c, s, a, nb, maxIn, 1)) return rc; }
                 else if (dictMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a);
                 else { if (int rc = launch_l1(c, s, a, nb, maxIn, 1, &sl.l1)) return rc; } break;
-        case 1: if (dictMode) hipLaunchKernelGGL(k_decode_raw_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
-                else { if (int rc = launch_decode(c, s, a, nb, maxIn, maxOut, false)) return rc; } break;
+        case 1: if (int rc = launch_decode(c, s, a, nb, maxIn, maxOut, false, dictMode ? kHistDict : kHistNone)) return rc;
+                break;
         case 2: a.dstCap = nullptr;
                 if (hcMode) { if (int rc = launch_hc(c, s, a, nb, maxIn, 0)) return rc; }
                 else if (dictMode) ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
                 else { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1)) return rc; } break;
         case 3: a.dstCap = nullptr;
-                if (dictMode && dj->linked) hipLaunchKernelGGL(k_decode_rec_linked, dim3(grid_for(nCh, c->decWaves)), dim3(64), 0, s, a);
-                else if (dictMode) hipLaunchKernelGGL(k_decode_rec_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
-                else { if (int rc = launch_decode(c, s, a, nb, bsz, bsz + 8, true)) return rc; } break;
+                if (int rc = launch_decode(c, s, a, nb, bsz, bsz + 8, true, !dictMode ? kHistNone : (dj->linked ? kHistLinked : kHistDict))) return rc;
+                break;
         case 4: hipLaunchKernelGGL(k_xxh32, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s,
                                    (const uint8_t*)a.src, a.srcStride, a.srcLen, (uint32_t*)a.result, nb, q); break;
         }
