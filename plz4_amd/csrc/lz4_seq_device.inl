@@ -115,10 +115,13 @@ DEV int ext16_fwd(const Ext16& p, const Ext16& c)                       // equal
 // by unrolling (grid(S2,S0,S1), grid(S0,S1,S2), grid(S1,S2,S0)), not by copies.
 #if defined(PLZ4_EMU)
 #define SHFLF(x, f, l) ((x)[(l) & 63].f)
-unsigned long long plz4_emu_cnt[16];              // test diagnostics: [0] grid batches, [1] primes, [2] atomics out of order, [3] second rounds for a long match alone, [4] long matches measured, [5] batches whose commit
+unsigned long long plz4_emu_cnt[32];              // test diagnostics: [0] grid batches, [1] primes, [2] atomics out of order, [3] second rounds for a long match alone, [4] long matches measured, [5] batches whose commit
                                                   // returned another entry to a probe, [6] batches with a second round, [7] entries outside the registers,
                                                   // [8] lanes that loaded a candidate window, [9] lanes whose peeked entry passed the position + tag test,
-                                                  // [10] 16-byte loads of the 36-byte window, [11] batches whose first walk executed a match that fills the 20-byte window
+                                                  // [10] 16-byte loads of the 36-byte window, [11] batches whose first walk executed a match that fills the 20-byte window,
+                                                  // how a grid batch left the steady state: [12] given up (-> generic batch), [13] a match reached lastProbe (block done),
+                                                  // [14] the search is past 64 misses, [15] the next batch is not the consecutive one (a long match), [16] the block's last
+                                                  // 224 bytes, [17] a piece's boundary ahead (kPiece); [18] warm-up boundaries passed (kPiece), [19] batches that took the 36-byte window
 #define EMU_CNT(i, v) (plz4_emu_cnt[(i)] += (unsigned long long)(v))
 #else
 #define SHFLF(x, f, l) plz4_bpermute((x)[0].f, (l))
@@ -245,8 +248,10 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
     const unsigned long long tBlock0 = STAT_NOW(); (void)tBlock0;
 
     if (n >= kMinLength) {
-        int  insPos  = 0; bool hasIns = true;      // pending table insert ("First Byte" lz4.c:1005-1010; ip-2 lz4.c:1236-1242)
-        int  rePos   = 0; bool hasRe  = false;     // pending immediate re-test at ip after a match (lz4.c:1255-1294)
+        // (the two flags are 0 / 1 integers, and step 6 of the grid batch combines them with integer selects: as `bool`s that live
+        // across batches the compiler keeps them as lane masks and moves them through a vector register at every batch's end)
+        int  insPos  = 0; int hasIns = 1;          // pending table insert ("First Byte" lz4.c:1005-1010; ip-2 lz4.c:1236-1242)
+        int  rePos   = 0; int hasRe  = 0;          // pending immediate re-test at ip after a match (lz4.c:1255-1294)
         int  sBase   = 1; int sIter = 0;           // search started at sBase; next un-probed probe number
         int  width   = 16;                         // generic batches: 16 lanes first, 64 when a search drags on
         // the pipeline's three stages; which one is batch k-1 / k / k+1 rotates with the unrolled loop below
@@ -254,7 +259,9 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         LV(uint32_t, pf);                              // kLdsWin: dword LANE of [base + 128, base + 384), requested a batch ago
         LANES({ pf[I_] = 0; })
         LANES({ for (int k = 0; k < 5; ++k) { S0[I_].P.w[k] = 0; S0[I_].C.w[k] = 0; } S0[I_].h = 0; S0[I_].ent = 0; S0[I_].pk = 0; S1[I_] = S0[I_]; S2[I_] = S0[I_]; })
-        enum { kGridNext = 0, kGridDone = 1, kGridGeneric = 2, kGridStop = 3 };
+        // why a grid batch is not followed by the consecutive one (0: it is).  Bits, so that a batch's one result is an OR.
+        // (kGridStop also comes as any of the bits 6 and up)
+        enum { kGridNext = 0, kGridDone = 1, kGridGeneric = 2, kGridStop = 4 };
         // kPiece: the next boundary and whether records are kept (not before cp).  A grid batch runs only where none of its executed
         // lanes can lie behind the boundary's post-match state: every match of it that ends at or beyond fxB ends at or beyond
         // base + 66, so its insert (anchor - 2) and re-test stay pending, and the state after the batch is that post-match state.
@@ -262,7 +269,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         if (kPiece) {
             if (run->entryAnchor >= 0) {
                 const int a0 = run->entryAnchor;
-                anchor = a0; hasIns = true; insPos = a0 - 2; hasRe = true; rePos = a0; sBase = a0 + 1; sIter = 0;
+                anchor = a0; hasIns = 1; insPos = a0 - 2; hasRe = 1; rePos = a0; sBase = a0 + 1; sIter = 0;
             }
             fxRec = run->cp < 0; fxB = fxRec ? run->end : run->cp;
         }
@@ -272,7 +279,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             if (anchor < fxB) return false;
             LDS_FENCE();
             if (!fxRec) {
-                fx_save_table(tab, run->cpTab); run->cpAnchor = anchor;
+                fx_save_table(tab, run->cpTab); run->cpAnchor = anchor; EMU_CNT(18, 1);
                 fxRec = true; nseq = 0; fxB = run->end;
                 if (anchor < fxB) return false;
             }
@@ -301,11 +308,19 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         //           registers: commits taken back, the generic batch takes over.
         // The loads are unconditional, so the number of memory operations in flight at any point of the loop is fixed (but for the two
         // of take36, which the rare batch that issues them waits for on the spot).
+        //
+        // Control flow.  A uniform conditional costs a wave 80-90 cycles whether it is taken or not, and the compiler turns every
+        // further way out of a loop body that has a divergent `if` anywhere in it into flags and a chain of branches on them at the
+        // body's foot, which every batch then walks through.  So a batch has ONE way out: steps 1-6 always run, and the batch
+        // returns one value -- 0, or why the consecutive batch must not follow (kGrid*) -- that the unrolled loop tests once.
+        // Whether batch k+1 may run (the stop test) is a question about the state batch k's step 6 has just computed, so it is
+        // asked there and not at batch k+1's entry; the caller guarantees it for the first batch after a prime.  What happens
+        // rarely lives behind the single `trouble` question: the second rounds, and a batch that gives up or ends the block.
+        // Those two set what the straight path needs to pass through steps 5 and 6 as a batch that executed nothing (mm = 0, Send = 0:
+        // no record, anchor and search state as they were; keepIns / keepWidth for the two values step 6 would overwrite).
+        // The questions left on a clean batch's path: take36, more than six hops, `upd`, `trouble`, and the loop's test.
         auto grid = [&](LVREF(GStage, prev), LVREF(GStage, cur), LVREF(GStage, next), const int base) -> int {
             const int probeStart = hasRe ? rePos : sBase + sIter;
-            const int firstPos   = hasIns ? insPos : probeStart;
-            if ((sIter > 64) | ((firstPos & ~63) != base) | (base + 224 > n)) return kGridStop;
-            if (kPiece && ((base + 66 > fxB) | (anchor >= fxB))) return kGridStop;
             if (kPiece && !fxRec) nseq = 0;
             uint32_t* T = (uint32_t*)tab;
             EMU_CNT(0, 1); STAT(P_BATCH, 1);
@@ -321,23 +336,25 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             })
             LDS_ORDER();
             // ---- 2. this batch against its peeked candidates
-            LV(uint32_t, ce); LV(uint32_t, rent); LV(bool, hit); LV(int, fwd); LV(int, eLane);
-            auto compare = [&](LVREF(Win20, W), LVREF(bool, hitV), LVREF(int, fwdV)) {
+            // (the hits are a wave-uniform mask from the start -- the AND of one ballot per term, BALLOT4 in wave.h -- and the lanes
+            // read it back as a select mask: a per-lane `bool` that is balloted later goes through a vector register and back)
+            LV(uint32_t, ce); LV(uint32_t, rent); LV(int, fwd); LV(int, eLane);
+            auto compare = [&](LVREF(Win20, W), LVREF(int, fwdV)) -> uint64_t {
+                const uint64_t ok = BALLOT4((ce[I_] >> sh) < (uint32_t)(base + LANE), (ce[I_] >> sh) + kMaxDist >= (uint32_t)(base + LANE),
+                                            ((ce[I_] ^ cur[I_].ent) & tagMask) == 0, W[I_].w[0] == cur[I_].P.w[0]);
                 LANES({
-                    const uint32_t q = (uint32_t)(base + LANE), cp = ce[I_] >> sh;
-                    const bool ok = (cp < q) & (cp + kMaxDist >= q) & (((ce[I_] ^ cur[I_].ent) & tagMask) == 0) & (W[I_].w[0] == cur[I_].P.w[0]);
                     const int f = win20_fwd(cur[I_].P, W[I_]);
-                    hitV[I_] = ok;
-                    fwdV[I_] = ok ? f : 0;
+                    fwdV[I_] = LANE_IN(ok) ? f : 0;
                 })
+                return ok;
             };
             LV(Win20, W);
             LANES({ ce[I_] = cur[I_].pk; rent[I_] = 0; W[I_] = cur[I_].C; })
-            compare(W, hit, fwd);
+            uint64_t hit = compare(W, fwd);
             LANES({ eLane[I_] = LANE + kMinMatch + fwd[I_]; })    // lane index just past a match that starts here
             // (the hits that fill their 20-byte window, 0.44 lanes of a batch on text: if the first walk executes one of them, take36
-            // gives them 16 bytes more)
-            const uint64_t full20 = BALLOT(hit[I_] & (fwd[I_] == 16));
+            // gives them 16 bytes more.  A lane that is no hit has fwd == 0.)
+            const uint64_t full20 = BALLOT(fwd[I_] == 16);
             const uint64_t x36 = (PLZ4_PW & 2) ? full20 : 0;
             STAT_WAIT_LGKM();
             const unsigned long long ts2 = STAT_NOW(); (void)ts2;
@@ -405,10 +422,12 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                     eLane[I_] = LANE + kMinMatch + fwd[I_];
                 })
                 w36 = x36;
+                EMU_CNT(19, 1);
             };
 #define PAST_WINDOW() ((BALLOT(fwd[I_] == 16) & ~w36) | (BALLOT(fwd[I_] == 32) & w36))
             const int  cur0 = probeStart - base;                  // first probe lane (>= 64: none in this batch, only the pending insert)
-            const bool re0  = hasRe;
+            const uint64_t fromCur0 = (cur0 < 64) ? (~0ull << (cur0 & 63)) : 0;      // the lanes from the first probe lane on
+            const int  re0  = hasRe;
             const uint64_t insBit0 = hasIns ? (1ull << (insPos - base)) : 0;
             int lim0 = sBase + 65 - base; if (lim0 > 63) lim0 = 63;   // probe number <= 65 keeps the stride at 1
             uint64_t mm = 0;           // executed match lanes
@@ -416,17 +435,17 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             uint64_t E = 0;            // executed lanes (probes + inserts)
             uint64_t probes = 0;
             int      Send = 0;
-            bool     finished = false;
+            int      finished = 0;
             // the parser over this batch's hits: scalar hop over the recorded matches only, everything else derived per lane
             auto walk = [&]() {
-                const uint64_t hits = BALLOT(hit[I_]);
+                const uint64_t hits = hit;
                 uint64_t specialLeft = hits & PAST_WINDOW();            // longer than the speculative window: the hop needs its end
                 LV(int, nextHit);      // first recorded match at or after the end of the match that starts here (64: none)
                 LANES({
                     const uint64_t ah = (eLane[I_] < 64) ? (hits >> eLane[I_]) : 0;
                     nextHit[I_] = ah ? eLane[I_] + ctz64(ah) : 64;
                 })
-                mm = 0; eL = 0; finished = false;
+                mm = 0; eL = 0; finished = 0;
                 int w = 64;
                 if (cur0 < 64) { const uint64_t hm = hits & (~0ull << cur0); if (hm) w = ctz64(hm); }
                 if (w > lim0) w = 64;                                  // (the stride limit concerns the first match only)
@@ -459,7 +478,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         specialLeft &= ~(1ull << ws);
                         const int e1 = ws + kMinMatch + mc0;
                         WL(eLane, ws, e1);
-                        if (base + e1 >= lastProbe) { finished = true; break; }   // lz4.c:1233 (only a long match gets there)
+                        if (base + e1 >= lastProbe) { finished = 1; break; }   // lz4.c:1233 (only a long match gets there)
                         const uint64_t hm = (e1 < 64) ? (hits & (~0ull << e1)) : 0;
                         w = hm ? ctz64(hm) : 64;
                         if (w >= 64) break;
@@ -477,7 +496,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 SCAN_MAX_EXCL(stA);
                 const uint64_t hasPm = BALLOT(stA[I_] > 0);
                 LANES({ stA[I_] = stA[I_] > 0 ? stA[I_] : cur0; })                // where probing resumed before me
-                probes = BALLOT(LANE >= stA[I_] && LANE < SendL && LANE >= cur0);
+                probes = BALLOT2(LANE >= stA[I_], LANE < SendL) & fromCur0;
                 E = probes | insBit0 | (hasPm & BALLOT(stA[I_] == LANE + 2));      // + the ip-2 inserts (lz4.c:1236-1242)
                 STAT(P_CYC_E, STAT_NOW() - tw2);
             };
@@ -491,7 +510,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                     const uint64_t ah = (eLane[I_] < 64) ? (hits >> eLane[I_]) : 0;
                     nextHit[I_] = ah ? eLane[I_] + ctz64(ah) : 64;
                 })
-                const uint64_t hm = (cur0 < 64) ? (hits & (~0ull << (cur0 & 63))) : 0;
+                const uint64_t hm = hits & fromCur0;
                 int w = hm ? ctz64(hm) : 64;
                 w = (w > lim0) ? 64 : w;                               // (the stride limit concerns the first match only)
                 const uint64_t low = (w == 0 ? 1ull : 0ull);
@@ -514,7 +533,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 mm = any ? ((m & ~1ull) | low) : 0;
                 eL = RL(eLane, (63 - __builtin_clzll(mm | 1ull)) & 63);
                 eL = mm ? eL : 0;
-                finished = false;
+                finished = 0;
                 const unsigned long long tw2 = STAT_NOW(); (void)tw2;
                 STAT(P_CYC_HOP, tw2 - tw1);
                 Send = mm ? 64 : min_(64, lim0 + 1);
@@ -524,15 +543,16 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 SCAN_MAX_EXCL(stA);
                 const uint64_t hasPm = BALLOT(stA[I_] > 0);
                 LANES({ stA[I_] = stA[I_] > 0 ? stA[I_] : cur0; })
-                probes = BALLOT((LANE >= stA[I_]) & (LANE < SendL) & (LANE >= cur0));
+                probes = BALLOT2(LANE >= stA[I_], LANE < SendL) & fromCur0;
                 E = probes | insBit0 | (hasPm & BALLOT(stA[I_] == LANE + 2));
                 STAT(P_CYC_E, STAT_NOW() - tw2);
             };
             // ---- 4. first round, straight: walk -> commit -> verify, every step unconditional, ONE question at the end
             uint64_t committed = 0;
-            bool giveUp = false;
+            int rare = 0;                       // kGridGeneric / kGridDone: only the rounds behind `trouble` set it
+            int keepIns = 0, keepWidth = 64;    // what step 6 leaves of hasIns / width: a batch that gives up leaves them as they were
             {
-                const uint64_t hits1 = BALLOT(hit[I_]);
+                const uint64_t hits1 = hit;
                 walk_fast(hits1);
                 EMU_CNT(11, (mm & full20) != 0);
                 if (mm & x36) { take36(); walk_fast(hits1); }
@@ -546,8 +566,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 // (ascending lane order of the atomics on one slot is what makes the returned entry the sequential one: any other
                 // order shows up as a position at or above the lane's own)
                 const uint64_t misorder = EL & BALLOT((rent[I_] >> sh) >= (uint32_t)(base + LANE));
-                const uint64_t noRegs   = upd & BALLOT(rent[I_] != cur[I_].pk && (rent[I_] >> sh) < (uint32_t)base);
-                LV(bool, hitN); LV(int, fwdN); LV(Win20, Wn);
+                const uint64_t noRegs   = upd & BALLOT2(rent[I_] != cur[I_].pk, (rent[I_] >> sh) < (uint32_t)base);
+                LV(int, fwdN); LV(Win20, Wn);
                 uint64_t diff = 0;
                 if (upd) {                   // (about half of the batches on text: worth the one conditional)
                     LANES({
@@ -560,13 +580,14 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                             Wn[I_].w[k] = same ? cur[I_].C.w[k] : a;
                         }
                     })
-                    compare(Wn, hitN, fwdN);
+                    const uint64_t hitN = compare(Wn, fwdN);
                     // (a window that compares equal to its end says nothing about the length behind it: that one is measured again)
-                    diff = upd & BALLOT((hitN[I_] != hit[I_]) | (fwdN[I_] != fwd[I_]) | (fwdN[I_] == 16));
+                    diff = upd & ((hitN ^ hit) | BALLOT(fwdN[I_] != fwd[I_]) | BALLOT(fwdN[I_] == 16));
                     LANES({
                         const bool u = LANE_IN(upd);
-                        hit[I_] = u ? hitN[I_] : hit[I_]; fwd[I_] = u ? fwdN[I_] : fwd[I_]; eLane[I_] = LANE + kMinMatch + fwd[I_];
+                        fwd[I_] = u ? fwdN[I_] : fwd[I_]; eLane[I_] = LANE + kMinMatch + fwd[I_];
                     })
+                    hit = (hit & ~upd) | (hitN & upd);
                     w36 &= ~upd;                 // (their lengths are the 20-byte register window's now)
                 }
                 STAT(P_CYC_REFRESH, STAT_NOW() - tc0);
@@ -576,53 +597,74 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                     // ---- rounds of walk -> commit -> verify (the walk with the long matches measured) until one verifies
                     EMU_CNT(6, 1); STAT(P_REPAIR, 1);
                     EMU_CNT(3, (diff | misorder | noRegs) == 0);                       // (only because of a match longer than the window)
-                    if (misorder | noRegs) { EMU_CNT(2, misorder != 0); EMU_CNT(7, noRegs != 0); giveUp = true; }
-                    for (int round = 1; !giveUp; ++round) {
+                    // (one variable says how the rounds end, and the loop has one way out: no `break`s whose flags a clean batch
+                    // would have to pass at the loop's foot)
+                    enum { kGoOn = 0, kVerified = 1, kGiveUp = 2 };
+                    int st = kGoOn;
+                    if (misorder | noRegs) { EMU_CNT(2, misorder != 0); EMU_CNT(7, noRegs != 0); st = kGiveUp; }
+                    for (int round = 1; st == kGoOn; ++round) {
                         {                                                      // take the last round's commits back
                             const uint64_t cm = committed;
                             LANES({ if (LANE_IN(cm)) lds_min(&T[cur[I_].h], rent[I_]); })   // min over a slot's group == its pre-batch value
                             LDS_ORDER();
                             committed = 0;
                         }
-                        if (round == 4) { giveUp = true; break; }
-                        walk();
-                        const uint64_t EL2 = E;
-                        LANES({ if (LANE_IN(EL2)) rent[I_] = lds_max_rtn(&T[cur[I_].h], cur[I_].ent); })
-                        committed = EL2;
-                        const uint64_t upd2 = probes & BALLOT(rent[I_] != ce[I_]);
-                        if (EL2 & BALLOT((rent[I_] >> sh) >= (uint32_t)(base + LANE))) { EMU_CNT(2, 1); giveUp = true; break; }
-                        if (!upd2) break;                                      // every probe read what it had assumed
-                        if (upd2 & BALLOT(rent[I_] != cur[I_].pk && (rent[I_] >> sh) < (uint32_t)base)) { EMU_CNT(7, 1); giveUp = true; break; }
-                        LANES({
-                            if (LANE_IN(upd2)) ce[I_] = rent[I_];
-                            const int t = (int)(ce[I_] >> sh) - base;
-                            const bool same = ce[I_] == cur[I_].pk;
-                            for (int k = 0; k < 5; ++k) {
-                                const uint32_t a = SHFLF(cur, P.w[k], t);
-                                Wn[I_].w[k] = same ? cur[I_].C.w[k] : a;
+                        if (round == 4) st = kGiveUp;
+                        else {
+                            walk();
+                            const uint64_t EL2 = E;
+                            LANES({ if (LANE_IN(EL2)) rent[I_] = lds_max_rtn(&T[cur[I_].h], cur[I_].ent); })
+                            committed = EL2;
+                            const uint64_t upd2 = probes & BALLOT(rent[I_] != ce[I_]);
+                            const uint64_t mis2 = EL2 & BALLOT((rent[I_] >> sh) >= (uint32_t)(base + LANE));
+                            const uint64_t noRegs2 = upd2 & BALLOT2(rent[I_] != cur[I_].pk, (rent[I_] >> sh) < (uint32_t)base);
+                            if (mis2) { EMU_CNT(2, 1); st = kGiveUp; }
+                            else if (!upd2) st = kVerified;                    // every probe read what it had assumed
+                            else if (noRegs2) { EMU_CNT(7, 1); st = kGiveUp; }
+                            else {
+                                LANES({
+                                    if (LANE_IN(upd2)) ce[I_] = rent[I_];
+                                    const int t = (int)(ce[I_] >> sh) - base;
+                                    const bool same = ce[I_] == cur[I_].pk;
+                                    for (int k = 0; k < 5; ++k) {
+                                        const uint32_t a = SHFLF(cur, P.w[k], t);
+                                        Wn[I_].w[k] = same ? cur[I_].C.w[k] : a;
+                                    }
+                                })
+                                const uint64_t hitN = compare(Wn, fwdN);
+                                const uint64_t diff2 = upd2 & ((hitN ^ hit) | BALLOT(fwdN[I_] != fwd[I_]) | BALLOT(fwdN[I_] == 16));
+                                if (!diff2) st = kVerified;                    // same walk, same executed set: only offsets moved
+                                else {
+                                    LANES({ if (LANE_IN(upd2)) { fwd[I_] = fwdN[I_]; eLane[I_] = LANE + kMinMatch + fwdN[I_]; } })
+                                    hit = (hit & ~upd2) | (hitN & upd2);
+                                    w36 &= ~upd2;
+                                }
                             }
-                        })
-                        compare(Wn, hitN, fwdN);
-                        const uint64_t diff2 = upd2 & BALLOT(hitN[I_] != hit[I_] || fwdN[I_] != fwd[I_] || fwdN[I_] == 16);
-                        if (!diff2) break;                                     // same walk, same executed set: only offsets moved
-                        LANES({ if (LANE_IN(upd2)) { hit[I_] = hitN[I_]; fwd[I_] = fwdN[I_]; eLane[I_] = LANE + kMinMatch + fwdN[I_]; } })
-                        w36 &= ~upd2;
+                        }
+                    }
+                    if (st == kGiveUp) {
+                        // commits taken back; the batch passes through steps 5 and 6 as one that executed nothing, and the generic
+                        // batch takes over from the state this batch found
+                        if (committed) {
+                            const uint64_t cm = committed;
+                            LANES({ if (LANE_IN(cm)) lds_min(&T[cur[I_].h], rent[I_]); })
+                        }
+                        LDS_FENCE();
+                        mm = 0; eL = 0; Send = 0; finished = 0;
+                        keepIns = hasIns; keepWidth = width;
+                        rare = kGridGeneric;
+                        EMU_CNT(12, 1);
+                    } else {
+                        rare = finished;                    // (0, or 1 == kGridDone)
+                        EMU_CNT(13, finished);
                     }
                 }
             }
 #undef PAST_WINDOW
-            if (giveUp) {
-                if (committed) {
-                    const uint64_t cm = committed;
-                    LANES({ if (LANE_IN(cm)) lds_min(&T[cur[I_].h], rent[I_]); })
-                }
-                LDS_FENCE();
-                return kGridGeneric;
-            }
             // ---- 4b. batch k+1's slots once more: the table holds this batch's inserts now, and a slot that changed since the peek
             // was taken by an executed lane of THIS batch -- whose window is here.  Its bytes replace the requested ones, so the
             // next batch starts from candidates that are exact against everything before it; what its commit can still return
-            // differently is a lane of its own.
+            // differently is a lane of its own.  (After a batch that gave up the stages are dead: the next grid batch primes anew.)
             LANES({
                 const uint32_t late = T[next[I_].h];
                 const bool ch = late != next[I_].pk;
@@ -645,25 +687,47 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                     seq[slot] = seq_pack((uint32_t)(base + LANE), (uint32_t)fwd[I_], (uint32_t)(base + LANE) - (ce[I_] >> sh));
                 })
                 nseq += __builtin_popcountll(mm);
-                anchor = mm ? base + eL : anchor;
+                const int pm = base + eL;
+                anchor = mm ? pm : anchor;
             }
-            if (finished) return kGridDone;
-
-            // ---- 6. parser state after this batch
-            {   // (selects, not branches)
-                const bool hm = mm != 0, c0 = cur0 < 64;
-                const bool reM = eL >= Send;                                // with a match: its re-test is not executed in this batch
-                const bool reN = c0 & !(Send > cur0) & re0;                 // without: the pending re-test stays pending
-                const int  sB  = hm ? base + eL + 1 : sBase;
-                const int  sI  = hm ? (reM ? 0 : (base + Send) - sB) : ((c0 & (Send > cur0)) ? (base + Send) - sBase : sIter);
-                const bool nRe = hm ? reM : (c0 ? reN : hasRe);
-                const int  nRp = hm ? base + eL : (reN ? base + cur0 : rePos);
-                hasIns = hm & (eL - 2 >= 64); insPos = hasIns ? base + eL - 2 : insPos;
+            // ---- 6. parser state after this batch, and whether the consecutive batch may follow it
+            // Every value is computed, then chosen: a select between two finished values is one s_cselect_b32, where a `?:` with
+            // work in its arms is a branch.  The 0 / 1 values that are KEPT (hasRe, hasIns) come from sign bits behind UNI_OPAQUE: a
+            // compare's result stored as an integer is a lane mask to the compiler, which turns it into 0 / 1 in a vector register
+            // and reads it back (v_cndmask 0,1 + v_readfirstlane, and a wait for both) -- and it recognises the sign bit, too.
+            int leave;
+            {
+                const bool hm = mm != 0, c0 = cur0 < 64, sc = Send > cur0, cs = c0 & sc, cn = c0 & !sc;
+                int dRe = Send - 1 - eL, dIns = 65 - eL;
+                UNI_OPAQUE(dRe); UNI_OPAQUE(dIns);
+                const int reM = (int)((uint32_t)dRe >> 31);                 // eL >= Send.  With a match: its re-test is not executed in this batch
+                const int nIns = (int)((uint32_t)dIns >> 31);               // eL - 2 >= 64 (eL == 0 without a match)
+                const int reN = cn ? re0 : 0;                               // without a match: the pending re-test stays pending
+                const int pm = base + eL, pe = base + Send;
+                const int sBm = pm + 1, sIm1 = pe - sBm, sIn1 = pe - sBase;
+                const int sIm = reM ? 0 : sIm1, sIn = cs ? sIn1 : sIter;
+                const int nRn = c0 ? reN : hasRe;
+                const int pc = base + cur0, nRpn = reN ? pc : rePos;
+                const int sB = hm ? sBm : sBase, sI = hm ? sIm : sIn, nRe = hm ? reM : nRn, nRp = hm ? pm : nRpn;
+                const int ip2 = pm - 2;
+                insPos = nIns ? ip2 : insPos;
+                hasIns = nIns | keepIns;
                 sBase = sB; sIter = sI; hasRe = nRe; rePos = nRp;
+                width = keepWidth;
+                // the stop test of batch k+1, on the state it will find: a first position outside [base + 64, base + 128) (a long
+                // match: bits 6 and up), the block's last 224 bytes, a search past 64 misses, a piece's boundary (sign bits -> kGridStop)
+                const int nb = base + 64;
+                const int fp0 = sB + sI, fp1 = nRe ? nRp : fp0;
+                const int firstPos = hasIns ? insPos : fp1;
+                int neg = (n - 224 - nb) | (64 - sI);
+                if (kPiece) neg |= (fxB - 66 - nb) | (fxB - 1 - anchor);
+                leave = rare | ((firstPos & ~63) ^ nb) | (int)(((uint32_t)neg >> 31) * kGridStop);
+                EMU_CNT(14, !rare && sI > 64); EMU_CNT(15, !rare && sI <= 64 && (firstPos & ~63) != nb);
+                EMU_CNT(16, !rare && sI <= 64 && (firstPos & ~63) == nb && nb + 224 > n);
+                EMU_CNT(17, kPiece && !rare && sI <= 64 && (firstPos & ~63) == nb && nb + 224 <= n && (((fxB - 66 - nb) | (fxB - 1 - anchor)) < 0));
             }
-            width = 64;
             STAT(P_CYC_TAIL, STAT_NOW() - ts5);
-            return kGridNext;
+            return leave;
         };
 
         for (;;) {
@@ -691,14 +755,17 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         if (kLdsWin) pf[I_] = ld32u(src + min_(base + 128 + 4 * LANE, n - 4));
                     })
                     LDS_ORDER();
+                    // (no stop test in front of the first batch: base is this state's first position, sIter <= 64, and fx_boundary()
+                    // has just answered anchor < fxB)
                     int rc;
                     for (;;) {
-                        rc = grid(S2, S0, S1, base); if (rc != kGridNext) break; base += 64;
-                        rc = grid(S0, S1, S2, base); if (rc != kGridNext) break; base += 64;
-                        rc = grid(S1, S2, S0, base); if (rc != kGridNext) break; base += 64;
+                        rc = grid(S2, S0, S1, base); if (rc) break; base += 64;
+                        rc = grid(S0, S1, S2, base); if (rc) break; base += 64;
+                        rc = grid(S1, S2, S0, base); if (rc) break; base += 64;
                     }
-                    if (rc == kGridDone) break;
-                    if (rc == kGridStop) {
+                    if (rc & kGridGeneric) { /* the generic batch below */ }
+                    else if (rc & kGridDone) break;
+                    else {
                         // the next batch is not the consecutive one (a long match, a search past 64 misses, the block's end):
                         // start over if it is still a grid batch, else fall through to the generic one
                         if (sIter <= 64) {
@@ -770,8 +837,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
 
             if (!hitsSafe) {
                 int used = keep;
-                if (hasIns && used > 0) { hasIns = false; used--; }
-                if (hasRe  && used > 0) { hasRe = false; used--; }
+                if (hasIns && used > 0) { hasIns = 0; used--; }
+                if (hasRe  && used > 0) { hasRe = 0; used--; }
                 sIter += used;
                 if (keep == nproc && endInBatch && !hasIns && !hasRe) break;      // -> last literals (lz4.c:1055)
                 width = 64;
@@ -793,8 +860,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             if (ip >= lastProbe) break;                                        // lz4.c:1233
 
             // next batch: insert ip-2 (lz4.c:1236-1242), re-test ip (lz4.c:1255-1294), then search from ip+1 (lz4.c:1298)
-            hasIns = true; insPos = ip - 2;
-            hasRe = true;  rePos = ip;
+            hasIns = 1; insPos = ip - 2;
+            hasRe = 1;  rePos = ip;
             sBase = ip + 1; sIter = 0; width = 16;
             }
         }

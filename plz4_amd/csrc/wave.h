@@ -38,6 +38,7 @@
 #define SCAN_INCL(x)   do { for (int s_ = 1; s_ < 64; ++s_) (x)[s_] += (x)[s_ - 1]; } while (0)   /* inclusive prefix sum over lanes */
 /* x[l] <- max of x over the lanes strictly below l (0 for lane 0); x >= 0 */
 #define SCAN_MAX_EXCL(x) do { int m_ = 0; for (int s_ = 0; s_ < 64; ++s_) { const int v_ = (x)[s_]; (x)[s_] = m_; if (v_ > m_) m_ = v_; } } while (0)
+#define UNI_OPAQUE(x)  do {} while (0)
 #define WAVE_FENCE()   do {} while (0)
 #define LDS_FENCE()    do {} while (0)
 #define LDS_ORDER()    do {} while (0)
@@ -63,6 +64,9 @@ static inline int plz4_emu_step()  { return plz4_emu_descending ? -1 : 1; }
 #define WL(x, w, v)    do { const auto wl_v_ = (v); (x)[0] = (LANE == (w)) ? wl_v_ : (x)[0]; } while (0)
 #define SHFL(x, l)     plz4_bpermute((x)[0], (l))
 #define UNI(x)         plz4_readfirstlane((x))
+// a wave-uniform 32-bit value the optimiser must take as it is (it stays in its scalar register; no instruction): keeps what is
+// computed from it from being recognised as a compare -- see step 6 of the grid batch, lz4_seq_device.inl
+#define UNI_OPAQUE(x)  __asm__("" : "+s"(x))
 // a wave-uniform 64-bit mask as a per-lane condition: the scalar register pair itself is the select / exec mask, where
 // ((mask >> LANE) & 1) costs two v_and and a 64-bit v_cmp
 #define LANE_IN(mask)  (__builtin_amdgcn_inverse_ballot_w64((uint64_t)(mask)))
@@ -122,6 +126,14 @@ __device__ __forceinline__ uint64_t plz4_readfirstlane(uint64_t v)
     return ((uint64_t)hi << 32) | lo;
 }
 #endif
+
+// The ballot of a conjunction, as the conjunction of the ballots of its terms.  BALLOT(a & b) is the same value, but the compiler
+// folds a ballot into the compare that feeds it only when its operand IS one compare; the AND of two goes mask -> v_cndmask 0,1 ->
+// v_cmp_ne -> mask (two VALU instructions and a VALU -> SGPR hazard on the way), where the AND of two masks is one s_and_b64.
+// Every term is evaluated by every lane (no short circuit), so the terms must be free of side effects.
+#define BALLOT2(a, b)        (BALLOT(a) & BALLOT(b))
+#define BALLOT3(a, b, c)     (BALLOT(a) & BALLOT(b) & BALLOT(c))
+#define BALLOT4(a, b, c, d)  (BALLOT(a) & BALLOT(b) & BALLOT(c) & BALLOT(d))
 
 // ---------------------------------------------------------------- unaligned little-endian access
 // gfx950 runs with unaligned-access-mode on, so these become single global_load/store_{ushort,dword,dwordx2,dwordx4}.
