@@ -90,7 +90,7 @@ typedef struct plz4hip_ctx plz4hip_ctx;
 int         plz4hip_abi_version(void);
 int         plz4hip_device_count(void);                       /* <0: PLZ4HIP_E_DEVICE */
 int         plz4hip_ctx_create(int device, plz4hip_ctx** out);
-void        plz4hip_ctx_destroy(plz4hip_ctx* ctx);
+void        plz4hip_ctx_destroy(plz4hip_ctx* ctx);            /* waits for the ctx's jobs still in flight on the callers' streams */
 const char* plz4hip_last_error(const plz4hip_ctx* ctx);       /* text of the last PLZ4HIP_E_* on this ctx */
 int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release staging buffers and HC workspaces (waits for work in flight) */
 /* Waits for the ctx's work, then writes up to n counters to out: [0] blocks encoded by the few-block level-1 path, [1] its rounds

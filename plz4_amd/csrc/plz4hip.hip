@@ -7,6 +7,7 @@
 // 1.1 KiB of LDS and is bounded by its registers (24 waves per CU).  Waves never communicate.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
 #include <mutex>
 #include <thread>
@@ -16,6 +17,7 @@
 #include <cstring>
 
 #include "../../include/plz4hip.h"
+#include "stream_ws.h"
 #if defined(PLZ4_STATS)
 __device__ unsigned long long plz4_stats[24];
 #endif
@@ -1446,27 +1448,24 @@ struct plz4hip_ctx {
     int          cus = 0;
     int          encWaves = 0, decWaves = 0;
     // host-API staging (grown on demand): a ring of chunks in flight, each with pinned host memory, device memory and a stream
-    // level 1 in stages: sequence records + chunk tables of one group of blocks (launch_l1)
-    struct L1Ws { uint8_t* d = nullptr; size_t bytes = 0; };
+    // l1: level 1 in stages, the sequence records + chunk tables of one group of blocks (launch_l1), ordered by the slot's stream
     struct HostSlot { uint8_t* h = nullptr; size_t hcap = 0; uint8_t* d = nullptr; size_t dcap = 0; hipStream_t s = nullptr;
-                      hipEvent_t evData = nullptr, evHash = nullptr; bool hashBusy = false; L1Ws l1; };
+                      hipEvent_t evData = nullptr, evHash = nullptr; bool hashBusy = false; DeviceBuffer l1; };
     plz4hip_xxh32_stream* contentHash = nullptr;   // plz4hip_ctx_set_content_hash
     static constexpr int kSlots = 3;
     HostSlot     slot[kSlots];
-    uint8_t*     d_hc = nullptr;   int hcWaves = 0;     // HC workspace, one slot per resident HC wave (allocated on first use)
+    // The workspaces below belong to one job at a time each and are ordered across the callers' streams on the device: a
+    // DeviceBuffer and the StreamOrder behind its last job (stream_ws.h).  Every one of them is listed in owned().
+    DeviceBuffer hc;  int hcWaves = 0;                  // HC workspace, one slot per resident HC wave (allocated on first use)
     // level 12 in three phases: chain + search results of one group of blocks, the parser's table overflow, an error flag
-    uint8_t*     d_h12 = nullptr;  size_t h12Bytes = 0;  int h12ParseWaves = 0;  int h12SegWaves = 0;  int hcLazyWaves = 0;  size_t h12ErrOff = 0;
-    // Both HC workspaces belong to one job at a time: the stream of the last HC job and an event recorded behind it; an HC
-    // job on another stream waits for that event on the device (no host block).
-    hipEvent_t   hcDone = nullptr; hipStream_t hcStream = nullptr; bool hcPending = false;
+    DeviceBuffer h12;  int h12ParseWaves = 0;  int h12SegWaves = 0;  int hcLazyWaves = 0;  size_t h12ErrOff = 0;
+    StreamOrder  hcOrder;                               // one HC job at a time: hc, h12 and hcPfx
     hipStream_t  hashStream = nullptr;   // the streaming content checksum runs here, beside the codec kernels
-    // the level-1 workspaces of the device-resident calls (the host-buffer calls have one per staging slot): one job at a time
-    // each, ordered across streams on the device like the HC workspaces.  Two of them, so that calls on two streams need not
+    // the level-1 workspaces of the device-resident calls (the host-buffer calls have one per staging slot).  Two of them, so that calls on two streams need not
     // wait for each other: the emit kernels of one call then run beside the parse of the next (the second one is only
     // allocated when a second stream shows up while the first workspace is another stream's; PLZ4HIP_L1_WORKSPACES=1: one)
     static constexpr int kL1Shared = 2;
-    L1Ws         l1[kL1Shared];
-    hipEvent_t   l1Done[kL1Shared] = {nullptr, nullptr}; hipStream_t l1Stream[kL1Shared] = {nullptr, nullptr}; bool l1Pending[kL1Shared] = {false, false};
+    DeviceBuffer l1[kL1Shared];  StreamOrder l1Order[kL1Shared];
     // The parse kernel of a staged call fills the device by itself (persistent workgroups around all of a CU's LDS).  Two of them
     // started together on two streams share the CUs half and half and stay in step, so that nothing of one call runs beside the
     // other's parse.  They are therefore ordered on the device: a call's parse on another stream than the last one's waits (behind
@@ -1477,24 +1476,25 @@ struct plz4hip_ctx {
     // levels 3..11 on independent blocks: the list builder of the next group of blocks runs on this stream beside the walk of the
     // current one (launch_hc)
     hipStream_t  hcBuildStream = nullptr; hipEvent_t evHcFork = nullptr, evHcHist = nullptr, evHcChain[2] = {nullptr, nullptr}, evHcFree[2] = {nullptr, nullptr};
-    // HC levels 3..12 with a dictionary / linked blocks on the list path: the blocks' segment lengths (k_hc_ext_prep); one HC job at a time
-    int32_t*     d_hcPfx = nullptr; int hcPfxCap = 0; int hcLazyExWaves = 0;
-    // LZ4_decompress_safe of a few blocks by the whole chip (lz4_dx_device.inl): tables of one job at a time, ordered across streams
-    uint8_t*     d_dx = nullptr; size_t dxBytes = 0;
-    hipEvent_t   dxDone = nullptr; hipStream_t dxStream = nullptr; bool dxPending = false;
+    // HC levels 3..12 with a dictionary / linked blocks on the list path: the blocks' segment lengths (k_hc_ext_prep), int32 each
+    DeviceBuffer hcPfx;  int hcLazyExWaves = 0;
+    // LZ4_decompress_safe of a few blocks by the whole chip (lz4_dx_device.inl): its tables
+    DeviceBuffer dx;  StreamOrder dxOrder;
     hipStream_t  dxHashStream = nullptr; hipEvent_t evDxFork = nullptr, evDxHash = nullptr;   // records: the block checksums beside the decode
-    // the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): pieces' states and records of one job at a time,
-    // sized per call, ordered across streams like the dx tables
-    uint8_t*     d_fx = nullptr; size_t fxBytes = 0;
-    hipEvent_t   fxDone = nullptr; hipStream_t fxStream = nullptr; bool fxPending = false;
+    // the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): pieces' states and records, sized per call
+    DeviceBuffer fx;  StreamOrder fxOrder;
     // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
     // parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history outside the block (dictionary,
     // linked) answered by it, [5] its jump rounds in the last such call
     unsigned long long* d_counters = nullptr;
-    // plz4hip_dev_compress: the sanitised block lengths of the last call.  One job at a time like the workspaces: a call on another
-    // stream waits (on the device) for the event behind the last job's kernels before it overwrites the copy.
-    int32_t*     d_lenCopy = nullptr; int lenCopyCap = 0;
-    hipEvent_t   lenDone = nullptr; hipStream_t lenStream = nullptr; bool lenPending = false;
+    // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
+    DeviceBuffer lenCopy;  StreamOrder lenOrder;
+    struct Owned { DeviceBuffer* buf; StreamOrder* order; bool trimmed; };     // trimmed: plz4hip_ctx_trim gives it back
+    std::array<Owned, 8> owned()
+    {
+        return {{{&hc, &hcOrder, true}, {&h12, &hcOrder, true}, {&hcPfx, &hcOrder, false}, {&l1[0], &l1Order[0], true},
+                 {&l1[1], &l1Order[1], true}, {&dx, &dxOrder, true}, {&fx, &fxOrder, true}, {&lenCopy, &lenOrder, false}}};
+    }
 };
 
 // == clz4.DictCtx (clz4.go:96-120): a private device copy of the last 64 KiB of the dictionary + the LZ4_loadDictSlow table.
@@ -1625,7 +1625,7 @@ bool is_hc_level(int level) { return level >= 2 && level <= 12; }        // ever
 
 int ensure_hc(plz4hip_ctx* c)
 {
-    if (c->d_hc) return PLZ4HIP_OK;
+    if (c->hc.d) return PLZ4HIP_OK;
     // The HC parsers are one dependent memory access after another: the more waves a CU holds, the more of that latency
     // is hidden.  Fill every wave slot the register budget allows (workspace: 320 KiB per wave); PLZ4HIP_HC_WAVES_PER_CU
     // overrides for experiments.
@@ -1637,23 +1637,18 @@ int ensure_hc(plz4hip_ctx* c)
     }
     if (const char* v = getenv("PLZ4HIP_HC_WAVES_PER_CU")) { const int w = atoi(v); if (w >= 1 && w <= per) per = w; }
     const int waves = c->cus * per;
-    if (hipMalloc((void**)&c->d_hc, (size_t)waves * kHcWorkBytes) != hipSuccess) return fail(c, PLZ4HIP_E_NOMEM, "HC workspace");
+    bool refused = false;  HIPCHK(c, c->hc.reserve((size_t)waves * kHcWorkBytes, c->hcOrder, &refused));
+    if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC workspace");
     c->hcWaves = waves;
     return PLZ4HIP_OK;
 }
 
-// ---- HC jobs and their workspaces.  hc_enter: called before an HC job is enqueued on `s` -- if the previous HC job went to a
-// different stream, `s` waits for it on the device.  hc_leave: marks the end of the job on `s`.
-int hc_enter(plz4hip_ctx* c, hipStream_t s)
+// The per-block HC workspace of at least `need` bytes; [0, 256) of a new one is zeroed (level 12's error flag, sticky).
+int reserve_h12(plz4hip_ctx* c, size_t need, bool* refused)
 {
-    if (c->hcPending && c->hcStream != s) HIPCHK(c, hipStreamWaitEvent(s, c->hcDone, 0));
-    return PLZ4HIP_OK;
-}
-int hc_leave(plz4hip_ctx* c, hipStream_t s)
-{
-    if (!c->hcDone) HIPCHK(c, hipEventCreateWithFlags(&c->hcDone, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->hcDone, s));
-    c->hcPending = true; c->hcStream = s;
+    const bool grows = need > c->h12.bytes;
+    HIPCHK(c, c->h12.reserve(need, c->hcOrder, refused));
+    if (grows && !*refused) HIPCHK(c, zero_sync(c, c->h12.d, 256));
     return PLZ4HIP_OK;
 }
 
@@ -1685,9 +1680,9 @@ int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, H12Plan* pl, bool lazy, bo
     // hc_default_budget of what is free (and whatever the ctx holds already) unless PLZ4HIP_HC_BUDGET_GIB says more: the parser runs
     // one wave per block, so the more blocks a group has (up to three waves per SIMD: 3072), the better its latency is hidden --
     // 4096 blocks in two groups of 2048 instead of four of 1024: 1418 -> 1664 MiB/s.  plz4hip_ctx_trim gives the memory back.
-    size_t budget = hc_default_budget(freeB + c->h12Bytes);
+    size_t budget = hc_default_budget(freeB + c->h12.bytes);
     if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) { const long g = atol(v); if (g >= 1) budget = (size_t)g << 30; }
-    if (budget < c->h12Bytes) budget = c->h12Bytes;
+    if (budget < c->h12.bytes) budget = c->h12.bytes;
     int64_t grp = (int64_t)(budget / pl->perBlock);
     if (const char* v = getenv("PLZ4HIP_HC12_GROUP")) { const int gv = atoi(v); if (gv >= 1) grp = gv; }
     if (grp < 1) grp = 1;
@@ -1724,18 +1719,9 @@ int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, H12Plan* pl, bool lazy, bo
             pl->total = pl->offPieces + round_up((size_t)pl->group * kLzMaxSegs * 2 * sizeof(LzPiece), 256);
         }
         if (getenv("PLZ4HIP_VERBOSE"))
-            fprintf(stderr, "plz4hip: level 12, %d blocks: free %zu MiB, held %zu MiB, groups of %d (%zu MiB)\n", nBlocks, freeB >> 20, c->h12Bytes >> 20, pl->group, pl->total >> 20);
-        if (pl->total <= c->h12Bytes) break;
-        if (c->hcPending) HIPCHK(c, hipEventSynchronize(c->hcDone));          // nothing may still use the old workspace
-        if (c->d_h12) hipFree(c->d_h12);
-        c->d_h12 = nullptr; c->h12Bytes = 0;
-        if (hipMalloc((void**)&c->d_h12, pl->total) == hipSuccess) {
-            c->h12Bytes = pl->total;
-            HIPCHK(c, zero_sync(c, c->d_h12, 256));
-            break;
-        }
-        (void)hipGetLastError();
-        c->d_h12 = nullptr;
+            fprintf(stderr, "plz4hip: level 12, %d blocks: free %zu MiB, held %zu MiB, groups of %d (%zu MiB)\n", nBlocks, freeB >> 20, c->h12.bytes >> 20, pl->group, pl->total >> 20);
+        bool refused = false;  if (int rc = reserve_h12(c, pl->total, &refused)) return rc;
+        if (!refused) break;
         if (grp <= 1) return fail(c, PLZ4HIP_E_NOMEM, "level-12 workspace");
         grp = (grp + 1) / 2;                                                  // refused: smaller groups
     }
@@ -1749,36 +1735,36 @@ bool use_h12(const CodecArgs& a, int maxLen) { return a.level >= 12 && !a.hcEx &
 // wave-wide, instead of every position's search up front, lz4hc12_device.inl)
 bool use_lazy(const CodecArgs& a, int maxLen) { return a.level >= 3 && (a.level <= 11 || getenv("PLZ4HIP_HC12_LAZY") != nullptr) && !a.hcEx && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_LAZY_OFF") == nullptr; }
 
-int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, plz4hip_ctx::L1Ws* ws, bool* midDeclined = nullptr,
+int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined = nullptr,
               const CodecArgs* rider = nullptr);
 
 // Enqueue one HC call of nb blocks (a: everything but queue / workspace filled in) on s.  rawMode: LZ4 blocks, else records.
 int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked);
 int launch_hc(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode)
 {
-    if (int rc = hc_enter(c, s)) return rc;
+    HIPCHK(c, c->hcOrder.wait(s));
+    // Whatever was enqueued uses the ctx's workspaces, also when the body left early: the call's stream joins the builder's
+    // stream (a completed body has done so group by group) and the job is marked in any case, so that a following trim /
+    // destroy / HC job waits for kernels that may still run.
+    MarkOnExit job;
+    job.arm(c->hcOrder, s);
     bool forked = false;
     const int rc = launch_hc_body(c, s, a, nb, maxLen, rawMode, &forked);
-    // Whatever was enqueued uses the ctx's workspaces, also when the body left early: the call's stream joins the builder's
-    // stream (a completed body has done so group by group) and the event behind the job is recorded in any case, so that a
-    // following trim / destroy / HC job waits for kernels that may still run.
     if (rc != PLZ4HIP_OK && forked && c->hcBuildStream && c->evHcFork
         && hipEventRecord(c->evHcFork, c->hcBuildStream) == hipSuccess) (void)hipStreamWaitEvent(s, c->evHcFork, 0);
-    const int rc2 = hc_leave(c, s);
-    return rc != PLZ4HIP_OK ? rc : rc2;
+    if (rc != PLZ4HIP_OK) return rc;
+    HIPCHK(c, job.leave());
+    return PLZ4HIP_OK;
 }
 int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked)
 {
     hipError_t e;
     const auto prep_ext = [&]() -> int {                                    // the blocks' segments laid out, their lengths noted (k_hc_ext_prep)
-        if (nb > c->hcPfxCap) {
-            if (c->hcPending) HIPCHK(c, hipEventSynchronize(c->hcDone));
-            if (c->d_hcPfx) hipFree(c->d_hcPfx);
-            c->d_hcPfx = nullptr; c->hcPfxCap = 0;
-            if (hipMalloc((void**)&c->d_hcPfx, (size_t)nb * 4 + 1024) != hipSuccess) return fail(c, PLZ4HIP_E_NOMEM, "HC segment lengths");
-            c->hcPfxCap = nb + 256;
+        if ((size_t)nb * 4 > c->hcPfx.bytes) {                               // (grown with room for 256 blocks more)
+            bool refused = false;  HIPCHK(c, c->hcPfx.reserve((size_t)nb * 4 + 1024, c->hcOrder, &refused));
+            if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC segment lengths");
         }
-        a.hcPfx = c->d_hcPfx; a.rawMode = rawMode; a.nBlocks = nb; a.blk0 = 0;
+        a.hcPfx = (int32_t*)c->hcPfx.d; a.rawMode = rawMode; a.nBlocks = nb; a.blk0 = 0;
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         hipLaunchKernelGGL(k_hc_ext_prep, dim3(grid_for(nb, c->cus * 8)), dim3(64), 0, s, a);
         return PLZ4HIP_OK;
@@ -1788,7 +1774,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         // meantime): the one-thread parser over the context's two sets of tables writes them now
         if (a0.dict == nullptr && a0.dictLen < 0) return PLZ4HIP_OK;
         if (int rc = ensure_hc(c)) return rc;
-        CodecArgs x = a0; x.hcWork = c->d_hc; x.blk0 = 0; x.nBlocks = nb; x.h12Chain = nullptr; x.h12Rank = nullptr; x.h12List = nullptr;
+        CodecArgs x = a0; x.hcWork = c->hc.d; x.blk0 = 0; x.nBlocks = nb; x.h12Chain = nullptr; x.h12Rank = nullptr; x.h12List = nullptr;
         x.queue = next_queue(c, s, &e); HIPCHK(c, e);
         if (rawMode) hipLaunchKernelGGL(k_encode_raw_hc, dim3(grid_for(nb, c->hcWaves)), dim3(64), 0, s, x);
         else         hipLaunchKernelGGL(k_encode_rec_hc, dim3(grid_for(nb, c->hcWaves)), dim3(64), 0, s, x);
@@ -1799,7 +1785,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
     if (a.level == 2 && (!a.hcEx || extOk) && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_MID_OFF") == nullptr) {
         // level 2, blocks up to 4 MiB: the staged call of level 1 with the level-2 walk as its parser (behind external segments too)
         if (int rc = ensure_hc(c)) return rc;
-        a.hcWork = c->d_hc;
+        a.hcWork = c->hc.d;
         if (a.hcEx) { if (int rc = prep_ext()) return rc; }
         bool declined = false;
         if (int rc = launch_l1(c, s, a, nb, maxLen, rawMode, nullptr, &declined)) return rc;
@@ -1818,14 +1804,14 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         H12Plan pl;
         if (int rc = plan_h12(c, nb, maxLen + (lazyEx ? 65536 : 0), &pl, lazy || seg12, !lazy)) return rc;
         if (lazyEx) { if (int rc = prep_ext()) return rc; }
-        a.h12Chain = (uint16_t*)(c->d_h12 + 256); a.h12ChainStride = pl.chainStride;
-        a.h12Rank = (uint32_t*)(c->d_h12 + pl.offRank); a.h12List = (uint32_t*)(c->d_h12 + pl.offList);
-        a.h12Offsets = (uint32_t*)(c->d_h12 + pl.offOffsets);
-        a.h12F = (Hc12F*)(c->d_h12 + pl.offF); a.h12FStride = pl.fStride;
-        a.h12Ws = c->d_h12 + pl.offWs; a.h12Err = (int32_t*)(c->d_h12 + pl.offErr); c->h12ErrOff = pl.offErr;
+        a.h12Chain = (uint16_t*)(c->h12.d + 256); a.h12ChainStride = pl.chainStride;
+        a.h12Rank = (uint32_t*)(c->h12.d + pl.offRank); a.h12List = (uint32_t*)(c->h12.d + pl.offList);
+        a.h12Offsets = (uint32_t*)(c->h12.d + pl.offOffsets);
+        a.h12F = (Hc12F*)(c->h12.d + pl.offF); a.h12FStride = pl.fStride;
+        a.h12Ws = c->h12.d + pl.offWs; a.h12Err = (int32_t*)(c->h12.d + pl.offErr); c->h12ErrOff = pl.offErr;
         a.rawMode = rawMode;
         if (lazy || seg12) {
-            if (lazy && a.level >= 10) { if (int rc = ensure_hc(c)) return rc; a.hcWork = c->d_hc; }
+            if (lazy && a.level >= 10) { if (int rc = ensure_hc(c)) return rc; a.hcWork = c->hc.d; }
             if (!c->hcLazyWaves) {
                 int per = 0;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_hc_lazy<false>, 64, 0) != hipSuccess || per < 1) per = 8;
@@ -1834,10 +1820,10 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
                 c->hcLazyExWaves = c->cus * per;
             }
             a.l1MaxLen = maxLen; a.l1Seq = (uint64_t*)a.h12F; a.l1SeqStride = pl.fStride; a.l1MaxChunks = pl.maxChunks; a.l1Bk = nullptr;
-            a.l1Info = (SeqInfo*)(c->d_h12 + pl.offInfo);
-            a.l1ChunkBytes = (uint32_t*)(c->d_h12 + pl.offChunkB); a.l1ChunkOff = (uint32_t*)(c->d_h12 + pl.offChunkO);
-            a.lzRec = (uint64_t*)(c->d_h12 + pl.offRec); a.lzBridge = (uint64_t*)(c->d_h12 + pl.offBridge); a.lzRecStride = pl.recStride;
-            a.lzMeta = (LzSegMeta*)(c->d_h12 + pl.offMeta); a.lzStarts = (uint64_t*)(c->d_h12 + pl.offStarts); a.lzPieces = (LzPiece*)(c->d_h12 + pl.offPieces);
+            a.l1Info = (SeqInfo*)(c->h12.d + pl.offInfo);
+            a.l1ChunkBytes = (uint32_t*)(c->h12.d + pl.offChunkB); a.l1ChunkOff = (uint32_t*)(c->h12.d + pl.offChunkO);
+            a.lzRec = (uint64_t*)(c->h12.d + pl.offRec); a.lzBridge = (uint64_t*)(c->h12.d + pl.offBridge); a.lzRecStride = pl.recStride;
+            a.lzMeta = (LzSegMeta*)(c->h12.d + pl.offMeta); a.lzStarts = (uint64_t*)(c->h12.d + pl.offStarts); a.lzPieces = (LzPiece*)(c->h12.d + pl.offPieces);
             a.lzMinSeg = 8192;
             if (const char* v = getenv("PLZ4HIP_HC_MIN_SEG")) { const int m = atoi(v); if (m >= 64) a.lzMinSeg = m; }     // tests: many segments in small blocks
         }
@@ -1971,7 +1957,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         if (lazyEx) { if (int rc = ctx_blocks(a0)) return rc; }
     } else {
         if (int rc = ensure_hc(c)) return rc;
-        a.hcWork = c->d_hc; a.nBlocks = nb;
+        a.hcWork = c->hc.d; a.nBlocks = nb;
         a.h12Chain = nullptr;
         a.blk0 = 0;
         int per = nb;                     // blocks per launch
@@ -1985,14 +1971,14 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
             const int64_t stride = (int64_t)round_up((size_t)maxLen + 1, 1024);
             size_t freeB = 0, totalB = 0;
             if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-            size_t budget = hc_default_budget(freeB + c->h12Bytes);      // the chain alone
+            size_t budget = hc_default_budget(freeB + c->h12.bytes);      // the chain alone
             // the lists are worth more memory than that: these kernels live on the number of blocks in flight (7 waves per SIMD
             // fit), and 4096 blocks of 4 MiB with their lists (40 MiB each) are 160 GiB: a machine that is there for this sets PLZ4HIP_HC_BUDGET_GIB;
             // plz4hip_ctx_trim gives it back.  What the ctx already holds is used in any case.
-            size_t budgetLists = hc_default_budget(freeB + c->h12Bytes);
+            size_t budgetLists = hc_default_budget(freeB + c->h12.bytes);
             if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) { const long g = atol(v); if (g >= 1) budget = budgetLists = (size_t)g << 30; }
-            if (budget < c->h12Bytes) budget = c->h12Bytes;
-            if (budgetLists < c->h12Bytes) budgetLists = c->h12Bytes;
+            if (budget < c->h12.bytes) budget = c->h12.bytes;
+            if (budgetLists < c->h12.bytes) budgetLists = c->h12.bytes;
             const size_t slack = 256 + 4 * 256;
             const size_t chainPer = (size_t)stride * 2;
             const size_t listsPer = chainPer + (size_t)stride * 4 + ((size_t)stride + 8) * 4 + (size_t)kHcHashEntries * 4;
@@ -2009,38 +1995,27 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
             // a group has to keep the chip busy: below 2048 blocks in flight the lists lose to the chain alone over more blocks
             // at levels 4..9; the optimal parser's levels gain an order of magnitude and take them in any case
             lists = perLists >= 1 && (perLists == nb || perLists >= (a.level >= 10 ? 256 : 2048) || perChain < 1);
-            if (lists && perLists > c->h12Bytes / listsPer) {             // try the large request first: refused -> the chain alone
-                if (c->hcPending) HIPCHK(c, hipEventSynchronize(c->hcDone));
-                if (c->d_h12) hipFree(c->d_h12);
-                c->d_h12 = nullptr; c->h12Bytes = 0;
-                const size_t need = slack + (size_t)perLists * listsPer;
-                if (hipMalloc((void**)&c->d_h12, need) != hipSuccess) { (void)hipGetLastError(); c->d_h12 = nullptr; lists = false; }
-                else { c->h12Bytes = need; HIPCHK(c, zero_sync(c, c->d_h12, 256)); }
+            if (lists && perLists > c->h12.bytes / listsPer) {            // try the large request first: refused -> the chain alone
+                bool refused = false;  if (int rc = reserve_h12(c, slack + (size_t)perLists * listsPer, &refused)) return rc;
+                if (refused) lists = false;
             }
             const int perPre = lists ? perLists : perChain;
             if (getenv("PLZ4HIP_VERBOSE"))
                 fprintf(stderr, "plz4hip: HC level %d, %d blocks: free %zu MiB, held %zu MiB, lists %d, %d blocks per group\n", a.level, nb,
-                        freeB >> 20, c->h12Bytes >> 20, (int)lists, perPre);
+                        freeB >> 20, c->h12.bytes >> 20, (int)lists, perPre);
             if (perPre >= 1) {
                 per = perPre;
-                const size_t need = slack + (size_t)per * (lists ? listsPer : chainPer);
-                if (need > c->h12Bytes) {
-                    if (c->hcPending) HIPCHK(c, hipEventSynchronize(c->hcDone));
-                    if (c->d_h12) hipFree(c->d_h12);
-                    c->d_h12 = nullptr; c->h12Bytes = 0;
-                    if (hipMalloc((void**)&c->d_h12, need) != hipSuccess) { c->d_h12 = nullptr; return fail(c, PLZ4HIP_E_NOMEM, "HC chain workspace"); }
-                    c->h12Bytes = need;
-                    HIPCHK(c, zero_sync(c, c->d_h12, 256));
-                }
+                bool refused = false;  if (int rc = reserve_h12(c, slack + (size_t)per * (lists ? listsPer : chainPer), &refused)) return rc;
+                if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC chain workspace");
                 chainBytes = round_up((size_t)per * chainPer, 256);
                 rankBytes = round_up((size_t)per * (size_t)stride * 4, 256);
                 listBytes = round_up((size_t)per * ((size_t)stride + 8) * 4, 256);
-                a.h12Chain = (uint16_t*)(c->d_h12 + 256); a.h12ChainStride = stride;
+                a.h12Chain = (uint16_t*)(c->h12.d + 256); a.h12ChainStride = stride;
                 a.h12Rank = nullptr; a.h12List = nullptr; a.h12Offsets = nullptr;
                 if (lists) {
-                    a.h12Rank = (uint32_t*)(c->d_h12 + 256 + chainBytes);
-                    a.h12List = (uint32_t*)(c->d_h12 + 256 + chainBytes + rankBytes);
-                    a.h12Offsets = (uint32_t*)(c->d_h12 + 256 + chainBytes + rankBytes + listBytes);
+                    a.h12Rank = (uint32_t*)(c->h12.d + 256 + chainBytes);
+                    a.h12List = (uint32_t*)(c->h12.d + 256 + chainBytes + rankBytes);
+                    a.h12Offsets = (uint32_t*)(c->h12.d + 256 + chainBytes + rankBytes + listBytes);
                 }
             }
         }
@@ -2075,7 +2050,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
 // be had, the caller then runs its one-kernel path.
 // rider: the record decode of another call (queue filled in) that shares the parse kernel's launch (k_l1_duplex); a call that
 // runs in groups carries it in its first group, one that takes the fused kernels launches it by itself.
-int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, plz4hip_ctx::L1Ws* ws, bool* midDeclined,
+int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined,
               const CodecArgs* rider)
 {
     hipError_t e;
@@ -2090,11 +2065,10 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         if (const char* v = getenv("PLZ4HIP_L1_WORKSPACES")) { if (atoi(v) == 1) nws = 1; }
         int mine = -1, idle = -1, fresh = -1;
         for (int i = 0; i < nws; ++i) {
-            if (c->l1[i].d && c->l1Stream[i] == s && mine < 0) mine = i;
-            if (c->l1[i].d && idle < 0 && (!c->l1Pending[i] || hipEventQuery(c->l1Done[i]) == hipSuccess)) idle = i;   // (its last job is over)
+            if (c->l1[i].d && c->l1Order[i].stream == s && mine < 0) mine = i;
+            if (c->l1[i].d && idle < 0 && c->l1Order[i].idle()) idle = i;
             if (!c->l1[i].d && fresh < 0) fresh = i;
         }
-        (void)hipGetLastError();                                                          // (hipErrorNotReady of the query)
         wsi = mine >= 0 ? mine : (idle >= 0 ? idle : (fresh >= 0 ? fresh : 0));
         ws = &c->l1[wsi];
     }
@@ -2108,14 +2082,13 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     if (shared && !fused && wsi != 0 && !ws->d) {
         // a SECOND workspace is there for overlap: it is taken whole or not at all (a smaller one would cut this call into groups,
         // which costs more than waiting for the first workspace does)
-        if (hipMalloc((void**)&ws->d, need_for(nb)) == hipSuccess) ws->bytes = need_for(nb);
-        else {
-            (void)hipGetLastError();
-            ws->d = nullptr; ws->bytes = 0; wsi = 0; ws = &c->l1[0];
-            c->l1Refused = 8;                                                    // (the next calls do not ask again)
+        bool refused = false;  HIPCHK(c, ws->reserve(need_for(nb), c->l1Order[wsi], &refused));
+        if (refused) {
+            wsi = 0; ws = &c->l1[0]; c->l1Refused = 8;                           // (the next calls do not ask again)
             if (getenv("PLZ4HIP_VERBOSE")) fprintf(stderr, "plz4hip: level 1: no room for a second workspace of %zu MiB, sharing the first\n", need_for(nb) >> 20);
         }
     }
+    StreamOrder* const order = shared ? &c->l1Order[wsi] : nullptr;                      // (a slot's own workspace: the slot's stream)
     if (!fused && need_for(nb) > ws->bytes) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
@@ -2128,14 +2101,8 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         while (grp >= 1) {
             const int nGroups = (int)((nb + grp - 1) / grp);
             per = (nb + nGroups - 1) / nGroups;
-            if (need_for(per) <= ws->bytes) break;
-            if (shared && c->l1Pending[wsi]) HIPCHK(c, hipEventSynchronize(c->l1Done[wsi]));     // nothing may still use the old workspace
-            else if (!shared) HIPCHK(c, hipStreamSynchronize(s));
-            if (ws->d) hipFree(ws->d);
-            ws->d = nullptr; ws->bytes = 0;
-            if (hipMalloc((void**)&ws->d, need_for(per)) == hipSuccess) { ws->bytes = need_for(per); break; }
-            (void)hipGetLastError();
-            ws->d = nullptr;
+            bool refused = false;  HIPCHK(c, order ? ws->reserve(need_for(per), *order, &refused) : ws->reserve(need_for(per), s, &refused));
+            if (!refused) break;
             grp = grp / 2;                                                              // refused: smaller groups
         }
         if (grp < 1) fused = true;                                                      // not even one block: the fused kernels need no workspace
@@ -2151,7 +2118,9 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         HIPCHK(c, hipGetLastError());
         return PLZ4HIP_OK;
     }
-    if (shared && c->l1Pending[wsi] && c->l1Stream[wsi] != s) HIPCHK(c, hipStreamWaitEvent(s, c->l1Done[wsi], 0));
+    // from here on the job is marked behind whatever was enqueued, whichever way the call ends
+    MarkOnExit job, fxJob;
+    if (order) { HIPCHK(c, order->wait(s)); job.arm(*order, s); }
     a.l1MaxLen = maxLen; a.l1SeqStride = (int64_t)seqStride; a.l1MaxChunks = maxChunks;
     a.l1Info = (SeqInfo*)ws->d;
     a.l1ChunkBytes = (uint32_t*)(ws->d + round_up((size_t)per * sizeof(SeqInfo), 256));
@@ -2175,18 +2144,13 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             const size_t nP = (size_t)per * fx.P;
             const size_t offIn = round_up(nP * sizeof(FxPiece), 256), offOut = offIn + nP * kFxTab * 4, offRec = offOut + 2 * nP * kFxTab * 4;
             const size_t need = offRec + nP * (size_t)fx.recStride * 8;
-            if (c->fxPending && c->fxStream != s) HIPCHK(c, hipStreamWaitEvent(s, c->fxDone, 0));
-            if (need > c->fxBytes) {
-                if (c->fxPending) HIPCHK(c, hipEventSynchronize(c->fxDone));
-                if (c->d_fx) hipFree(c->d_fx);
-                c->d_fx = nullptr; c->fxBytes = 0;
-                if (hipMalloc((void**)&c->d_fx, need) != hipSuccess) { (void)hipGetLastError(); c->d_fx = nullptr; }
-                else c->fxBytes = need;
-            }
-            if (c->d_fx) {
-                fx.meta = (FxPiece*)c->d_fx; fx.tabIn = (uint32_t*)(c->d_fx + offIn); fx.tabOut = (uint32_t*)(c->d_fx + offOut);
-                fx.rec = (uint64_t*)(c->d_fx + offRec);
+            HIPCHK(c, c->fxOrder.wait(s));
+            bool refused = false;  HIPCHK(c, c->fx.reserve(need, c->fxOrder, &refused));
+            if (!refused) {
+                fx.meta = (FxPiece*)c->fx.d; fx.tabIn = (uint32_t*)(c->fx.d + offIn); fx.tabOut = (uint32_t*)(c->fx.d + offOut);
+                fx.rec = (uint64_t*)(c->fx.d + offRec);
                 useFx = true;
+                fxJob.arm(c->fxOrder, s);
             }
         }
     }
@@ -2263,16 +2227,8 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 3) / 4), dim3(256), 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
-    if (shared) {
-        if (!c->l1Done[wsi]) HIPCHK(c, hipEventCreateWithFlags(&c->l1Done[wsi], hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->l1Done[wsi], s));
-        c->l1Pending[wsi] = true; c->l1Stream[wsi] = s;
-    }
-    if (useFx) {
-        if (!c->fxDone) HIPCHK(c, hipEventCreateWithFlags(&c->fxDone, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->fxDone, s));
-        c->fxPending = true; c->fxStream = s;
-    }
+    HIPCHK(c, job.leave());
+    HIPCHK(c, fxJob.leave());
     return PLZ4HIP_OK;
 }
 
@@ -2291,6 +2247,7 @@ enum { kHistNone = 0, kHistDict = 1, kHistLinked = 2 };
 int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t maxIn, int64_t maxOut, bool records, int hist = kHistNone)
 {
     hipError_t e;
+    MarkOnExit job;
     int dxMax = 128;
     if (const char* v = getenv("PLZ4HIP_DX_MAX_BLOCKS")) dxMax = atoi(v);
     bool dx = nb <= dxMax && maxIn >= 16384 && maxIn <= (int64_t)(6 << 20) && maxOut >= 1;
@@ -2309,22 +2266,18 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
         const size_t offInfo = offUnits + round_up((size_t)nb * maxSeg * sizeof(DxUnit), 256), offRec = offInfo + round_up((size_t)nb * sizeof(DxInfo), 256);
         const size_t offLink = offRec + round_up((size_t)nb * 16, 256);
         const size_t need = offLink + (hist ? round_up((size_t)nb * (12 + 4 * (kDxlMaxRounds + 1)), 256) : 0);
-        if (c->dxPending && c->dxStream != s) HIPCHK(c, hipStreamWaitEvent(s, c->dxDone, 0));
-        if (need > c->dxBytes) {
-            if (c->dxPending) HIPCHK(c, hipEventSynchronize(c->dxDone));
-            if (c->d_dx) hipFree(c->d_dx);
-            c->d_dx = nullptr; c->dxBytes = 0;
-            if (hipMalloc((void**)&c->d_dx, need) != hipSuccess) { (void)hipGetLastError(); c->d_dx = nullptr; dx = false; }   // no room: one wave per block
-            else c->dxBytes = need;
-        }
+        HIPCHK(c, c->dxOrder.wait(s));
+        bool refused = false;  HIPCHK(c, c->dx.reserve(need, c->dxOrder, &refused));
+        if (refused) dx = false;                                                // no room: one wave per block
         if (dx) {
-            a.dxT = (uint64_t*)c->d_dx; a.dxTStride = (int64_t)tStride;
-            a.dxPtr = (uint32_t*)(c->d_dx + offPtr); a.dxPtrStride = (int64_t)pStride;
-            a.dxUnits = (DxUnit*)(c->d_dx + offUnits); a.dxMaxSeg = maxSeg;
-            a.dxInfo = (DxInfo*)(c->d_dx + offInfo);
+            job.arm(c->dxOrder, s);
+            a.dxT = (uint64_t*)c->dx.d; a.dxTStride = (int64_t)tStride;
+            a.dxPtr = (uint32_t*)(c->dx.d + offPtr); a.dxPtrStride = (int64_t)pStride;
+            a.dxUnits = (DxUnit*)(c->dx.d + offUnits); a.dxMaxSeg = maxSeg;
+            a.dxInfo = (DxInfo*)(c->dx.d + offInfo);
             const bool hashed = records && a.blockChecksum;
             if (records) {
-                int64_t* so = (int64_t*)(c->d_dx + offRec); int32_t* ln = (int32_t*)(so + nb);
+                int64_t* so = (int64_t*)(c->dx.d + offRec); int32_t* ln = (int32_t*)(so + nb);
                 hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, so, ln);
                 a.dxSrcOff = so; a.dxLen = ln;
                 if (hashed) {
@@ -2350,7 +2303,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
                 if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
                 hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
             } else {
-                a.dxlFirst = (int32_t*)(c->d_dx + offLink); a.dxlChain = a.dxlFirst + nb; a.dxlGood = a.dxlChain + nb;
+                a.dxlFirst = (int32_t*)(c->dx.d + offLink); a.dxlChain = a.dxlFirst + nb; a.dxlGood = a.dxlChain + nb;
                 a.dxlMoved = (uint32_t*)(a.dxlGood + nb);
                 // the copy chain of a call can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
                 int rounds = 1;
@@ -2376,11 +2329,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
     else if (records)  hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     else               hipLaunchKernelGGL(k_decode_raw, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     HIPCHK(c, hipGetLastError());
-    if (dx) {
-        if (!c->dxDone) HIPCHK(c, hipEventCreateWithFlags(&c->dxDone, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->dxDone, s));
-        c->dxPending = true; c->dxStream = s;
-    }
+    HIPCHK(c, job.leave());
     return PLZ4HIP_OK;
 }
 
@@ -2439,7 +2388,7 @@ int plz4hip_ctx_create(int device, plz4hip_ctx** out)
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&decPer, k_decode_rec, 64, 0);
     if (e != hipSuccess) {
         fprintf(stderr, "plz4hip_ctx_create: %s\n", hipGetErrorString(e));
-        if (c->d_queues) hipFree(c->d_queues);
+        for (void* p : {(void*)c->d_queues, (void*)c->d_gate, (void*)c->d_counters}) if (p) hipFree(p);
         if (c->stream) hipStreamDestroy(c->stream);
         delete c;
         return PLZ4HIP_E_DEVICE;
@@ -2457,39 +2406,22 @@ void plz4hip_ctx_destroy(plz4hip_ctx* c)
 {
     if (!c) return;
     DeviceGuard dg(c->device);
+    // the jobs still in flight on the callers' streams first: every workspace is freed behind its last job
+    for (auto& w : c->owned()) (void)w.buf->release(*w.order);
+    for (auto& w : c->owned()) w.order->destroy();
     if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
-    if (c->d_queues) hipFree(c->d_queues);
     for (auto& sl : c->slot) {
         if (sl.s) { hipStreamSynchronize(sl.s); hipStreamDestroy(sl.s); }
         if (sl.evData) hipEventDestroy(sl.evData);
         if (sl.evHash) hipEventDestroy(sl.evHash);
         if (sl.h) hipHostFree(sl.h);
         if (sl.d) hipFree(sl.d);
-        if (sl.l1.d) hipFree(sl.l1.d);
+        sl.l1.release();
     }
-    if (c->d_hc) hipFree(c->d_hc);
-    if (c->d_h12) hipFree(c->d_h12);
-    for (int i = 0; i < plz4hip_ctx::kL1Shared; ++i) {
-        if (c->l1Pending[i]) hipEventSynchronize(c->l1Done[i]);
-        if (c->l1[i].d) hipFree(c->l1[i].d);
-        if (c->l1Done[i]) hipEventDestroy(c->l1Done[i]);
-    }
-    if (c->fxPending) hipEventSynchronize(c->fxDone);
-    if (c->d_fx) hipFree(c->d_fx);
-    if (c->fxDone) hipEventDestroy(c->fxDone);
-    if (c->dxPending) { hipEventSynchronize(c->dxDone); c->dxPending = false; }
-    if (c->d_dx) { hipFree(c->d_dx); c->d_dx = nullptr; c->dxBytes = 0; }
-    if (c->dxDone) { hipEventDestroy(c->dxDone); c->dxDone = nullptr; }
-    if (c->evDxFork) { hipEventDestroy(c->evDxFork); c->evDxFork = nullptr; }
-    if (c->evDxHash) { hipEventDestroy(c->evDxHash); c->evDxHash = nullptr; }
-    if (c->d_counters) hipFree(c->d_counters);
-    if (c->d_lenCopy) hipFree(c->d_lenCopy);
-    if (c->d_hcPfx) hipFree(c->d_hcPfx);
-    if (c->lenDone) hipEventDestroy(c->lenDone);
-    if (c->d_gate) hipFree(c->d_gate);
-    if (c->hcDone) hipEventDestroy(c->hcDone);
+    for (hipEvent_t ev : {c->evDxFork, c->evDxHash}) if (ev) hipEventDestroy(ev);
     if (c->hashStream) { hipStreamSynchronize(c->hashStream); hipStreamDestroy(c->hashStream); }
     if (c->hcBuildStream) { hipStreamSynchronize(c->hcBuildStream); hipStreamDestroy(c->hcBuildStream); }
+    for (void* p : {(void*)c->d_queues, (void*)c->d_gate, (void*)c->d_counters}) if (p) hipFree(p);
     for (hipEvent_t ev : {c->evHcFork, c->evHcHist, c->evHcChain[0], c->evHcChain[1], c->evHcFree[0], c->evHcFree[1]}) if (ev) hipEventDestroy(ev);
     delete c;
 }
@@ -2500,24 +2432,14 @@ int plz4hip_ctx_trim(plz4hip_ctx* c)
     if (!c) return PLZ4HIP_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
-    if (c->hcPending) { HIPCHK(c, hipEventSynchronize(c->hcDone)); c->hcPending = false; }
     for (auto& sl : c->slot) {
         if (sl.s) HIPCHK(c, hipStreamSynchronize(sl.s));
         if (sl.h) { hipHostFree(sl.h); sl.h = nullptr; sl.hcap = 0; }
         if (sl.d) { hipFree(sl.d); sl.d = nullptr; sl.dcap = 0; }
-        if (sl.l1.d) { hipFree(sl.l1.d); sl.l1.d = nullptr; sl.l1.bytes = 0; }
+        sl.l1.release();
     }
-    for (int i = 0; i < plz4hip_ctx::kL1Shared; ++i) {
-        if (c->l1Pending[i]) { HIPCHK(c, hipEventSynchronize(c->l1Done[i])); c->l1Pending[i] = false; }
-        if (c->l1[i].d) { hipFree(c->l1[i].d); c->l1[i].d = nullptr; c->l1[i].bytes = 0; }
-        c->l1Stream[i] = nullptr;
-    }
-    if (c->d_hc) { hipFree(c->d_hc); c->d_hc = nullptr; c->hcWaves = 0; }
-    if (c->d_h12) { hipFree(c->d_h12); c->d_h12 = nullptr; c->h12Bytes = 0; }
-    if (c->dxPending) { HIPCHK(c, hipEventSynchronize(c->dxDone)); c->dxPending = false; }
-    if (c->d_dx) { hipFree(c->d_dx); c->d_dx = nullptr; c->dxBytes = 0; }
-    if (c->fxPending) { HIPCHK(c, hipEventSynchronize(c->fxDone)); c->fxPending = false; }
-    if (c->d_fx) { hipFree(c->d_fx); c->d_fx = nullptr; c->fxBytes = 0; }
+    for (auto& w : c->owned()) if (w.trimmed) HIPCHK(c, w.buf->release(*w.order));
+    c->hcWaves = 0;
     return PLZ4HIP_OK;
 }
 
@@ -2560,32 +2482,30 @@ int plz4hip_dev_compress(plz4hip_ctx* c, int nBlocks, const void* src, int64_t s
     a.dst = (uint8_t*)dst; a.dstStride = dstStride; a.dstCap = dstCap;
     a.result = result; a.nBlocks = nBlocks;
     a.dictLen = -1; a.prevTailLen = -1;
+    MarkOnExit job;
     if (maxLen > 0) {
         // the kernels index per-block workspaces sized from maxLen: they read lengths that were checked against it
-        if (nBlocks > c->lenCopyCap) {
-            HIPCHK(c, hipDeviceSynchronize());                           // (a copy an earlier call still reads is not freed under it)
-            if (c->d_lenCopy) hipFree(c->d_lenCopy);
-            c->d_lenCopy = nullptr; c->lenCopyCap = 0;
-            if (hipMalloc((void**)&c->d_lenCopy, (size_t)nBlocks * 4 + 1024) != hipSuccess) return fail(c, PLZ4HIP_E_NOMEM, "plz4hip_dev_compress: length copy");
-            c->lenCopyCap = nBlocks + 256;
+        if ((size_t)nBlocks * 4 > c->lenCopy.bytes) {                     // (grown with room for 256 blocks more)
+            // (every reader of the copy was enqueued on its call's stream -- the HC builder's stream joins it -- in front of that
+            // call's mark, on whichever way the call ended: the order's own event is enough to free it)
+            bool refused = false;  HIPCHK(c, c->lenCopy.reserve((size_t)nBlocks * 4 + 1024, c->lenOrder, &refused));
+            if (refused) return fail(c, PLZ4HIP_E_NOMEM, "plz4hip_dev_compress: length copy");
         }
-        if (c->lenPending && c->lenStream != s) HIPCHK(c, hipStreamWaitEvent(s, c->lenDone, 0));   // the last job's kernels still read the copy
-        hipLaunchKernelGGL(k_check_len, dim3((nBlocks + 255) / 256), dim3(256), 0, s, srcLen, maxLen, nBlocks, c->d_lenCopy, result, 0);
-        a.srcLen = c->d_lenCopy;
+        HIPCHK(c, c->lenOrder.wait(s));                                   // the last job's kernels still read the copy
+        job.arm(c->lenOrder, s);                                          // (also after a failed launch: whatever was enqueued reads the copy)
+        hipLaunchKernelGGL(k_check_len, dim3((nBlocks + 255) / 256), dim3(256), 0, s, srcLen, maxLen, nBlocks, (int32_t*)c->lenCopy.d, result, 0);
+        a.srcLen = (const int32_t*)c->lenCopy.d;
     }
     int rc;
     if (is_hc_level(level)) { a.level = level; rc = launch_hc(c, s, a, nBlocks, maxLen, 1); }
     else rc = launch_l1(c, s, a, nBlocks, maxLen, 1, nullptr);           // (maxLen <= 0: lengths unknown to the host -> fused kernels)
     if (rc == PLZ4HIP_OK && maxLen > 0) {
-        hipLaunchKernelGGL(k_check_len, dim3((nBlocks + 255) / 256), dim3(256), 0, s, srcLen, maxLen, nBlocks, c->d_lenCopy, result, 1);
+        hipLaunchKernelGGL(k_check_len, dim3((nBlocks + 255) / 256), dim3(256), 0, s, srcLen, maxLen, nBlocks, (int32_t*)c->lenCopy.d, result, 1);
         HIPCHK(c, hipGetLastError());
     }
-    if (maxLen > 0) {                                                     // (also after a failed launch: whatever was enqueued reads the copy)
-        if (!c->lenDone) HIPCHK(c, hipEventCreateWithFlags(&c->lenDone, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->lenDone, s));
-        c->lenPending = true; c->lenStream = s;
-    }
-    return rc;
+    if (rc != PLZ4HIP_OK) return rc;
+    HIPCHK(c, job.leave());
+    return PLZ4HIP_OK;
 }
 
 int plz4hip_dev_decompress(plz4hip_ctx* c, int nBlocks, const void* src, int64_t srcStride, const int32_t* srcLen,
@@ -2993,11 +2913,11 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
     }
     for (; retired < nChunks && rc == PLZ4HIP_OK; ++retired) rc = retire(retired);
     if (rc != PLZ4HIP_OK) for (int i = 0; i < nSlots; ++i) if (c->slot[i].s) hipStreamSynchronize(c->slot[i].s);   // nothing left in flight
-    if (rc == PLZ4HIP_OK && hcMode && c->d_h12 && dj->level >= 12) {
+    if (rc == PLZ4HIP_OK && hcMode && c->h12.d && dj->level >= 12) {
         // the level-12 search kernel bounds its spins and raises this flag if it ever gives up (never seen): an engine failure,
         // not a result
         int32_t flag = 0;
-        HIPCHK(c, copy_sync(c, &flag, c->d_h12 + c->h12ErrOff, 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, copy_sync(c, &flag, c->h12.d + c->h12ErrOff, 4, hipMemcpyDeviceToHost));
         if (flag) return fail(c, PLZ4HIP_E_DEVICE, "level-12 search kernel gave up (spin guard)");
     }
     return rc;

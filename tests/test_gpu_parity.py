@@ -587,6 +587,49 @@ def test_gpu_dev_compress_on_two_streams_of_one_ctx(ref, orc):
 
 
 @pytest.mark.gpu
+def test_gpu_close_with_jobs_in_flight_on_two_streams(ref, orc):
+    """plz4hip_ctx_destroy waits for the work in flight before it frees what that work uses: a level-9 encode on a side stream
+    (HC workspaces) and a plz4hip_dev_compress with maxLen on a second stream (level-1 workspace, the few-block parse's, the length
+    copy) are enqueued and the engine is closed at once -- no synchronise, no trim.  Both results must be the reference's."""
+    import torch
+    from plz4_amd._native import Engine
+    e = Engine(0)
+    dev = torch.device("cuda:0")
+    sa, sb = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    bsz, nb = 256 << 10, 48
+    data = np.concatenate([synth.text(bsz, seed=60 + i) for i in range(nb)])
+    rstride = e.stage_stride(bsz)
+    d_data = torch.from_numpy(data).to(dev)
+    d_stage = torch.zeros(nb * rstride, dtype=torch.uint8, device=dev)
+    d_rlen = torch.zeros(nb, dtype=torch.int32, device=dev)
+    n, stride = 300000, 1 << 19
+    srcs = [synth.text(n - 17 * i, seed=90 + i) for i in range(6)]
+    cap = orc.bound(n)
+    d_src = torch.zeros(len(srcs) * stride, dtype=torch.uint8, device=dev)
+    for i, s in enumerate(srcs):
+        d_src[i * stride:i * stride + s.size] = torch.from_numpy(s).to(dev)
+    d_len = torch.tensor([s.size for s in srcs], dtype=torch.int32, device=dev)
+    d_cap = torch.full((len(srcs),), cap, dtype=torch.int32, device=dev)
+    d_dst = torch.zeros(len(srcs) * stride, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(len(srcs), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    e.dev_encode_records(d_data.data_ptr(), data.size, bsz, True, d_stage.data_ptr(), d_rlen.data_ptr(), sa.cuda_stream, level=9)
+    e._chk(e.L.plz4hip_dev_compress(e.h, len(srcs), d_src.data_ptr(), stride, d_len.data_ptr(), d_dst.data_ptr(), stride,
+                                    d_cap.data_ptr(), 1, n, d_res.data_ptr(), sb.cuda_stream))
+    e.close()
+    torch.cuda.synchronize()
+    rlen = d_rlen.cpu().numpy(); stage = d_stage.cpu().numpy()
+    for i in range(nb):
+        want_n, want = ref.compress_hc(data[i * bsz:(i + 1) * bsz], bsz, 9)
+        rec = stage[i * rstride:i * rstride + int(rlen[i])]
+        assert want_n > 0 and rec.size == want_n + 8 and np.array_equal(rec[4:-4], want[:want_n]), i
+    res = d_res.cpu().numpy(); out = d_dst.cpu().numpy()
+    for i, s in enumerate(srcs):
+        want_n, want = orc.compress_fast(s, cap)
+        assert int(res[i]) == want_n and np.array_equal(out[i * stride:i * stride + want_n], want[:want_n]), i
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("nstreams,starve", [(2, False), (3, False), (2, True)])
 def test_gpu_duplex_body_calls_alternating_over_streams_of_one_ctx(orc, nstreams, starve):
     """The bench's pipelines in small: plz4hip_dev_duplex_body calls of DIFFERENT batches enqueued back to back on two (three)
