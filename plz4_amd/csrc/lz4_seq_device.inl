@@ -121,11 +121,17 @@ unsigned long long plz4_emu_cnt[32];              // test diagnostics: [0] grid 
                                                   // [10] 16-byte loads of the 36-byte window, [11] batches whose first walk executed a match that fills the 20-byte window,
                                                   // how a grid batch left the steady state: [12] given up (-> generic batch), [13] a match reached lastProbe (block done),
                                                   // [14] the search is past 64 misses, [15] the next batch is not the consecutive one (a long match), [16] the block's last
-                                                  // 224 bytes, [17] a piece's boundary ahead (kPiece); [18] warm-up boundaries passed (kPiece), [19] batches that took the 36-byte window
+                                                  // 224 bytes, [17] a piece's boundary ahead (kPiece); [18] warm-up boundaries passed (kPiece), [19] batches that took the 36-byte window,
+                                                  // the first walk of a grid batch: [20] not finished after its unconditional hops, [21] of those, the ones that also executed
+                                                  // a lane of x36, [22] no executed match while lane 0 has a successor (the first hop's guard), [23] three matches or
+                                                  // more, the first of them at lane 0
+unsigned long long plz4_emu_hops[18];             // batches by the number of matches their first walk executed (17: more)
 #define EMU_CNT(i, v) (plz4_emu_cnt[(i)] += (unsigned long long)(v))
+#define EMU_HOPS(mask) (plz4_emu_hops[min_(__builtin_popcountll(mask), 17)] += 1)
 #else
 #define SHFLF(x, f, l) plz4_bpermute((x)[0].f, (l))
 #define EMU_CNT(i, v) do {} while (0)
+#define EMU_HOPS(mask) do {} while (0)
 #endif
 // The block as a bounds-checked buffer, for the loads that only some lanes of a wave need (a candidate's window: 28.6 of 64 lanes on
 // text).  The number of load INSTRUCTIONS a batch issues stays fixed -- the pipeline's waits count instructions -- but a lane that is
@@ -139,6 +145,15 @@ unsigned long long plz4_emu_cnt[32];              // test diagnostics: [0] grid 
 #if !defined(PLZ4_PW)
 #define PLZ4_PW 3
 #endif
+// PLZ4_HOP: compile-time A/B of the grid batch's scalar hop (a finished walk stays on its last match, kHopN unconditional hops, one
+// question for "more hops" and take36); the product is built with it, -DPLZ4_HOP=0 is the walk as it was.
+#if !defined(PLZ4_HOP)
+#define PLZ4_HOP 1
+#endif
+#if !defined(PLZ4_HOP_N)
+#define PLZ4_HOP_N 8                                      // (the smallest number that leaves at most 2 % of a text block's batches unfinished: DESIGN 3.1)
+#endif
+enum { kHopN = PLZ4_HOP ? PLZ4_HOP_N : 6 };
 enum : uint32_t { kBufOff = 0x80000000u };                 // beyond any block (<= 4 MiB), and + 36 does not wrap
 #if defined(PLZ4_EMU)
 int plz4_emu_poison = 1;
@@ -318,7 +333,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         // rarely lives behind the single `trouble` question: the second rounds, and a batch that gives up or ends the block.
         // Those two set what the straight path needs to pass through steps 5 and 6 as a batch that executed nothing (mm = 0, Send = 0:
         // no record, anchor and search state as they were; keepIns / keepWidth for the two values step 6 would overwrite).
-        // The questions left on a clean batch's path: take36, more than six hops, `upd`, `trouble`, and the loop's test.
+        // The questions left on a clean batch's path: "more than eight hops, or take36" (one question), `upd`, `trouble`, and the loop's test.
         auto grid = [&](LVREF(GStage, prev), LVREF(GStage, cur), LVREF(GStage, next), const int base) -> int {
             const int probeStart = hasRe ? rePos : sBase + sIter;
             if (kPiece && !fxRec) nseq = 0;
@@ -436,6 +451,14 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             uint64_t probes = 0;
             int      Send = 0;
             int      finished = 0;
+            // The hop.  `succ` is the successor table in which a match without a successor is its OWN successor: a walk that has
+            // finished stays on its last match and marks it again, so a hop needs no test -- v_readlane -> v_readlane, and the mark
+            // beside it -- no bit of the mask has to be put right afterwards, the walk's last position is the last executed match
+            // (whose end the batch wants), and "not finished" is "the position I stand on is not marked yet".
+            LV(int, succ);
+            int hopW = 63; uint64_t hopM = 0;                  // walk_fast's position and marks, for the batch that has to finish the hops
+#define HOP(m, w) do { BITSET64(m, w); w = RL(succ, w); } while (0)
+#define HOP_MORE(m, w) ((((m) >> (w)) & 1ull) == 0)
             // the parser over this batch's hits: scalar hop over the recorded matches only, everything else derived per lane
             auto walk = [&]() {
                 const uint64_t hits = hit;
@@ -444,6 +467,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 LANES({
                     const uint64_t ah = (eLane[I_] < 64) ? (hits >> eLane[I_]) : 0;
                     nextHit[I_] = ah ? eLane[I_] + ctz64(ah) : 64;
+                    succ[I_] = ah ? nextHit[I_] : LANE;
                 })
                 mm = 0; eL = 0; finished = 0;
                 int w = 64;
@@ -455,17 +479,25 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                     // (w == 64) the remaining hops of a group only touch bit 0 of the mask, which no hop but the very
                     // first can legitimately set.  Matches longer than the speculative window are not known to the hop: it
                     // walks through them as if they ended there, and the first one it touched is put right afterwards.
+                    // (PLZ4_HOP: w < 64 here, at every turn; a walk that has ended stays on its last match, see `succ`)
                     for (;;) {
-                        const uint64_t low = (mm & 1) | (w == 0 ? 1ull : 0ull);
-                        do {
-                            for (int u = 0; u < 4; ++u) {
-                                const int n1 = RL(nextHit, w & 63);
-                                mm |= 1ull << (w & 63);
-                                w = (w < 64) ? n1 : 64;
-                            }
-                            STAT(P_HOPS, 4);
-                        } while (w < 64);
-                        mm = (mm & ~1ull) | low;
+                        if (PLZ4_HOP) {
+                            do {
+                                for (int u = 0; u < 4; ++u) HOP(mm, w);
+                                STAT(P_HOPS, 4);
+                            } while (HOP_MORE(mm, w));
+                        } else {
+                            const uint64_t low = (mm & 1) | (w == 0 ? 1ull : 0ull);
+                            do {
+                                for (int u = 0; u < 4; ++u) {
+                                    const int n1 = RL(nextHit, w & 63);
+                                    mm |= 1ull << (w & 63);
+                                    w = (w < 64) ? n1 : 64;
+                                }
+                                STAT(P_HOPS, 4);
+                            } while (w < 64);
+                            mm = (mm & ~1ull) | low;
+                        }
                         const uint64_t sp = mm & specialLeft;
                         if (!sp) break;
                         EMU_CNT(4, 1);
@@ -500,39 +532,61 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 E = probes | insBit0 | (hasPm & BALLOT(stA[I_] == LANE + 2));      // + the ip-2 inserts (lz4.c:1236-1242)
                 STAT(P_CYC_E, STAT_NOW() - tw2);
             };
-            // the same walk without a branch in it, for the first round: eight hops unconditionally (a hop past the end only
-            // touches bit 0 again), more only if the batch has more matches; matches longer than the speculative window are
-            // taken at that length and reported by the caller's check (a uniform branch costs this machine 80-90 cycles, taken
-            // or not: scripts/micro/branch.hip -- the steady state is written to have a handful of them per batch, not forty)
-            auto walk_fast = [&](const uint64_t hits) {
+            // the same walk without a branch in it, for the first round: kHopN hops unconditionally (a hop past the end only
+            // marks the last match again); matches longer than the speculative window are taken at that length and reported by the
+            // caller's check (a uniform branch costs this machine 80-90 cycles, taken or not: scripts/micro/branch.hip -- the
+            // steady state is written to have a handful of them per batch, not forty).  Returns whether the walk is NOT finished:
+            // with `finish` it goes on to its end and that is never so; without, the caller asks -- together with its take36
+            // question -- and finishes the hops itself (fewer than 1 % of the batches on text have more than eight matches).
+            auto walk_fast = [&](const uint64_t hits, const bool finish) -> bool {
                 LV(int, nextHit);
                 LANES({
                     const uint64_t ah = (eLane[I_] < 64) ? (hits >> eLane[I_]) : 0;
                     nextHit[I_] = ah ? eLane[I_] + ctz64(ah) : 64;
+                    if (PLZ4_HOP) succ[I_] = ah ? nextHit[I_] : LANE;
                 })
                 const uint64_t hm = hits & fromCur0;
                 int w = hm ? ctz64(hm) : 64;
                 w = (w > lim0) ? 64 : w;                               // (the stride limit concerns the first match only)
-                const uint64_t low = (w == 0 ? 1ull : 0ull);
                 const bool any = w < 64;
                 uint64_t m = 0;
+                bool more = false;
                 const unsigned long long tw1 = STAT_NOW(); (void)tw1;
-                for (int u = 0; u < 6; ++u) {                           // (4 .. 8 unconditional hops measure the same on text)
-                    const int n1 = RL(nextHit, w & 63);
-                    m |= 1ull << (w & 63);
-                    w = (w < 64) ? n1 : 64;
-                }
-                while (w < 64) {
-                    for (int u = 0; u < 4; ++u) {
+                if (PLZ4_HOP) {
+                    // The one guard, in front of the chain: a batch without an executed match (w == 64) would start at lane 0 and
+                    // walk matches the parser never executed.  It walks from lane 63 instead, which never has a successor (a
+                    // match there ends at lane 67 or beyond), and its marks are dropped.
+                    EMU_CNT(22, !any && RL(succ, 0) != 0);
+                    w = any ? w : 63;
+                    for (int u = 0; u < kHopN; ++u) HOP(m, w);
+                    STAT(P_HOPS, kHopN);
+                    if (finish) while (HOP_MORE(m, w)) { for (int u = 0; u < 4; ++u) HOP(m, w); STAT(P_HOPS, 4); }
+                    hopW = w; hopM = m;
+                    more = HOP_MORE(m, w);
+                    mm = any ? m : 0;
+                    eL = RL(eLane, w);                                  // (a finished walk stands on its last match)
+                    eL = any ? eL : 0;
+                } else {
+                    const uint64_t low = (w == 0 ? 1ull : 0ull);
+                    for (int u = 0; u < kHopN; ++u) {                   // (4 .. 8 unconditional hops of this form measure the same on text)
                         const int n1 = RL(nextHit, w & 63);
                         m |= 1ull << (w & 63);
                         w = (w < 64) ? n1 : 64;
                     }
+                    STAT(P_HOPS, kHopN);
+                    hopW = w;
+                    while (w < 64) {
+                        for (int u = 0; u < 4; ++u) {
+                            const int n1 = RL(nextHit, w & 63);
+                            m |= 1ull << (w & 63);
+                            w = (w < 64) ? n1 : 64;
+                        }
+                        STAT(P_HOPS, 4);
+                    }
+                    mm = any ? ((m & ~1ull) | low) : 0;
+                    eL = RL(eLane, (63 - __builtin_clzll(mm | 1ull)) & 63);
+                    eL = mm ? eL : 0;
                 }
-                STAT(P_HOPS, 8);
-                mm = any ? ((m & ~1ull) | low) : 0;
-                eL = RL(eLane, (63 - __builtin_clzll(mm | 1ull)) & 63);
-                eL = mm ? eL : 0;
                 finished = 0;
                 const unsigned long long tw2 = STAT_NOW(); (void)tw2;
                 STAT(P_CYC_HOP, tw2 - tw1);
@@ -546,6 +600,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 probes = BALLOT2(LANE >= stA[I_], LANE < SendL) & fromCur0;
                 E = probes | insBit0 | (hasPm & BALLOT(stA[I_] == LANE + 2));
                 STAT(P_CYC_E, STAT_NOW() - tw2);
+                return more;
             };
             // ---- 4. first round, straight: walk -> commit -> verify, every step unconditional, ONE question at the end
             uint64_t committed = 0;
@@ -553,9 +608,26 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             int keepIns = 0, keepWidth = 64;    // what step 6 leaves of hasIns / width: a batch that gives up leaves them as they were
             {
                 const uint64_t hits1 = hit;
-                walk_fast(hits1);
-                EMU_CNT(11, (mm & full20) != 0);
-                if (mm & x36) { take36(); walk_fast(hits1); }
+                // ONE question for the two rare ways of the first walk -- more matches than the unconditional hops, a lane of x36
+                // executed -- behind which the hops are finished, the 36-byte window is taken if such a lane was executed, and
+                // the batch is walked again (the straight path has eL, the scan and E already; this one computes them anew)
+                const bool more = walk_fast(hits1, !PLZ4_HOP);
+                // (the counters of the first walk, once all of its matches are in mm; `unfinished`: after the unconditional hops)
+                auto count_first_walk = [&](const bool unfinished) {
+                    (void)unfinished;
+                    EMU_CNT(11, (mm & full20) != 0); EMU_CNT(20, unfinished); EMU_CNT(21, unfinished && (mm & x36) != 0);
+                    EMU_CNT(23, (mm & 1) && __builtin_popcountll(mm) >= 3); EMU_HOPS(mm);
+                };
+                if (!PLZ4_HOP) {
+                    count_first_walk(hopW < 64);
+                    if (mm & x36) { take36(); walk_fast(hits1, true); }
+                } else if (more | ((mm & x36) != 0)) {
+                    while (HOP_MORE(hopM, hopW)) { for (int u = 0; u < 4; ++u) HOP(hopM, hopW); STAT(P_HOPS, 4); }
+                    mm = hopM;                                          // (a batch without an executed match is not here)
+                    count_first_walk(more);
+                    if (mm & x36) take36();
+                    walk_fast(hits1, true);
+                } else count_first_walk(false);
                 const uint64_t special1 = hits1 & PAST_WINDOW();
                 const unsigned long long tc0 = STAT_NOW(); (void)tc0;
                 const uint64_t EL = E;
@@ -661,6 +733,8 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 }
             }
 #undef PAST_WINDOW
+#undef HOP
+#undef HOP_MORE
             // ---- 4b. batch k+1's slots once more: the table holds this batch's inserts now, and a slot that changed since the peek
             // was taken by an executed lane of THIS batch -- whose window is here.  Its bytes replace the requested ones, so the
             // next batch starts from candidates that are exact against everything before it; what its commit can still return

@@ -39,6 +39,7 @@
 /* x[l] <- max of x over the lanes strictly below l (0 for lane 0); x >= 0 */
 #define SCAN_MAX_EXCL(x) do { int m_ = 0; for (int s_ = 0; s_ < 64; ++s_) { const int v_ = (x)[s_]; (x)[s_] = m_; if (v_ > m_) m_ = v_; } } while (0)
 #define UNI_OPAQUE(x)  do {} while (0)
+#define BITSET64(m, b) do { (m) |= 1ull << ((b) & 63); } while (0)   /* set bit (b & 63) of a wave-uniform 64-bit mask */
 #define WAVE_FENCE()   do {} while (0)
 #define LDS_FENCE()    do {} while (0)
 #define LDS_ORDER()    do {} while (0)
@@ -67,6 +68,9 @@ static inline int plz4_emu_step()  { return plz4_emu_descending ? -1 : 1; }
 // a wave-uniform 32-bit value the optimiser must take as it is (it stays in its scalar register; no instruction): keeps what is
 // computed from it from being recognised as a compare -- see step 6 of the grid batch, lz4_seq_device.inl
 #define UNI_OPAQUE(x)  __asm__("" : "+s"(x))
+// set bit (b & 63) of a wave-uniform 64-bit mask: one scalar instruction (the hardware takes the low six bits of b), where the
+// compiler forms s_lshl_b64 + s_or_b64 from the shift and the or
+#define BITSET64(m, b) __asm__("s_bitset1_b64 %0, %1" : "+s"(m) : "s"(b))
 // a wave-uniform 64-bit mask as a per-lane condition: the scalar register pair itself is the select / exec mask, where
 // ((mask >> LANE) & 1) costs two v_and and a 64-bit v_cmp
 #define LANE_IN(mask)  (__builtin_amdgcn_inverse_ballot_w64((uint64_t)(mask)))
