@@ -42,6 +42,14 @@
  * the call's total output (up to 32).  A chain is answered up to its first block that is not plainly good; the one-wavefront chain
  * walk goes on from there inside the call, from the window the good blocks leave.  PLZ4HIP_DX_LINKED=0 keeps such calls on the
  * one-wavefront kernels (a switch for tests and A/B runs; PLZ4HIP_DX_MAX_BLOCKS=0 does so too).
+ * A LINKED call of more blocks than that (decode_records_ex with linked = 1, decode_records_chains, dev_decode_records_ex) is cut
+ * into groups of PLZ4HIP_DXL_GROUP_BLOCKS consecutive blocks (default 128; read per call), each group the same path across the whole
+ * chip, one behind the other on the call's stream: a block needs only the 64 KiB in front of it, so the window, its length and one
+ * word per chain (the chain has had a bad block: its later blocks are PLZ4HIP_BLK_CORRUPT with result 0) go from group to group in
+ * device memory and the host never waits in between.  The workspace is that of one group.  Results, status, bytes and windows are
+ * those of the one-wavefront walk.  Groups are taken when blocks x 0.33 ms <= longest chain x 59 ms -- few long chains; many short
+ * chains keep one wavefront per chain -- and PLZ4HIP_DXL_GROUP_BLOCKS=0 keeps every call beyond PLZ4HIP_DX_MAX_BLOCKS on the walk
+ * (set to a number, it also cuts calls that would fit one pass: a switch for tests and measurements).
  * An ENCODE call of few blocks at level 1 (compress_batch, encode_records, dev_compress with maxLen > 0, dev_encode_records,
  * dev_encode_body; up to PLZ4HIP_FX_MAX_BLOCKS = 128 blocks, 0 turns it off) whose largest block is 65 547 bytes .. 4 MiB (liblz4's
  * byU32 tables) has its parse cut across the whole chip: pieces of PLZ4HIP_FX_PIECE_KIB (64) parsed by a wave each, in rounds
@@ -95,8 +103,9 @@ const char* plz4hip_last_error(const plz4hip_ctx* ctx);       /* text of the las
 int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release staging buffers and HC workspaces (waits for work in flight) */
 /* Waits for the ctx's work, then writes up to n counters to out: [0] blocks encoded by the few-block level-1 path, [1] its rounds
  * in the last such call, [2] pieces it parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history
- * outside the block (dictionary, linked) answered by it, [5] its jump rounds in the last such call.  Returns how many counters
- * there are (6), or PLZ4HIP_E_*. */
+ * outside the block (dictionary, linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of
+ * a call cut into groups), [6] the groups of the last call that was cut into groups.  Returns how many counters there are (7), or
+ * PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */
@@ -246,6 +255,20 @@ int plz4hip_dev_scatter_records(plz4hip_ctx* ctx, const void* src, const int64_t
 int plz4hip_dev_decode_records(plz4hip_ctx* ctx, const void* body, const int64_t* recOff, int nBlocks,
                                int bsz, int blockChecksum, void* dst, int64_t dstStride, int dstCap,
                                int32_t* result, int32_t* status, void* stream);
+
+/* plz4hip_dev_decode_records_ex: plz4hip_dev_decode_records for records with history outside the block -- what
+ * plz4hip_decode_records_ex / plz4hip_decode_records_chains do over host buffers, for a consumer whose frame body is on the device.
+ * linked = 0 with `dict`: independent blocks, every one against the dictionary, at any block count.  linked = 1 (dict NULL): the
+ * call's blocks are the chains of chainFirst (a HOST array of nChains + 1 entries, chainFirst[0] == 0, non-decreasing, the last one
+ * == nBlocks; it is not read after the call returns; NULL: one chain); windows / windowLen are DEVICE memory, in/out: 128 KiB per
+ * chain -- the live window (compress.DictT) in the first 64 KiB, the rest scratch -- and int32[nChains]; as with
+ * plz4hip_decode_records_ex the caller seeds a chain's window with the dictionary's last 64 KiB (or length 0).  Few blocks go
+ * across the chip at once, a long chain in groups (see DECODE above).  Enqueued on `stream`, no synchronisation; it does not feed
+ * plz4hip_ctx_set_content_hash (plz4hip_dev_xxh32_stream_update takes the plaintext where it lies). */
+int plz4hip_dev_decode_records_ex(plz4hip_ctx* ctx, const void* body, const int64_t* recOff, int nBlocks,
+                                  int bsz, int blockChecksum, int linked, const plz4hip_dict* dict,
+                                  int nChains, const int32_t* chainFirst, void* windows, int32_t* windowLen,
+                                  void* dst, int64_t dstStride, int dstCap, int32_t* result, int32_t* status, void* stream);
 
 /* plz4hip_dev_duplex_records: plz4hip_dev_encode_records (level 1) of one batch AND plz4hip_dev_decode_records of another --
  * a writer's next batch and a reader's -- enqueued as one call, with results identical to the two calls made one after the

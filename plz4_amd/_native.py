@@ -18,7 +18,7 @@ SYMBOLS = [
     "plz4hip_last_error", "plz4hip_compress_bound", "plz4hip_compress_batch", "plz4hip_decompress_batch",
     "plz4hip_xxh32_batch", "plz4hip_encode_records", "plz4hip_decode_records", "plz4hip_dev_stage_stride",
     "plz4hip_dev_encode_records", "plz4hip_dev_compact_records", "plz4hip_dev_scatter_records",
-    "plz4hip_dev_decode_records", "plz4hip_dev_duplex_records", "plz4hip_dev_encode_body", "plz4hip_dev_duplex_body", "plz4hip_dev_compress", "plz4hip_dev_decompress", "plz4hip_ctx_trim",
+    "plz4hip_dev_decode_records", "plz4hip_dev_decode_records_ex", "plz4hip_dev_duplex_records", "plz4hip_dev_encode_body", "plz4hip_dev_duplex_body", "plz4hip_dev_compress", "plz4hip_dev_decompress", "plz4hip_ctx_trim",
     "plz4hip_ctx_counters",
     "plz4hip_dev_resident_waves", "plz4hip_dict_create", "plz4hip_dict_destroy", "plz4hip_compress_batch_dict", "plz4hip_decode_records_chains",
     "plz4hip_decompress_batch_dict", "plz4hip_encode_records_ex", "plz4hip_decode_records_ex",
@@ -89,6 +89,9 @@ def load():
     L.plz4hip_dev_scatter_records.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp]
     L.plz4hip_dev_decode_records.restype = C.c_int
     L.plz4hip_dev_decode_records.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp]
+    L.plz4hip_dev_decode_records_ex.restype = C.c_int
+    L.plz4hip_dev_decode_records_ex.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, i32p, vp, vp,
+                                                vp, C.c_int64, C.c_int, vp, vp, vp]
     L.plz4hip_dev_duplex_records.restype = C.c_int
     L.plz4hip_dev_duplex_records.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp, vp,
                                              vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp]
@@ -340,6 +343,19 @@ class Engine:
         self._chk(self.L.plz4hip_dev_decode_records(self.h, body_ptr, recoff_ptr, nblocks, bsz, int(block_checksum), dst_ptr,
                                                     dst_stride, dst_cap, result_ptr, status_ptr, stream))
 
+    def dev_decode_records_ex(self, body_ptr, recoff_ptr, nblocks, bsz, block_checksum, dst_ptr, dst_stride, dst_cap,
+                              result_ptr, status_ptr, linked=False, d=None, chain_first=None, n_chains=1,
+                              windows_ptr=None, window_len_ptr=None, stream=0):
+        """dev_decode_records for linked chains (chain_first: host ints, n_chains + 1 of them, or None for one chain; windows_ptr:
+        n_chains x 128 KiB on the device, the live window in the first 64 KiB; window_len_ptr: int32 per chain on the device) or
+        for independent blocks under the dictionary d"""
+        cf = None
+        if chain_first is not None:
+            cf = _i32(chain_first); n_chains = cf.size - 1
+        self._chk(self.L.plz4hip_dev_decode_records_ex(self.h, body_ptr, recoff_ptr, nblocks, bsz, int(block_checksum), int(linked), d,
+                                                       n_chains, _i32p(cf) if cf is not None else None, windows_ptr, window_len_ptr,
+                                                       dst_ptr, dst_stride, dst_cap, result_ptr, status_ptr, stream))
+
     def dev_duplex_records(self, src_ptr, src_bytes, bsz, block_checksum, stage_ptr, reclen_ptr,
                            body_ptr, recoff_ptr, ndec, dec_bsz, dec_block_checksum, dst_ptr, dst_stride, dst_cap,
                            result_ptr, status_ptr, stream=0):
@@ -394,12 +410,13 @@ class Engine:
     def trim(self):
         self._chk(self.L.plz4hip_ctx_trim(self.h))
 
-    COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last")
+    COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last", "dxl_groups_last")
 
     def counters(self) -> dict:
         """plz4hip_ctx_counters (waits for the ctx's work): blocks encoded by the few-block level-1 path, its rounds in the last
         such call, pieces it parsed more than once, blocks answered by the few-block decoder, blocks with history outside the block
-        (dictionary, linked) answered by it, its jump rounds in the last such call."""
+        (dictionary, linked) answered by it, its jump rounds in the last such call, the groups of the last linked call that was
+        cut into groups."""
         out = (C.c_int64 * len(self.COUNTERS))()
         rc = int(self.L.plz4hip_ctx_counters(self.h, out, len(self.COUNTERS)))
         if rc < 0:

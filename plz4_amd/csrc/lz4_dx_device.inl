@@ -507,4 +507,118 @@ DEV int dxl_window(const DxlCall& c, const int first, const int cut, const uint8
     return keep + s;
 }
 
+// ---- A linked call cut into groups of consecutive blocks (launch_decode): the plan, made on the host, and a group's view of the
+// call's chains.  A group is the blocks [g0, g1) and the chains [ch0, ch1): ch0 the chain block g0 belongs to, ch1 - 1 the last chain
+// that starts in front of g1; a chain in between may have no block at all.  first: the call's chainFirst (nCh + 1 entries; null: one
+// chain); *cursor: where the search for ch0 goes on from group to group (0 at the first).
+struct DxlGroup { int g0, g1, ch0, ch1; };
+static inline void dxl_group(const int32_t* first, const int nCh, const int nb, const int G, const int g0, int* cursor, DxlGroup* g)
+{
+    g->g0 = g0; g->g1 = g0 + G < nb ? g0 + G : nb;
+    if (!first) { g->ch0 = 0; g->ch1 = 1; return; }
+    int ch = *cursor;
+    while (ch + 1 < nCh && first[ch + 1] <= g0) ++ch;
+    int hi = ch;
+    while (hi + 1 < nCh && first[hi + 1] < g->g1) ++hi;
+    *cursor = ch; g->ch0 = ch; g->ch1 = hi + 1;
+}
+// where chain ch (counted from the group's first chain; chainFirst points at that chain's entry) starts inside a group of nb blocks
+// that begins at the call's block blk0: the call's own number, clamped to the group
+DEV int dxl_chain_lo(const int32_t* chainFirst, const int blk0, const int nb, const int ch)
+{
+    const int v = chainFirst[ch] - blk0;
+    return v < 0 ? 0 : (v > nb ? nb : v);
+}
+
+// ---- The finish stage of a linked chain, and the one-wave walk behind it.  One body for k_dxl_finish, k_decode_rec_linked and the
+// lane-emulated build.  rec(i, hist, histLen, &r, &st, &stored) decodes record i of the call the serial way against the
+// window (hist, histLen): its result, its status (0: ok), and whether it was a stored block (copied out; it does not enter the
+// window).  DxlFin: what the stage reads beside the DxlCall (checksum verdicts, the blocks' rows of moved flags, the rounds
+// launched) and where the blocks' answers go.
+enum : int { kDxlStCorrupt = 3 };                                   // PLZ4HIP_BLK_CORRUPT: what a block behind a bad block of its chain gets
+
+struct DxlFin {
+    const int32_t*  hashBad;                                        // per block: its checksum does not match (null: none is checked)
+    const uint32_t* moved;  int rounds;                             // per block kDxlMaxRounds + 1 flags; the jump rounds launched
+    int32_t*        result; int32_t* status;
+};
+DEV bool dxl_block_good(const DxlCall& c, const DxlFin& f, const int b)
+{
+    return !(c.len && c.len[b] < 0) && !c.info[b].bad && !(f.hashBad && f.hashBad[b])
+        && dxl_converged(f.moved + (int64_t)b * (kDxlMaxRounds + 1), f.rounds);
+}
+DEV void dxl_answer(const DxlFin& f, const int i, const int r, const int st)
+{
+    LANES({ if (LANE == 0) { f.result[i] = r; f.status[i] = st; } })
+}
+
+// Linked blocks: a serial chain, one wave.  The window follows compress.DictT.Update (compress/dict.go:28-41) and is
+// NOT updated by stored blocks (sync/reader.go:75-78, async/reader.go:149-163) -- the reference's behaviour, kept.
+// The records [first, last) of a chain from the window (winA, winLen) on; dead: an earlier record of the chain has failed (every
+// record then gets result 0 / kDxlStCorrupt, its output and the window stay as they are).  The live window ends up in win0;
+// *winLenOut / *deadOut: the state the chain's next records start from.
+template <class Rec>
+DEV void dxl_walk(const DxlCall& c, const DxlFin& f, Rec& rec, const int first, const int last, uint8_t* const win0,
+                  uint8_t* winA, uint8_t* winB, int winLen, bool dead, int* winLenOut, int* deadOut)
+{
+    for (int i = first; i < last; ++i) {
+        int r = 0, st = kDxlStCorrupt; bool stored = false;
+        if (!dead) rec(i, winA, winLen, &r, &st, &stored);
+        dxl_answer(f, i, r, st);
+        if (st != 0) { dead = true; continue; }                             // first error ends the stream
+        if (stored) continue;
+        const uint8_t* out = c.dst + (int64_t)i * c.dstStride;
+        WAVE_FENCE();
+        if (r >= kDxlHist) { wave_copy(winB, out + (r - kDxlHist), kDxlHist); winLen = kDxlHist; }
+        else {
+            int keep = winLen;
+            if (winLen + r > kDxlHist) keep = kDxlHist - r;
+            wave_copy(winB, winA + (winLen - keep), keep);
+            wave_copy(winB + keep, out, r);
+            winLen = keep + r;
+        }
+        WAVE_FENCE();
+        uint8_t* t = winA; winA = winB; winB = t;
+    }
+    // leave the live window in the first half for whoever goes on
+    if (winA != win0) { WAVE_FENCE(); wave_copy(win0, winA, winLen); }
+    *winLenOut = winLen; *deadOut = dead ? 1 : 0;
+}
+
+// The blocks [first, last) of one chain behind the gather, one wave: the chain's good blocks are answered (a stored block among them
+// is copied out here and does not enter the window), the window they leave is laid down, and from the first block that is not
+// plainly good the one-wave walk goes on (its own verdict for that block, CORRUPT for what follows, the window as it was in front
+// of it).  win0: the chain's 2 x 64 KiB, the live window in the first half.  *winLenIO, *deadIO: the chain's state in front of
+// `first` and behind `last` -- what a call cut into groups of blocks carries from group to group.  *takenOut: compressed blocks the
+// few-block path answered, *roundsOut: the jump rounds the slowest of them took.
+template <class Rec>
+DEV void dxl_finish(const DxlCall& c, const DxlFin& f, Rec& rec, const int first, const int last, uint8_t* const win0,
+                    int* winLenIO, int* deadIO, int* takenOut, int* roundsOut)
+{
+    uint8_t* winA = win0; uint8_t* winB = win0 + kDxlHist;
+    int winLen = *winLenIO;
+    bool dead = *deadIO != 0;
+    int i = first, taken = 0, rounds = 0;
+    if (!dead) for (; i < last; ++i) {
+        if (!(c.len && UNI(c.len[i]) < 0)) {
+            if (!UNI((int)dxl_block_good(c, f, i))) break;
+            dxl_answer(f, i, c.info[i].outLen, 0);
+            ++taken;
+            const int rr = UNI(dxl_rounds_of(f.moved + (int64_t)i * (kDxlMaxRounds + 1), f.rounds));
+            if (rr > rounds) rounds = rr;
+        } else {
+            int r = 0, st = 0; bool stored = false;
+            rec(i, nullptr, 0, &r, &st, &stored);                           // a stored block, or a record that fails the frame reader's checks
+            dxl_answer(f, i, r, st);
+            if (st != 0) { dead = true; ++i; break; }
+        }
+    }
+    WAVE_FENCE();
+    const int t = dxl_window(c, first, i, winA, winLen, winB);
+    WAVE_FENCE();
+    if (t >= 0) { uint8_t* x = winA; winA = winB; winB = x; winLen = t; }
+    *takenOut = taken; *roundsOut = rounds;
+    dxl_walk(c, f, rec, i, last, win0, winA, winB, winLen, dead, winLenIO, deadIO);
+}
+
 }  // namespace plz4

@@ -97,6 +97,11 @@ struct CodecArgs {
     // ... with history outside the block (dxl_*, lz4_dx_device.inl): per block the first block and the number of its chain, its row
     // of moved flags (kDxlMaxRounds + 1), whether the path has answered it; the jump rounds launched
     int32_t*        dxlFirst;   int32_t* dxlChain;   uint32_t* dxlMoved;   int32_t* dxlGood;   int dxlRounds;
+    // a linked call cut into groups of consecutive blocks (launch_decode): every pointer above is the group's own view (block 0 = the
+    // group's first block, chain 0 = the first chain with a block in it); chainFirst stays the call's, so the group's first block
+    // dxlBlk0 comes off it.  dxlDead: per chain, an earlier group has met a bad block of it (null: the call is one group).
+    // dxlGroup / dxlGroups: this group's number / how many the call has (0: not a grouped call).
+    int32_t*        dxlDead;    int dxlBlk0;    int dxlGroup;   int dxlGroups;
 };
 
 __device__ __forceinline__ int next_block(uint32_t* q)
@@ -438,34 +443,31 @@ __global__ __launch_bounds__(64) void k_decode_rec_dict(CodecArgs a)
     }
 }
 
-// Linked blocks: a serial chain, one wave.  The window follows compress.DictT.Update (compress/dict.go:28-41) and is
-// NOT updated by stored blocks (sync/reader.go:75-78, async/reader.go:149-163) -- the reference's behaviour, kept.
+// Linked blocks: a serial chain, one wave (dxl_walk, lz4_dx_device.inl).  RecWave: its record decoder.
 // The records [first, last) of chain ch from the window (winA, winLen) on; dead: an earlier record of the chain has failed.
+static_assert((int)kDxlStCorrupt == (int)PLZ4HIP_BLK_CORRUPT && (int)PLZ4HIP_BLK_OK == 0, "dxl_walk's status codes");
+struct RecWave {
+    const CodecArgs& a; uint8_t* dl;
+    __device__ __forceinline__ void operator()(int i, const uint8_t* hist, int histLen, int* r, int* st, bool* stored) const
+    {
+        decode_one_record(a, i, hist, histLen, r, st, stored, dl);
+    }
+};
+// the chain's first and last record as the kernels' view of the call has them (a group's view: the call's chainFirst, clamped)
+__device__ __forceinline__ int chain_lo(const CodecArgs& a, int ch)
+{
+    if (!a.chainFirst) return ch == 0 ? 0 : a.nBlocks;
+    return dxl_chain_lo(a.chainFirst, a.dxlBlk0, a.nBlocks, ch);
+}
 __device__ __forceinline__ void linked_walk(const CodecArgs& a, const int ch, const int first, const int last, uint8_t* const win0,
                                             uint8_t* winA, uint8_t* winB, int winLen, bool dead, uint8_t* dl)
 {
-    for (int i = first; i < last; ++i) {
-        int r = 0, st = PLZ4HIP_BLK_CORRUPT; bool stored = false;
-        if (!dead) decode_one_record(a, i, winA, winLen, &r, &st, &stored, dl);
-        if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
-        if (st != PLZ4HIP_BLK_OK) { dead = true; continue; }             // first error ends the stream
-        if (stored) continue;
-        const uint8_t* out = a.dst + (int64_t)i * a.dstStride;
-        WAVE_FENCE();
-        if (r >= 65536) { wave_copy(winB, out + (r - 65536), 65536); winLen = 65536; }
-        else {
-            int keep = winLen;
-            if (winLen + r > 65536) keep = 65536 - r;
-            wave_copy(winB, winA + (winLen - keep), keep);
-            wave_copy(winB + keep, out, r);
-            winLen = keep + r;
-        }
-        WAVE_FENCE();
-        uint8_t* t = winA; winA = winB; winB = t;
-    }
-    // leave the live window in the first half for the next call
-    if (winA != win0) { WAVE_FENCE(); wave_copy(win0, winA, winLen); }
-    if ((threadIdx.x & 63u) == 0) a.windowLen[ch] = winLen;
+    DxlCall c{}; c.dst = a.dst; c.dstStride = a.dstStride;
+    DxlFin f{}; f.result = a.result; f.status = a.status;
+    RecWave rec{a, dl};
+    int wl = winLen, dd = 0;
+    dxl_walk(c, f, rec, first, last, win0, winA, winB, winLen, dead, &wl, &dd);
+    if ((threadIdx.x & 63u) == 0) a.windowLen[ch] = wl;
 }
 __global__ __launch_bounds__(64) void k_decode_rec_linked(CodecArgs a)
 {
@@ -1126,6 +1128,11 @@ __device__ __forceinline__ DxlCall dxl_call(const CodecArgs& a)
     c.dst = a.dst; c.dstStride = a.dstStride;
     return c;
 }
+__device__ __forceinline__ DxlFin dxl_fin(const CodecArgs& a)
+{
+    DxlFin f; f.hashBad = a.dxHashBad; f.moved = a.dxlMoved; f.rounds = a.dxlRounds; f.result = a.result; f.status = a.status;
+    return f;
+}
 __device__ __forceinline__ bool dxl_good(const CodecArgs& a, int b)
 {
     return dx_len(a, b) >= 0 && !a.dxInfo[b].bad && !(a.dxHashBad && a.dxHashBad[b])
@@ -1134,12 +1141,13 @@ __device__ __forceinline__ bool dxl_good(const CodecArgs& a, int b)
 __global__ __launch_bounds__(256) void k_dxl_link(CodecArgs a, unsigned long long* cnt)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) cnt[5] = 0;                                                 // (plz4hip_ctx_counters: jump rounds of the last such call)
+    // (plz4hip_ctx_counters: jump rounds of the last such call -- the maximum over its groups -- and how many groups it had)
+    if (i == 0 && a.dxlGroup == 0) { cnt[5] = 0; if (a.dxlGroups) cnt[6] = (unsigned long long)a.dxlGroups; }
     if (i >= a.nBlocks) return;
     int first = i, ch = 0;
     if (a.linked) {
         first = 0;
-        if (a.chainFirst) { while (ch + 1 < a.nChains && a.chainFirst[ch + 1] <= i) ++ch; first = a.chainFirst[ch]; }
+        if (a.chainFirst) { while (ch + 1 < a.nChains && chain_lo(a, ch + 1) <= i) ++ch; first = chain_lo(a, ch); }
     }
     a.dxlFirst[i] = first; a.dxlChain[i] = ch; a.dxlGood[i] = 0;
     for (int r = 0; r <= kDxlMaxRounds; ++r) a.dxlMoved[(int64_t)i * (kDxlMaxRounds + 1) + r] = 0;
@@ -1205,34 +1213,18 @@ __global__ __launch_bounds__(64) void k_dxl_finish(CodecArgs a, unsigned long lo
 {
     __shared__ __attribute__((aligned(16))) uint8_t dl[kDecLdsBytes];
     const int ch = blockIdx.x;
-    const int first = a.chainFirst ? a.chainFirst[ch] : 0;
-    const int last  = a.chainFirst ? a.chainFirst[ch + 1] : a.nBlocks;
-    const DxlCall c = dxl_call(a);
-    uint8_t* const win0 = a.window + (size_t)ch * 131072;
-    uint8_t* winA = win0; uint8_t* winB = win0 + 65536;
+    const int first = chain_lo(a, ch), last = a.chainFirst ? chain_lo(a, ch + 1) : a.nBlocks;
+    if (a.dxlDead && first >= last) return;                                 // (a group of a cut call: the chain has no block in it)
+    RecWave rec{a, dl};
     int winLen = plz4_readfirstlane(a.windowLen[ch]);
-    bool dead = false;
-    int i = first, taken = 0, rounds = 0;
-    for (; i < last; ++i) {
-        if (plz4_readfirstlane(a.dxLen[i]) >= 0) {
-            if (!plz4_readfirstlane((int)dxl_good(a, i))) break;
-            if ((threadIdx.x & 63u) == 0) { a.result[i] = a.dxInfo[i].outLen; a.status[i] = PLZ4HIP_BLK_OK; }
-            ++taken;
-            const int rr = plz4_readfirstlane(dxl_rounds_of(a.dxlMoved + (int64_t)i * (kDxlMaxRounds + 1), a.dxlRounds));
-            if (rr > rounds) rounds = rr;
-        } else {
-            int r, st; bool stored;
-            decode_one_record(a, i, nullptr, 0, &r, &st, &stored, dl);      // a stored block, or a record that fails the frame reader's checks
-            if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
-            if (st != PLZ4HIP_BLK_OK) { dead = true; ++i; break; }
-        }
+    int dead = a.dxlDead ? plz4_readfirstlane(a.dxlDead[ch]) : 0;
+    int taken = 0, rounds = 0;
+    dxl_finish(dxl_call(a), dxl_fin(a), rec, first, last, a.window + (size_t)ch * 131072, &winLen, &dead, &taken, &rounds);
+    if ((threadIdx.x & 63u) == 0) {
+        a.windowLen[ch] = winLen;
+        if (a.dxlDead) a.dxlDead[ch] = dead;
+        if (taken) { atomicAdd(&cnt[4], (unsigned long long)taken); atomicMax(&cnt[5], (unsigned long long)rounds); }
     }
-    WAVE_FENCE();
-    const int t = dxl_window(c, first, i, winA, winLen, winB);
-    WAVE_FENCE();
-    if (t >= 0) { uint8_t* x = winA; winA = winB; winB = x; winLen = t; }
-    if (taken && (threadIdx.x & 63u) == 0) { atomicAdd(&cnt[4], (unsigned long long)taken); atomicMax(&cnt[5], (unsigned long long)rounds); }
-    linked_walk(a, ch, i, last, win0, winA, winB, winLen, dead, dl);
 }
 
 __global__ __launch_bounds__(64) void k_decode_raw(CodecArgs a)
@@ -1485,15 +1477,19 @@ struct plz4hip_ctx {
     DeviceBuffer fx;  StreamOrder fxOrder;
     // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
     // parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history outside the block (dictionary,
-    // linked) answered by it, [5] its jump rounds in the last such call
+    // linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of a call cut into groups),
+    // [6] the groups of the last call that was cut into groups
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
+    // plz4hip_dev_decode_records_ex: the chainFirst of the last call (int32 each), which that job's kernels read
+    DeviceBuffer chainCopy;  StreamOrder chainOrder;
     struct Owned { DeviceBuffer* buf; StreamOrder* order; bool trimmed; };     // trimmed: plz4hip_ctx_trim gives it back
-    std::array<Owned, 8> owned()
+    std::array<Owned, 9> owned()
     {
         return {{{&hc, &hcOrder, true}, {&h12, &hcOrder, true}, {&hcPfx, &hcOrder, false}, {&l1[0], &l1Order[0], true},
-                 {&l1[1], &l1Order[1], true}, {&dx, &dxOrder, true}, {&fx, &fxOrder, true}, {&lenCopy, &lenOrder, false}}};
+                 {&l1[1], &l1Order[1], true}, {&dx, &dxOrder, true}, {&fx, &fxOrder, true}, {&lenCopy, &lenOrder, false},
+                 {&chainCopy, &chainOrder, false}}};
     }
 };
 
@@ -2243,82 +2239,144 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
 // a.chainFirst.  Few blocks of that kind take the same path with one pointer space for the whole call (dxl_*, lz4_dx_device.inl;
 // PLZ4HIP_DX_LINKED=0: they do not); a chain is answered up to its first block that is not plainly good, and the one-wave walk goes
 // on from there inside k_dxl_finish.
+// A linked call that does not fit one pass of that path is cut into groups of consecutive blocks, each group the same stage train on
+// s: a block needs only the 64 KiB in front of it, which the finish stage of the group before has laid down in a.window; that, the
+// window's length and one word per chain -- the chain has had a bad block -- are what goes from group to group, in device memory.
+// hostFirst: the call's chainFirst on the host (nChains + 1 entries; null: one chain).
+// Groups are taken iff blocks x kDxlMsPerBlock <= longest chain x kWalkMsPerBlock: many short chains are better served by one wave
+// per chain.  PLZ4HIP_DXL_GROUP_BLOCKS: blocks per group (0: no groups, one wave per chain beyond PLZ4HIP_DX_MAX_BLOCKS; set, it
+// also cuts calls that would fit one pass).  The constants and the default: profiles/dxl_group_rate.json.
 enum { kHistNone = 0, kHistDict = 1, kHistLinked = 2 };
-int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t maxIn, int64_t maxOut, bool records, int hist = kHistNone)
+constexpr int    kDxlGroupBlocks = 128;                                     // the fastest of 16 / 32 / 64 / 128 on a 256-block chain
+constexpr double kDxlMsPerBlock = 0.33, kWalkMsPerBlock = 59.0;             // t_dx, t_wave: 4 MiB blocks; both scale with the block alike
+constexpr int    kDxlGroupChains = 1024;                                    // chains a group's pointer space has room for
+int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t maxIn, int64_t maxOut, bool records, int hist = kHistNone,
+                  const int32_t* hostFirst = nullptr)
 {
     hipError_t e;
     MarkOnExit job;
     int dxMax = 128;
     if (const char* v = getenv("PLZ4HIP_DX_MAX_BLOCKS")) dxMax = atoi(v);
-    bool dx = nb <= dxMax && maxIn >= 16384 && maxIn <= (int64_t)(6 << 20) && maxOut >= 1;
+    const bool dxShape = maxIn >= 16384 && maxIn <= (int64_t)(6 << 20) && maxOut >= 1;
+    bool dx = nb <= dxMax && dxShape;
+    bool dxl = true;
     if (hist) {
         const char* v = getenv("PLZ4HIP_DX_LINKED");
-        if (v && atoi(v) == 0) dx = false;
-        if (hist == kHistLinked && (!records || !a.window || a.nChains < 1)) dx = false;
+        if (v && atoi(v) == 0) dxl = false;
+        if (hist == kHistLinked && (!records || !a.window || a.nChains < 1)) dxl = false;
+        if (!dxl) dx = false;
     }
     const int nCh = hist == kHistLinked ? a.nChains : 0;
+    const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
+    const size_t tStride = round_up((size_t)maxIn + 64, 64), pStride = round_up((size_t)outB + 64, 1024);
+    // groups: [g0, g1) blocks and [ch0, ch1) chains each
+    std::vector<DxlGroup> groups;
+    int gMax = nb;
+    if (hist == kHistLinked && dxl && dxShape && dxMax > 0 && (hostFirst || nCh == 1)) {
+        int G = kDxlGroupBlocks; bool forced = false;
+        if (const char* v = getenv("PLZ4HIP_DXL_GROUP_BLOCKS")) { G = atoi(v); forced = true; }
+        // the pointer space: blocks x stride + chains x 64 Ki stays below 2^31 (bit 31 tags a distance)
+        const int64_t room = ((int64_t)1 << 31) - (int64_t)kDxlGroupChains * kDxlHist - 1;
+        if (G > 0 && (int64_t)G * (int64_t)pStride > room) G = (int)(room / (int64_t)pStride);
+        if (G > 0 && (forced ? nb > G : !dx)) {
+            int longest = 0;
+            for (int ch = 0; ch < nCh; ++ch) {
+                const int n = hostFirst ? hostFirst[ch + 1] - hostFirst[ch] : nb;
+                if (n > longest) longest = n;
+            }
+            bool take = (double)nb * kDxlMsPerBlock <= (double)longest * kWalkMsPerBlock;
+            int cursor = 0;
+            for (int g0 = 0; take && g0 < nb; g0 += G) {
+                DxlGroup g;
+                dxl_group(hostFirst, nCh, nb, G, g0, &cursor, &g);
+                if (g.ch1 - g.ch0 > kDxlGroupChains) take = false;             // (chains without a block in between, by the thousand)
+                groups.push_back(g);
+            }
+            if (!take || groups.size() < 2) groups.clear();
+            else { dx = true; gMax = G; }
+        }
+    }
     a.dxInfo = nullptr; a.dxSrcOff = nullptr; a.dxLen = nullptr; a.dxHashBad = nullptr; a.dxlGood = nullptr;
+    a.dxlDead = nullptr; a.dxlBlk0 = 0; a.dxlGroup = 0; a.dxlGroups = 0;
     if (dx) {
-        const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
-        const size_t tStride = round_up((size_t)maxIn + 64, 64), pStride = round_up((size_t)outB + 64, 1024);
         const int maxSeg = (int)((maxIn + kDxSeg - 1) / kDxSeg);
-        const size_t offPtr = round_up((size_t)nb * tStride * 8, 256), offUnits = offPtr + round_up((size_t)nb * pStride * 4, 256);
-        const size_t offInfo = offUnits + round_up((size_t)nb * maxSeg * sizeof(DxUnit), 256), offRec = offInfo + round_up((size_t)nb * sizeof(DxInfo), 256);
-        const size_t offLink = offRec + round_up((size_t)nb * 16, 256);
-        const size_t need = offLink + (hist ? round_up((size_t)nb * (12 + 4 * (kDxlMaxRounds + 1)), 256) : 0);
+        const size_t wb = (size_t)gMax;                                         // blocks the workspace is laid out for: the call, or one group
+        const size_t offPtr = round_up(wb * tStride * 8, 256), offUnits = offPtr + round_up(wb * pStride * 4, 256);
+        const size_t offInfo = offUnits + round_up(wb * maxSeg * sizeof(DxUnit), 256), offRec = offInfo + round_up(wb * sizeof(DxInfo), 256);
+        const size_t offLink = offRec + round_up(wb * 16, 256);
+        const size_t offDead = offLink + (hist ? round_up(wb * (12 + 4 * (kDxlMaxRounds + 1)), 256) : 0);
+        const size_t need = offDead + (groups.empty() ? 0 : round_up((size_t)nCh * 4, 256));
         HIPCHK(c, c->dxOrder.wait(s));
         bool refused = false;  HIPCHK(c, c->dx.reserve(need, c->dxOrder, &refused));
         if (refused) dx = false;                                                // no room: one wave per block
         if (dx) {
             job.arm(c->dxOrder, s);
-            a.dxT = (uint64_t*)c->dx.d; a.dxTStride = (int64_t)tStride;
-            a.dxPtr = (uint32_t*)(c->dx.d + offPtr); a.dxPtrStride = (int64_t)pStride;
-            a.dxUnits = (DxUnit*)(c->dx.d + offUnits); a.dxMaxSeg = maxSeg;
-            a.dxInfo = (DxInfo*)(c->dx.d + offInfo);
-            const bool hashed = records && a.blockChecksum;
-            if (records) {
-                int64_t* so = (int64_t*)(c->dx.d + offRec); int32_t* ln = (int32_t*)(so + nb);
-                hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, so, ln);
-                a.dxSrcOff = so; a.dxLen = ln;
-                if (hashed) {
-                    a.dxHashBad = ln + nb;
-                    // (the ctx's own stream, idle otherwise: one stream more would push the staging slots' streams onto shared
-                    // hardware queues -- the runtime has four -- and cost the large host calls their overlap: 412 -> 610 ms per
-                    // 2304 blocks, measured)
-                    c->dxHashStream = c->stream;
-                    if (!c->evDxFork) HIPCHK(c, hipEventCreateWithFlags(&c->evDxFork, hipEventDisableTiming));
-                    if (!c->evDxHash) HIPCHK(c, hipEventCreateWithFlags(&c->evDxHash, hipEventDisableTiming));
-                    HIPCHK(c, hipEventRecord(c->evDxFork, s));
-                    HIPCHK(c, hipStreamWaitEvent(c->dxHashStream, c->evDxFork, 0));
-                    hipLaunchKernelGGL(k_dx_rec_hash, dim3(nb), dim3(64), 0, c->dxHashStream, a);
-                    HIPCHK(c, hipEventRecord(c->evDxHash, c->dxHashStream));
+            const CodecArgs call = a;
+            int32_t* const dead = groups.empty() ? nullptr : (int32_t*)(c->dx.d + offDead);
+            if (dead) HIPCHK(c, hipMemsetAsync(dead, 0, (size_t)nCh * 4, s));
+            const int nGroups = groups.empty() ? 1 : (int)groups.size();
+            for (int gi = 0; gi < nGroups; ++gi) {
+                if (!groups.empty()) {
+                    // the group's view of the call
+                    const DxlGroup& g = groups[gi];
+                    a = call; nb = g.g1 - g.g0;
+                    if (a.recOff) a.recOff += g.g0; else { a.src += (int64_t)g.g0 * a.srcStride; a.srcLen += g.g0; }
+                    a.dst += (int64_t)g.g0 * a.dstStride; a.result += g.g0; a.status += g.g0; a.nBlocks = nb;
+                    a.window += (size_t)g.ch0 * 131072; a.windowLen += g.ch0; a.nChains = g.ch1 - g.ch0;
+                    if (a.chainFirst) a.chainFirst += g.ch0;
+                    a.dxlDead = dead + g.ch0; a.dxlBlk0 = g.g0; a.dxlGroup = gi; a.dxlGroups = nGroups;
                 }
+                const int nChG = hist == kHistLinked ? a.nChains : 0;
+                a.dxT = (uint64_t*)c->dx.d; a.dxTStride = (int64_t)tStride;
+                a.dxPtr = (uint32_t*)(c->dx.d + offPtr); a.dxPtrStride = (int64_t)pStride;
+                a.dxUnits = (DxUnit*)(c->dx.d + offUnits); a.dxMaxSeg = maxSeg;
+                a.dxInfo = (DxInfo*)(c->dx.d + offInfo);
+                const bool hashed = records && a.blockChecksum;
+                if (records) {
+                    int64_t* so = (int64_t*)(c->dx.d + offRec); int32_t* ln = (int32_t*)(so + nb);
+                    hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, so, ln);
+                    a.dxSrcOff = so; a.dxLen = ln;
+                    if (hashed) {
+                        a.dxHashBad = ln + nb;
+                        // (the ctx's own stream, idle otherwise: one stream more would push the staging slots' streams onto shared
+                        // hardware queues -- the runtime has four -- and cost the large host calls their overlap: 412 -> 610 ms per
+                        // 2304 blocks, measured)
+                        c->dxHashStream = c->stream;
+                        if (!c->evDxFork) HIPCHK(c, hipEventCreateWithFlags(&c->evDxFork, hipEventDisableTiming));
+                        if (!c->evDxHash) HIPCHK(c, hipEventCreateWithFlags(&c->evDxHash, hipEventDisableTiming));
+                        HIPCHK(c, hipEventRecord(c->evDxFork, s));
+                        HIPCHK(c, hipStreamWaitEvent(c->dxHashStream, c->evDxFork, 0));
+                        hipLaunchKernelGGL(k_dx_rec_hash, dim3(nb), dim3(64), 0, c->dxHashStream, a);
+                        HIPCHK(c, hipEventRecord(c->evDxHash, c->dxHashStream));
+                    }
+                }
+                const int chunks = (int)((outB + 1023) / 1024);
+                hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_dx_stitch, dim3(nb), dim3(64), 0, s, a);
+                if (!hist) {
+                    hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                    for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+                    if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
+                    hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+                } else {
+                    a.dxlFirst = (int32_t*)(c->dx.d + offLink); a.dxlChain = a.dxlFirst + nb; a.dxlGood = a.dxlChain + nb;
+                    a.dxlMoved = (uint32_t*)(a.dxlGood + nb);
+                    // the copy chain of a call (of a group) can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
+                    int rounds = 1;
+                    while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
+                    a.dxlRounds = rounds;
+                    hipLaunchKernelGGL(k_dxl_link, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
+                    hipLaunchKernelGGL(k_dxl_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                    hipLaunchKernelGGL(k_dxl_resolve, dim3((int)(pStride / 1024), nb), dim3(256), 0, s, a);
+                    for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxl_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+                    hipLaunchKernelGGL(k_dxl_gather, dim3(chunks, nb), dim3(256), 0, s, a);
+                    if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
+                    if (hist == kHistLinked) hipLaunchKernelGGL(k_dxl_finish, dim3(nChG), dim3(64), 0, s, a, c->d_counters);
+                    else                     hipLaunchKernelGGL(k_dxl_verdict, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
+                }
+                HIPCHK(c, hipGetLastError());
             }
-            const int chunks = (int)((outB + 1023) / 1024);
-            hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
-            hipLaunchKernelGGL(k_dx_stitch, dim3(nb), dim3(64), 0, s, a);
-            if (!hist) {
-                hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-                if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-                hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
-            } else {
-                a.dxlFirst = (int32_t*)(c->dx.d + offLink); a.dxlChain = a.dxlFirst + nb; a.dxlGood = a.dxlChain + nb;
-                a.dxlMoved = (uint32_t*)(a.dxlGood + nb);
-                // the copy chain of a call can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
-                int rounds = 1;
-                while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
-                a.dxlRounds = rounds;
-                hipLaunchKernelGGL(k_dxl_link, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
-                hipLaunchKernelGGL(k_dxl_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                hipLaunchKernelGGL(k_dxl_resolve, dim3((int)(pStride / 1024), nb), dim3(256), 0, s, a);
-                for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxl_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-                hipLaunchKernelGGL(k_dxl_gather, dim3(chunks, nb), dim3(256), 0, s, a);
-                if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-                if (hist == kHistLinked) hipLaunchKernelGGL(k_dxl_finish, dim3(nCh), dim3(64), 0, s, a, c->d_counters);
-                else                     hipLaunchKernelGGL(k_dxl_verdict, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
-            }
-            HIPCHK(c, hipGetLastError());
+            if (!groups.empty()) { a = call; nb = call.nBlocks; }
         }
     }
     a.queue = next_queue(c, s, &e); HIPCHK(c, e);
@@ -2448,11 +2506,11 @@ int plz4hip_ctx_counters(plz4hip_ctx* c, int64_t* out, int n)
     if (!c || n < 0 || (n > 0 && !out)) return PLZ4HIP_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
-    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
+    unsigned long long v[7] = {0, 0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipDeviceSynchronize());                                      // (the ctx's work runs on the callers' streams)
     HIPCHK(c, copy_sync(c, v, c->d_counters, sizeof v, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n && i < 6; ++i) out[i] = (int64_t)v[i];
-    return 6;
+    for (int i = 0; i < n && i < 7; ++i) out[i] = (int64_t)v[i];
+    return 7;
 }
 
 const char* plz4hip_last_error(const plz4hip_ctx* c)
@@ -2599,6 +2657,65 @@ int plz4hip_dev_decode_records(plz4hip_ctx* c, const void* body, const int64_t* 
     a.result = result; a.status = status; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
     a.dictLen = -1; a.prevTailLen = -1;
     return launch_decode(c, s, a, nBlocks, bsz, dstCap, true);
+}
+
+// Linked and dictionary records from device memory.  The call's chainFirst goes to the device by value, 64 entries per launch: the
+// caller's array is not read after the call returns, and nothing here waits for the device.
+namespace {
+struct I32x64 { int32_t v[64]; };
+__global__ void k_put_i32(int32_t* dst, I32x64 vals, int n) { if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x]; }
+}
+int plz4hip_dev_decode_records_ex(plz4hip_ctx* c, const void* body, const int64_t* recOff, int nBlocks,
+                                  int bsz, int blockChecksum, int linked, const plz4hip_dict* dict,
+                                  int nChains, const int32_t* chainFirst, void* windows, int32_t* windowLen,
+                                  void* dst, int64_t dstStride, int dstCap, int32_t* result, int32_t* status, void* stream)
+{
+    if (!c || nBlocks < 0 || !body || !recOff || !dst || !result || !status || bsz <= 0) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_decode_records_ex: bad argument");
+    if (linked && dict) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_decode_records_ex: a linked call takes its dictionary through the window");
+    if (!linked && !dict) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_decode_records_ex: neither linked nor a dictionary (plz4hip_dev_decode_records)");
+    if (linked) {
+        if (!windows || !windowLen || nChains < 1) return fail(c, PLZ4HIP_E_ARG, "linked decode needs the window state of its chains");
+        if (!chainFirst && nChains != 1) return fail(c, PLZ4HIP_E_ARG, "several chains need chainFirst");
+        if (chainFirst) {
+            if (chainFirst[0] != 0) return fail(c, PLZ4HIP_E_ARG, "chainFirst[0] must be 0");
+            for (int k = 0; k < nChains; ++k) if (chainFirst[k + 1] < chainFirst[k]) return fail(c, PLZ4HIP_E_ARG, "chainFirst must not decrease");
+            if (chainFirst[nChains] != nBlocks) return fail(c, PLZ4HIP_E_ARG, "chainFirst must end at nBlocks");
+        }
+    }
+    if (nBlocks == 0) return PLZ4HIP_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    CodecArgs a{};
+    a.src = (const uint8_t*)body; a.recOff = recOff; a.bsz = bsz;
+    a.dst = (uint8_t*)dst; a.dstStride = dstStride; a.dstCapAll = dstCap;
+    a.result = result; a.status = status; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
+    a.dictLen = -1; a.prevTailLen = -1;
+    if (!linked) {
+        a.dict = dict->d_bytes; a.dictLen = dict->len; a.dictTable = dict->d_table;
+        return launch_decode(c, s, a, nBlocks, bsz, dstCap, true, kHistDict);
+    }
+    a.linked = 1; a.window = (uint8_t*)windows; a.windowLen = windowLen; a.nChains = nChains;
+    MarkOnExit job;
+    if (chainFirst) {
+        const size_t bytes = (size_t)(nChains + 1) * 4;
+        if (bytes > c->chainCopy.bytes) {
+            bool refused = false;  HIPCHK(c, c->chainCopy.reserve(bytes + 1024, c->chainOrder, &refused));
+            if (refused) return fail(c, PLZ4HIP_E_NOMEM, "plz4hip_dev_decode_records_ex: chain copy");
+        }
+        HIPCHK(c, c->chainOrder.wait(s));                                   // the last job's kernels still read the copy
+        job.arm(c->chainOrder, s);
+        for (int k = 0; k <= nChains; k += 64) {
+            I32x64 v; const int n = nChains + 1 - k < 64 ? nChains + 1 - k : 64;
+            memcpy(v.v, chainFirst + k, (size_t)n * 4);
+            hipLaunchKernelGGL(k_put_i32, dim3(1), dim3(64), 0, s, (int32_t*)c->chainCopy.d + k, v, n);
+        }
+        HIPCHK(c, hipGetLastError());
+        a.chainFirst = (const int32_t*)c->chainCopy.d;
+    }
+    if (int rc = launch_decode(c, s, a, nBlocks, bsz, dstCap, true, kHistLinked, chainFirst)) return rc;
+    HIPCHK(c, job.leave());
+    return PLZ4HIP_OK;
 }
 
 int plz4hip_dev_duplex_records(plz4hip_ctx* c, const void* src, int64_t srcBytes, int bsz, int blockChecksum, void* stage, int32_t* recLen,
@@ -2845,7 +2962,8 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
                 else if (dictMode) ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
                 else { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1)) return rc; } break;
         case 3: a.dstCap = nullptr;
-                if (int rc = launch_decode(c, s, a, nb, bsz, bsz + 8, true, !dictMode ? kHistNone : (dj->linked ? kHistLinked : kHistDict))) return rc;
+                if (int rc = launch_decode(c, s, a, nb, bsz, bsz + 8, true, !dictMode ? kHistNone : (dj->linked ? kHistLinked : kHistDict),
+                                           dictMode ? dj->chainFirst : nullptr)) return rc;    // (a linked decode is one chunk: the call's chains)
                 break;
         case 4: hipLaunchKernelGGL(k_xxh32, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s,
                                    (const uint8_t*)a.src, a.srcStride, a.srcLen, (uint32_t*)a.result, nb, q); break;
