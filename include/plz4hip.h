@@ -55,6 +55,11 @@
  * byU32 tables) has its parse cut across the whole chip: pieces of PLZ4HIP_FX_PIECE_KIB (64) parsed by a wave each, in rounds
  * until every piece starts from the exact state its predecessor ends in; a guessed start begins PLZ4HIP_FX_WARMUP_KIB (64) early.
  * Output, results and error codes are exactly those of the one-wave parse; smaller blocks of such a call are parsed whole.
+ * A level-1 call with a dictionary and/or linked blocks through host buffers (compress_batch_dict, encode_records_ex, and the
+ * multi-GPU / host-layer routes that end there) takes the same path under the same limits, per staging chunk: the segment -- the
+ * previous block's tail or the dictionary -- is laid in front of every block and the table liblz4 starts the block with is the
+ * first piece's entry state; every block of such a call may be shorter than a piece, only blocks <= 4 KiB under a dictionary
+ * context keep their two-table encoder.  PLZ4HIP_FX_LINKED=0 (read per call) keeps such calls on one wavefront per block.
  * Duplex calls and level 2 keep their kernels.  It keeps about 3 bytes per input byte of the call's blocks (the pieces' tables
  * and records) until plz4hip_ctx_trim.  plz4hip_ctx_counters reports what these few-block paths did.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
@@ -104,8 +109,8 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
 /* Waits for the ctx's work, then writes up to n counters to out: [0] blocks encoded by the few-block level-1 path, [1] its rounds
  * in the last such call, [2] pieces it parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history
  * outside the block (dictionary, linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of
- * a call cut into groups), [6] the groups of the last call that was cut into groups.  Returns how many counters there are (7), or
- * PLZ4HIP_E_*. */
+ * a call cut into groups), [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block encoded by
+ * the few-block level-1 path (a subset of [0]).  Returns how many counters there are (8), or PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */
@@ -169,6 +174,9 @@ int plz4hip_decode_records(plz4hip_ctx* ctx, int nBlocks,
  *                   fails the write instead (compress/linked.go:47-49 returns the error without zerr.ErrCompress, so
  *                   blk.CompressToBlk takes no fallback) -- a drop-in caller checks the stored bit of rec[i] for
  *                   linked && level > 1 and reports the error (the host layer and the Go shim do).
+ *                   At level 1 a call of few blocks (see ENCODE above) has every block's parse cut across the chip: for
+ *                   the encoder linked blocks are no chain -- block i needs the PLAINTEXT tail of block i-1, which the
+ *                   call's input holds -- so every block and every piece starts at once.  Same records, byte for byte.
  *    decode_records_ex: independent blocks + dict: every block against `dict` (compress/decompress.go:42-58);
  *                   linked: the batch is one chain; `window` (64 KiB, caller-owned) / `*windowLen` carry
  *                   compress.DictT (compress/dict.go:5-56) across calls: initialise with the dictionary's last 64 KiB

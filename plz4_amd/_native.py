@@ -410,13 +410,14 @@ class Engine:
     def trim(self):
         self._chk(self.L.plz4hip_ctx_trim(self.h))
 
-    COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last", "dxl_groups_last")
+    COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last", "dxl_groups_last",
+                "fxl_blocks")
 
     def counters(self) -> dict:
         """plz4hip_ctx_counters (waits for the ctx's work): blocks encoded by the few-block level-1 path, its rounds in the last
         such call, pieces it parsed more than once, blocks answered by the few-block decoder, blocks with history outside the block
         (dictionary, linked) answered by it, its jump rounds in the last such call, the groups of the last linked call that was
-        cut into groups."""
+        cut into groups, blocks with history outside the block encoded by the few-block level-1 path (a subset of the first)."""
         out = (C.c_int64 * len(self.COUNTERS))()
         rc = int(self.L.plz4hip_ctx_counters(self.h, out, len(self.COUNTERS)))
         if rc < 0:

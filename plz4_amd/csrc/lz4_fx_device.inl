@@ -21,6 +21,17 @@
 // block's end out as the block's records; the emit kernels of lz4_seq_device.inl run unchanged behind it.
 // A piece whose search runs past its end simply goes on to the next post-match state (or the block's end): the worst case is one
 // exact walk of the rest of the block, as with one wave per block.
+//
+// Blocks with history outside the block (kExt: linked blocks, blocks under a dictionary context -- LZ4_compress_fast_continue as
+// wave_encode_block_ext plays it) take the same rounds.  For the encoder they are no chain: block i needs the last <= 64 KiB of
+// block i-1's PLAINTEXT, which the call's input holds, so every block and every piece starts at once.  fxl_prep (one wave per
+// block) copies the segment right in front of the block and writes the table liblz4 starts the block with -- LZ4_loadDict over
+// the tail, the dictionary context's table, or an empty one -- as piece 0's entry table (tabIn of piece 0, which the independent
+// flavour never uses): piece 0 is exact in round 1 as before, pieces k > 0 guess as before, and the round rule, the parity of
+// the exit states, the gather and the P-rounds argument are the independent flavour's.  Anchors are liblz4 indices (the parser's
+// positions, lz4_seq_device.inl), records and lastAnchor block coordinates.  A block shorter than one piece is a block of one
+// piece (these blocks take byU32 tables at any length); blocks <= 4 KiB under a dictionary context (two tables, kDictCtxLookup)
+// are not this path's: they get an empty parse here and wave_encode_block_dict behind the emit stage.
 #pragma once
 #include "lz4_seq_device.inl"
 
@@ -37,10 +48,12 @@ struct FxPiece {
 };
 
 DEV int fx_pieces(int n, int pb) { return (n + pb - 1) / pb; }
+template <bool kExt> DEV int fx_pieces_of(int n, int pb) { return kExt ? max_(fx_pieces(n, pb), 1) : fx_pieces(n, pb); }
 // records a piece has room for (+ the dump entry): those of its own bytes, one that crosses its end, a batch of warm-up records
 static inline int fx_rec_stride_host(int pb) { return ((pb / 4 + 80) + 7) & ~7; }
 
-// two states at one anchor: same live entries (dead ones never matter again)
+// two states at one anchor: same live entries (dead ones never matter again).  kExt: the flavour's shift, anchor = its index.
+template <bool kExt = false>
 DEV bool fx_same_state(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B, int anchor)
 {
     LV(int, bad);
@@ -48,7 +61,7 @@ DEV bool fx_same_state(const uint32_t* __restrict__ A, const uint32_t* __restric
         int b = 0;
         for (int i = LANE; i < kFxTab; i += 64) {
             const uint32_t x = A[i], y = B[i];
-            const bool lx = (x >> 10) + kMaxDist >= (uint32_t)anchor, ly = (y >> 10) + kMaxDist >= (uint32_t)anchor;
+            const bool lx = (x >> (kExt ? 9 : 10)) + kMaxDist >= (uint32_t)anchor, ly = (y >> (kExt ? 9 : 10)) + kMaxDist >= (uint32_t)anchor;
             b |= (int)((lx != ly) | (lx & (x != y)));
         }
         bad[I_] = b;
@@ -58,30 +71,35 @@ DEV bool fx_same_state(const uint32_t* __restrict__ A, const uint32_t* __restric
 
 // One wave: piece k of a block of n bytes in round `round` (1, 2, ...).  meta / tabIn: P entries of the block; tabOut: 2 x P
 // tables (parity major); rec: P x recStride records.  Returns 1 when it parsed.
+// kExt: src = the block (its segment in front of it, piece 0's entry table in tabIn: fxl_prep), bs = liblz4's index of its first byte.
+template <bool kExt = false>
 DEV int fx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int pb, int warm, FxPiece* meta, uint32_t* tabIn, uint32_t* tabOut,
-                 uint64_t* rec, int recStride, uint32_t* lds)
+                 uint64_t* rec, int recStride, uint32_t* lds, const int bs = 0)
 {
-    const int P = fx_pieces(n, pb);
+    const int P = fx_pieces_of<kExt>(n, pb);
     if (k >= P) return 0;
-    const int par = round & 1, start = k * pb;
+    const int par = round & 1, start = bs + k * pb, nEnd = bs + n;
     FxPiece* const me = meta + k;
     uint32_t* const myIn = tabIn + (int64_t)k * kFxTab;
     FxRun run;
     run.entryAnchor = -1; run.entryTab = nullptr; run.cp = -1; run.cpTab = myIn; run.cpAnchor = -1;
-    run.end = min_(n, start + pb); run.outTab = tabOut + ((int64_t)par * P + k) * kFxTab; run.outAnchor = -1;
-    run.seqCap = recStride - 1; run.fin = 0;
+    run.end = min_(nEnd, start + pb); run.outTab = tabOut + ((int64_t)par * P + k) * kFxTab; run.outAnchor = -1;
+    run.seqCap = recStride - 1; run.fin = 0; run.bs = bs;
     if (round == 1) {
         if (k > 0) {
             run.cp = start;
             const int p0 = start - warm;
-            if (p0 >= 64) run.entryAnchor = p0;                      // (else from the block's start: exact)
+            if (p0 >= bs + 64) run.entryAnchor = p0;                 // (else from the block's start: exact)
         }
+        // the block's start: the table liblz4 starts it with.  (The pointer is said to be wave-uniform: as one of three values that
+        // meet at the parser's "is there a table" question, the compiler otherwise keeps it in vector registers and fails on that question.)
+        if (kExt && run.entryAnchor < 0) run.entryTab = (const uint32_t*)(uintptr_t)UNI((uint64_t)(uintptr_t)tabIn);
     } else {
         bool go = false;
         if (k > 0 && meta[k - 1].ran[par ^ 1] && !meta[k - 1].outFin[par ^ 1]) {
             const int a = meta[k - 1].outAnchor[par ^ 1];
             const uint32_t* T = tabOut + ((int64_t)(par ^ 1) * P + k - 1) * kFxTab;
-            if (a != me->inAnchor || !fx_same_state(T, myIn, a)) {
+            if (a != me->inAnchor || !fx_same_state<kExt>(T, myIn, a)) {
                 go = true;
                 run.entryAnchor = a; run.entryTab = T;
                 LANES({ for (int i = LANE; i < kFxTab; i += 64) myIn[i] = T[i]; })
@@ -93,8 +111,9 @@ DEV int fx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int p
         }
     }
     int lastAnchor = 0;
-    const int ns = wave_parse_l1_tt<false, 2, true>(src, n, lds, rec + (int64_t)k * recStride, &lastAnchor, nullptr, &run);
-    const int inA = round == 1 ? (k > 0 ? run.cpAnchor : 0) : run.entryAnchor;
+    const int ns = wave_parse_l1_tt<false, 2, true, kExt>(src - bs, nEnd, lds, rec + (int64_t)k * recStride, &lastAnchor, nullptr, &run);
+    if (kExt && n < kMinLength) run.fin = 1;                         // (no parse at all: the block is its last literals)
+    const int inA = round == 1 ? (k > 0 ? run.cpAnchor : bs) : run.entryAnchor;
     const int runs = round == 1 ? 1 : me->runs + 1;
     WAVE_FENCE();
     LANES({
@@ -110,10 +129,11 @@ DEV int fx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int p
 // One wave: piece k's records into the block's record array, if the block's chain reaches it; the piece that reached the block's
 // end writes the block's SeqInfo.  Returns 0: not in the chain, 1: in it, 2: the last of it.  (Counts beyond the room of a piece
 // or of the block cannot come out of an exact parse; they would fail the block -- kSeqEngineFailed -- rather than be written.)
+template <bool kExt = false>
 DEV int fx_gather(int n, int k, int pb, const FxPiece* __restrict__ meta, const uint64_t* __restrict__ rec, int recStride,
                   uint64_t* __restrict__ seq, int seqCap, SeqInfo* info)
 {
-    const int P = fx_pieces(n, pb);
+    const int P = fx_pieces_of<kExt>(n, pb);
     if (k >= P) return 0;
     int off = 0;
     bool over = false;
@@ -134,6 +154,47 @@ DEV int fx_gather(int n, int k, int pb, const FxPiece* __restrict__ meta, const 
         LANES({ if (LANE == 0) { SeqInfo inf; inf.nseq = room ? off + ns : kSeqEngineFailed; inf.lastAnchor = la; inf.total = 0; inf.stored = 0; *info = inf; } })
     }
     return fin ? 2 : 1;
+}
+
+// ---- blocks with history outside the block
+struct FxlBlk { int32_t pfx, bs; };       // the segment's bytes (-1: not this path's block) and liblz4's index of the block's first byte
+
+// One wave: how block `blk` of n bytes starts under `mode` (kDict*, lz4_device.inl; seg / segLen: the previous block's tail or the
+// dictionary, dictTable: the dictionary context's LZ4_loadDictSlow table).  The segment is copied right in front of the block --
+// the caller has left 64 KiB there -- and the table liblz4 starts the block with goes to tabG (16 KiB of global memory) as
+// index << 9 | tag: LZ4_loadDict over the segment, every 3rd position, the largest index per slot (lz4.c:1621-1628); the context's
+// table, copied and tagged (lz4.c:1762-1768); else every slot "index 0".  Indices: the segment ends at 64 KiB, so delta =
+// 64 KiB - segLen and every entry is 0 or a position of the segment.  lds: 16 KiB owned by the wave.
+DEV FxlBlk fxl_prep(uint8_t* blk, int n, int mode, const uint8_t* __restrict__ seg, int segLen, const uint32_t* __restrict__ dictTable,
+                    uint32_t* __restrict__ tabG, uint32_t* lds)
+{
+    FxlBlk b; b.pfx = 0; b.bs = 65536;
+    if (mode == kDictCtxLookup) { b.pfx = -1; return b; }
+    uint32_t e0 = 0;
+    if (mode == kDictFreshPrefix) { b.bs = 0; if (n >= 4) e0 = seq_tag(UNI(ld32u(blk))) & 0x1FFu; }       // "index 0" is the block's first byte
+    const bool withSeg = mode == kDictLoad || mode == kDictCtxCopy;
+    if (withSeg) b.pfx = segLen;
+    const uint32_t delta = 65536u - (uint32_t)b.pfx;
+    if (mode == kDictCtxCopy) {
+        LANES({ for (int i = LANE; i < kFxTab; i += 64) {
+            const uint32_t idx = dictTable[i];
+            lds[i] = idx >= delta ? ((idx << 9) | (seq_tag(ld32u(seg + (idx - delta))) & 0x1FFu)) : 0u;
+        } })
+    } else {
+        LANES({ for (int i = LANE; i < kFxTab; i += 64) lds[i] = e0; })
+        if (mode == kDictLoad) {
+            LDS_FENCE();
+            const int cnt = (segLen - 8) / 3 + 1;
+            LANES({ for (int k = LANE; k < cnt; k += 64) {
+                const uint64_t s8 = ld64u(seg + 3 * k);
+                lds_max(&lds[seq_hash<false>(s8)], (((uint32_t)(3 * k) + delta) << 9) | (seq_tag((uint32_t)s8) & 0x1FFu));
+            } })
+        }
+    }
+    LDS_FENCE();
+    LANES({ for (int i = LANE; i < kFxTab; i += 64) tabG[i] = lds[i]; })
+    if (withSeg) wave_copy(blk - segLen, seg, segLen);
+    return b;
 }
 
 }  // namespace plz4

@@ -228,6 +228,7 @@ struct FxRun {
     uint32_t*       outTab; int outAnchor;     // out: the state at end
     int             seqCap;           // records the piece has room for; seq[seqCap] is the dump entry
     int             fin;              // out
+    int             bs;               // kExt: liblz4's index of the block's first byte (0 or 64 KiB)
 };
 DEV void fx_save_table(const void* tab, uint32_t* g)
 {
@@ -240,14 +241,25 @@ DEV void fx_save_table(const void* tab, uint32_t* g)
 // cache for them (its tag pipeline is what ten parser waves per CU saturate: TA busy 65 %, TCP stalled on pending misses 46 % of
 // the time, profiles/r04b_ta_counters.txt).  The lanes fetch consecutive dwords a batch earlier (one coalesced load), park them in
 // LDS and every lane reads its 20 bytes back from its byte offset.
-template <bool U16, int kLdsWin = 0, bool kPiece = false>
+//
+// kExt (with kPiece, byU32 only): the block has history outside of it -- the previous block's tail or a dictionary, `pfx` bytes lying
+// immediately before the block in memory (lz4_fx_device.inl lays them out and primes piece 0's entry table) -- and the parse follows
+// the rules of wave_encode_block_tt<false, true> (ExtEnc, lz4_device.inl).  Positions here ARE liblz4's indices (position in segment +
+// block, + delta): `src` points at index 0, i.e. delta bytes in front of the segment's first byte -- nothing below the segment is ever
+// read: an entry is either a position the prep or the parser inserted, or "index 0", which is dead by distance from index 64 KiB on
+// (the dictSmall test of lz4.c:1085-1087 has nothing left to reject) -- the block is [run->bs, n), and entries are index << 9 | tag
+// (indices reach 4 MiB + 64 KiB).  Records keep the block's coordinates (index - bs): a match into the segment has offset > position.
+// The catch-up (lowLimit, lz4.c:1065-1079) belongs to the emit stage.
+template <bool U16, int kLdsWin = 0, bool kPiece = false, bool kExt = false>
 DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab, uint64_t* __restrict__ seq, int* lastAnchor, uint8_t* scr = nullptr,
                          FxRun* run = nullptr)
 {
-    const int      sh      = U16 ? 0 : 10;
+    static_assert(!kExt || (kPiece && !U16), "the external-segment flavour is a piece parse with byU32 tables");
+    const int      sh      = U16 ? 0 : (kExt ? 9 : 10);
+    const int      bs      = kExt ? run->bs : 0;          // the block's first position
     const uint32_t tagMask = (1u << sh) - 1u;
     {   // fresh table per block (LZ4_initStream, lz4.c:1384): every slot = "position 0"
-        const uint32_t e0 = (sh && n >= 4) ? (seq_tag(UNI(ld32u(src))) & tagMask) : 0u;
+        const uint32_t e0 = (sh && n >= 4 && !kExt) ? (seq_tag(UNI(ld32u(src))) & tagMask) : 0u;
         uint32_t* t = (uint32_t*)tab;
         if (kPiece && run->entryTab) { const uint32_t* g = run->entryTab; LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) t[i] = g[i]; }) }
         else LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) t[i] = e0; })
@@ -258,16 +270,16 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
     const int matchLimit = n - kLastLiterals;     // lz4.c:964
     const int seqDump    = kPiece ? run->seqCap : seq_capacity(n);    // one entry behind the records: where lanes without a record store
     const SrcBuf sbuf    = src_buf(src, n);       // the block as a buffer (the candidate loads)
-    int nseq = 0, anchor = 0;
+    int nseq = 0, anchor = bs;
     STAT_DECL;
     const unsigned long long tBlock0 = STAT_NOW(); (void)tBlock0;
 
-    if (n >= kMinLength) {
+    if (n - bs >= kMinLength) {
         // (the two flags are 0 / 1 integers, and step 6 of the grid batch combines them with integer selects: as `bool`s that live
         // across batches the compiler keeps them as lane masks and moves them through a vector register at every batch's end)
-        int  insPos  = 0; int hasIns = 1;          // pending table insert ("First Byte" lz4.c:1005-1010; ip-2 lz4.c:1236-1242)
-        int  rePos   = 0; int hasRe  = 0;          // pending immediate re-test at ip after a match (lz4.c:1255-1294)
-        int  sBase   = 1; int sIter = 0;           // search started at sBase; next un-probed probe number
+        int  insPos  = bs; int hasIns = 1;          // pending table insert ("First Byte" lz4.c:1005-1010; ip-2 lz4.c:1236-1242)
+        int  rePos   = bs; int hasRe  = 0;          // pending immediate re-test at ip after a match (lz4.c:1255-1294)
+        int  sBase   = bs + 1; int sIter = 0;      // search started at sBase; next un-probed probe number
         int  width   = 16;                         // generic batches: 16 lanes first, 64 when a search drags on
         // the pipeline's three stages; which one is batch k-1 / k / k+1 rotates with the unrolled loop below
         LV(GStage, S0); LV(GStage, S1); LV(GStage, S2);
@@ -758,7 +770,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                 const uint64_t mmL = mm; const int at = nseq;
                 LANES({
                     const int slot = LANE_IN(mmL) ? (kPiece ? min_(at + LANE_RANK(mmL), seqDump) : at + LANE_RANK(mmL)) : seqDump;
-                    seq[slot] = seq_pack((uint32_t)(base + LANE), (uint32_t)fwd[I_], (uint32_t)(base + LANE) - (ce[I_] >> sh));
+                    seq[slot] = seq_pack((uint32_t)(base - bs + LANE), (uint32_t)fwd[I_], (uint32_t)(base + LANE) - (ce[I_] >> sh));
                 })
                 nseq += __builtin_popcountll(mm);
                 const int pm = base + eL;
@@ -926,7 +938,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
             const int mc = wave_common_len(src, p + kMinMatch, c + kMinMatch, matchLimit);
             {
                 const int at = nseq;
-                LANES({ if (LANE == 0) seq[kPiece ? min_(at, seqDump) : at] = seq_pack((uint32_t)p, (uint32_t)mc, (uint32_t)(p - c)); })
+                LANES({ if (LANE == 0) seq[kPiece ? min_(at, seqDump) : at] = seq_pack((uint32_t)(p - bs), (uint32_t)mc, (uint32_t)(p - c)); })
             }
             nseq++;
             const int ip = p + kMinMatch + mc;
@@ -941,7 +953,7 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
         }
         if (kPiece) run->fin = !fxStop;
     }
-    *lastAnchor = anchor;
+    *lastAnchor = anchor - bs;
     STAT(P_CYC_TOTAL, STAT_NOW() - tBlock0); STAT(P_BLOCKS, 1); STAT(P_SEQ, nseq);
     STAT_FLUSH();
     return nseq;
@@ -987,11 +999,11 @@ DEV int seq_backext_from(const uint8_t* __restrict__ src, int pos, int cnd, int 
 }
 // its first four bytes without a branch: the dwords in front of the two positions (clamped to the block's start, shifted so
 // that the byte right before the position is the top one), equal leading bytes of their XOR, at most maxBack
-DEV int seq_backext4(const uint8_t* __restrict__ src, int pos, int cnd, int maxBack, bool* more)
+DEV int seq_backext4(const uint8_t* __restrict__ src, int pos, int cnd, int maxBack, bool* more, const int lo = 0)
 {
     // (a match that starts at the anchor cannot catch up, maxBack == 0: its candidate-side load -- a random sector, the bytes this
     // pass is bound by -- goes to the position's dword instead, which the neighbouring lanes read anyway; the result is 0 either way)
-    const int pa = max_(pos - 4, 0), ca = maxBack > 0 ? max_(cnd - 4, 0) : pa;
+    const int pa = max_(pos - 4, 0), ca = maxBack > 0 ? max_(cnd - 4, lo) : pa;
     const uint32_t xa = ld32u(src + pa) << ((8 * (4 - (pos - pa))) & 31), xc = ld32u(src + ca) << ((8 * (4 - (cnd - ca))) & 31);
     const uint32_t x = xa ^ xc;
     const int e4 = x ? (__builtin_clz(x) >> 3) : 4;
@@ -1002,8 +1014,12 @@ DEV int seq_backext4(const uint8_t* __restrict__ src, int pos, int cnd, int maxB
 // bytes of the sequences [c*kSeqChunk, min(nseq, (c+1)*kSeqChunk)) of a block; their catch-up lengths go to bkOut[].
 // Four sequences per lane and trip: their loads are independent, so one memory round trip serves 256 sequences.
 // kBack = false: records that carry the final match (the HC parsers', lz4hc_lazy_device.inl): no catch-up, bkOut unused.
-template <bool kBack = true>
-DEV uint32_t seq_emit_sizes(const uint8_t* __restrict__ src, const uint64_t* __restrict__ seq, uint8_t* __restrict__ bkOut, int nseq, int c)
+// kSeg: the block has an external segment of `pfx` bytes right in front of it (the kExt parser's records): a candidate in the
+// block is not extended backwards into the segment, one in the segment (offset > position) not beyond the segment's first byte
+// (lowLimit, lz4.c:1065-1079).
+DEV int seq_back_room(int pos, int anchor, int cnd, bool seg, int pfx) { return min_(pos - anchor, (seg && cnd < 0) ? cnd + pfx : cnd); }
+template <bool kBack = true, bool kSeg = false>
+DEV uint32_t seq_emit_sizes(const uint8_t* __restrict__ src, const uint64_t* __restrict__ seq, uint8_t* __restrict__ bkOut, int nseq, int c, const int pfx = 0)
 {
     const int i0 = c * kSeqChunk, i1 = min_(nseq, i0 + kSeqChunk);
     LV(int, acc);
@@ -1020,7 +1036,7 @@ DEV uint32_t seq_emit_sizes(const uint8_t* __restrict__ src, const uint64_t* __r
             AN[I_]  = seq_anchor(k_ ? seq[k_ - 1] : 0, k_ == 0); \
             const int pos_ = (int)seq_pos(REC[I_]), cnd_ = pos_ - (int)seq_off(REC[I_]); \
             bool m_ = false; \
-            BK[I_] = kBack ? seq_backext4(src, pos_, cnd_, min_(pos_ - AN[I_], cnd_), &m_) : 0; \
+            BK[I_] = kBack ? seq_backext4(src, pos_, cnd_, seq_back_room(pos_, AN[I_], cnd_, kSeg, pfx), &m_, kSeg ? -pfx : 0) : 0; \
             MO[I_] = m_; \
         })
         SEQ_SZ_STEP(0, rec0, bk0, an0, mo0) SEQ_SZ_STEP(1, rec1, bk1, an1, mo1) SEQ_SZ_STEP(2, rec2, bk2, an2, mo2) SEQ_SZ_STEP(3, rec3, bk3, an3, mo3)
@@ -1028,7 +1044,7 @@ DEV uint32_t seq_emit_sizes(const uint8_t* __restrict__ src, const uint64_t* __r
         if (kBack && BALLOT(mo0[I_] | mo1[I_] | mo2[I_] | mo3[I_])) {               // a catch-up beyond four bytes (rare): the loop
 #define SEQ_SZ_MORE(REC, BK, AN, MO) \
             LANES({ if (MO[I_]) { const int pos_ = (int)seq_pos(REC[I_]), cnd_ = pos_ - (int)seq_off(REC[I_]); \
-                                  BK[I_] = seq_backext_from(src, pos_, cnd_, min_(pos_ - AN[I_], cnd_), 4); } })
+                                  BK[I_] = seq_backext_from(src, pos_, cnd_, seq_back_room(pos_, AN[I_], cnd_, kSeg, pfx), 4); } })
             SEQ_SZ_MORE(rec0, bk0, an0, mo0) SEQ_SZ_MORE(rec1, bk1, an1, mo1) SEQ_SZ_MORE(rec2, bk2, an2, mo2) SEQ_SZ_MORE(rec3, bk3, an3, mo3)
 #undef SEQ_SZ_MORE
         }
@@ -1086,9 +1102,9 @@ DEV void lane_copy(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int l
 // Writes chunk c of a block at dst + chunkOff (token, literal length bytes, literals, offset, match length bytes per sequence:
 // lz4.c:1112-1226); the wave that writes the last chunk (or chunk 0 of a block without sequences) also writes the last
 // literals (lz4.c:1302-1329).  Long literal runs and long length-byte runs are left to the whole wave.
-template <bool kBack = true>
+template <bool kBack = true, bool kSeg = false>
 DEV void seq_emit_write(const uint8_t* __restrict__ src, int n, const uint64_t* __restrict__ seq, const uint8_t* __restrict__ bkIn, int nseq, int lastAnchor, int c,
-                        uint32_t chunkOff, uint8_t* __restrict__ dst)
+                        uint32_t chunkOff, uint8_t* __restrict__ dst, const int pfx = 0)
 {
     const int i0 = c * kSeqChunk, i1 = min_(nseq, i0 + kSeqChunk);
     int op = (int)chunkOff;
@@ -1100,7 +1116,7 @@ DEV void seq_emit_write(const uint8_t* __restrict__ src, int n, const uint64_t* 
                 const uint64_t rec = seq[k];
                 const int an = seq_anchor(k ? seq[k - 1] : 0, k == 0);
                 int bk = kBack ? (int)bkIn[k] : 0;
-                if (kBack && bk == 255) { const int pos = (int)seq_pos(rec), cnd = pos - (int)seq_off(rec); bk = seq_backext_from(src, pos, cnd, min_(pos - an, cnd), 0); }
+                if (kBack && bk == 255) { const int pos = (int)seq_pos(rec), cnd = pos - (int)seq_off(rec); bk = seq_backext_from(src, pos, cnd, seq_back_room(pos, an, cnd, kSeg, pfx), 0); }
                 so[I_] = seq_layout(rec, an, bk);
             }
             else { so[I_].anchor = 0; so[I_].lit = 0; so[I_].mlen = 0; so[I_].extL = 0; so[I_].extM = 0; so[I_].size = 0; so[I_].off = 0; }

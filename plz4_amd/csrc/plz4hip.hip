@@ -240,7 +240,8 @@ __global__ __launch_bounds__(64) void k_fx_begin(unsigned long long* cnt) { if (
 
 // grid (waves per block / 4, blocks of the group): bytes of every chunk of 1024 sequences.  kBack: the level-1 parser's records
 // (their catch-up is measured here); false: the HC parsers' records, which carry the final match.
-template <bool kBack> __global__ __launch_bounds__(256) void k_l1_sizes(CodecArgs a)
+// (kSeg / xb: blocks with an external segment in front of them, k_fxl_sizes / k_fxl_write below)
+template <bool kBack, bool kSeg = false> __device__ __forceinline__ void l1_sizes_body(const CodecArgs a, const FxlBlk* xb = nullptr)
 {
     const int i = blockIdx.y, wave = blockIdx.x * 4 + (int)(threadIdx.x >> 6), nW = gridDim.x * 4;
     const int nseq = a.l1Info[i].nseq;
@@ -250,10 +251,11 @@ template <bool kBack> __global__ __launch_bounds__(256) void k_l1_sizes(CodecArg
     const uint64_t* seq = a.l1Seq + (int64_t)i * a.l1SeqStride;
     const int nChunks = (nseq + kSeqChunk - 1) / kSeqChunk;
     for (int c = wave; c < nChunks; c += nW) {
-        const uint32_t v = seq_emit_sizes<kBack>(s, seq, kBack ? a.l1Bk + (int64_t)i * a.l1SeqStride : nullptr, nseq, c);
+        const uint32_t v = seq_emit_sizes<kBack, kSeg>(s, seq, kBack ? a.l1Bk + (int64_t)i * a.l1SeqStride : nullptr, nseq, c, kSeg ? max_(xb[i].pfx, 0) : 0);
         if ((threadIdx.x & 63u) == 0) a.l1ChunkBytes[(int64_t)i * a.l1MaxChunks + c] = v;
     }
 }
+template <bool kBack> __global__ __launch_bounds__(256) void k_l1_sizes(CodecArgs a) { l1_sizes_body<kBack>(a); }
 
 // one wave per block: where every chunk goes, the block's size, liblz4's limitedOutput verdict; raw mode: result[i] = size or 0;
 // records (blk.CompressToBlk, blk/blk.go:69-109): the size word (stored iff the encoder returned 0) and, without block
@@ -288,7 +290,7 @@ __global__ __launch_bounds__(256) void k_l1_scan(CodecArgs a)
 }
 
 // grid as k_l1_sizes: every chunk written at its place; a record whose encoder returned 0 gets the plaintext instead
-template <bool kBack> __global__ __launch_bounds__(256) void k_l1_write(CodecArgs a)
+template <bool kBack, bool kSeg = false> __device__ __forceinline__ void l1_write_body(const CodecArgs a, const FxlBlk* xb = nullptr)
 {
     const int i = blockIdx.y, wave = blockIdx.x * 4 + (int)(threadIdx.x >> 6), nW = gridDim.x * 4;
     const SeqInfo inf = a.l1Info[i];
@@ -308,13 +310,15 @@ template <bool kBack> __global__ __launch_bounds__(256) void k_l1_write(CodecArg
         const uint64_t* seq = a.l1Seq + (int64_t)i * a.l1SeqStride;
         const int nChunks = (inf.nseq + kSeqChunk - 1) / kSeqChunk;
         for (int c = wave; c < (nChunks ? nChunks : 1); c += nW)
-            seq_emit_write<kBack>(s, n, seq, kBack ? a.l1Bk + (int64_t)i * a.l1SeqStride : nullptr, inf.nseq, inf.lastAnchor, c, nChunks ? a.l1ChunkOff[(int64_t)i * a.l1MaxChunks + c] : 0u, out);
+            seq_emit_write<kBack, kSeg>(s, n, seq, kBack ? a.l1Bk + (int64_t)i * a.l1SeqStride : nullptr, inf.nseq, inf.lastAnchor, c, nChunks ? a.l1ChunkOff[(int64_t)i * a.l1MaxChunks + c] : 0u, out,
+                                        kSeg ? max_(xb[i].pfx, 0) : 0);
     } else if (!a.rawMode && n > 0) {
         const int slice = (((n + nW - 1) / nW) + 15) & ~15;
         const int off = wave * slice;
         if (off < n) wave_copy(out + off, s + off, min_(slice, n - off));
     }
 }
+template <bool kBack> __global__ __launch_bounds__(256) void k_l1_write(CodecArgs a) { l1_write_body<kBack>(a); }
 
 // records with block checksums: xxh32 over the payload as stored (blk.go:98-102), one wave per block
 __global__ __launch_bounds__(256) void k_l1_finish(CodecArgs a)
@@ -398,6 +402,103 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_encode_raw_dict(Cod
         const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
         const int r = encode_block_primed(a.src + (int64_t)i * a.srcStride, n, a.dst + (int64_t)i * a.dstStride, cap, dc, lds);
         if ((threadIdx.x & 63u) == 0) a.result[i] = r;
+    }
+}
+
+// ---- few level-1 blocks with history outside the block cut across the chip (the kExt flavour of lz4_fx_device.inl) -----------------
+// How block i of the call is primed: what k_encode_rec_dict / k_encode_raw_dict decide, in one place for the kernels below.
+__device__ __forceinline__ DictEnc fxl_dict_of(const CodecArgs& a, int i, int n)
+{
+    DictEnc dc{nullptr, 0, a.rawMode ? kDictNonePrefix : kDictFreshPrefix, nullptr};
+    const uint8_t* tail = nullptr; int tailLen = -1;
+    if (!a.rawMode && a.linked) {
+        if (i > 0) { const int pl = block_len(a, i - 1); tailLen = pl < 65536 ? pl : 65536; tail = a.src + (int64_t)(i - 1) * a.srcStride + (pl - tailLen); }
+        else if (a.prevTailLen >= 0) { tail = a.prevTail; tailLen = a.prevTailLen; }
+    }
+    if (tailLen >= 0) {                                       // linked block after another block: LZ4_loadDict(previous tail)
+        dc.mode = tailLen >= 8 ? kDictLoad : kDictNonePrefix;
+        if (tailLen >= 8) { dc.dict = tail; dc.dictSize = tailLen; }
+    } else if (a.rawMode || a.dict != nullptr || a.dictLen >= 0) {     // a dictionary context is attached (possibly an empty one)
+        if (a.dictLen >= 8) { dc.dict = a.dict; dc.dictSize = a.dictLen; dc.dictTable = a.dictTable; dc.mode = n > 4096 ? kDictCtxCopy : kDictCtxLookup; }
+        else dc.mode = kDictNonePrefix;
+    }
+    return dc;
+}
+// grid (blocks of the group), one wave each: the segment in front of the block, piece 0's entry table, the block's FxlBlk
+__global__ __launch_bounds__(64) void k_fxl_prep(CodecArgs a, FxArgs f, FxlBlk* xb)
+{
+    __shared__ uint32_t lds[kHashBytes / 4];
+    const int i = blockIdx.x, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    FxlBlk b; b.pfx = -2; b.bs = 0;                                          // -2: a length the workspace was not sized for
+    if (n >= 0 && n <= a.l1MaxLen) {
+        const DictEnc dc = fxl_dict_of(a, gi, n);
+        b = fxl_prep(const_cast<uint8_t*>(a.src) + (int64_t)gi * a.srcStride, n, dc.mode, dc.dict, dc.dictSize, dc.dictTable,
+                     f.tabIn + (int64_t)i * f.P * kFxTab, lds);
+    }
+    if ((threadIdx.x & 63u) == 0) xb[i] = b;
+}
+__global__ __launch_bounds__(64) void k_fxl_piece(CodecArgs a, FxArgs f, const FxlBlk* xb, int round)
+{
+    __shared__ uint32_t lds[kHashBytes / 4];
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi), pfx = xb[i].pfx, bs = xb[i].bs;          // (loaded before anything is stored: scalar loads)
+    if (pfx < 0) {
+        // not this path's: an empty parse (k_fxl_small writes the block behind the emit stage), or no result (-1, as k_l1_parse says it)
+        if (round == 1 && k == 0 && (threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = pfx == -1 ? 0 : -1; inf.lastAnchor = 0; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
+        return;
+    }
+    const int64_t pb0 = (int64_t)i * f.P;
+    fx_piece<true>(a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * kFxTab, f.tabOut + pb0 * 2 * kFxTab,
+                   f.rec + pb0 * f.recStride, f.recStride, lds, bs);
+}
+__global__ __launch_bounds__(64) void k_fxl_gather(CodecArgs a, FxArgs f, const FxlBlk* xb)
+{
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    if (xb[i].pfx < 0 || k >= fx_pieces_of<true>(n, f.pb)) return;
+    const int64_t pb0 = (int64_t)i * f.P;
+    const FxPiece* m = f.meta + pb0;
+    const int g = fx_gather<true>(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
+                                (int)a.l1SeqStride - 1, a.l1Info + i);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicMax(&f.cnt[1], (unsigned long long)m[k].lastRound);
+        if (m[k].runs > 1) atomicAdd(&f.cnt[2], 1ull);
+        if (g == 2) { atomicAdd(&f.cnt[0], 1ull); atomicAdd(&f.cnt[7], 1ull); }
+    }
+}
+__global__ __launch_bounds__(256) void k_fxl_sizes(CodecArgs a, const FxlBlk* xb) { l1_sizes_body<true, true>(a, xb); }
+__global__ __launch_bounds__(256) void k_fxl_write(CodecArgs a, const FxlBlk* xb) { l1_write_body<true, true>(a, xb); }
+// Behind the emit stage: the blocks <= 4 KiB under a dictionary context (two tables, wave_encode_block_dict), as k_encode_rec_dict /
+// k_encode_raw_dict write them -- record or block, checksum and result; what the emit stage wrote for them does not survive.
+__global__ __launch_bounds__(64) void k_fxl_small(CodecArgs a)
+{
+    __shared__ uint32_t lds[kHashBytes / 4];
+    for (int i = blockIdx.x; i < a.nBlocks; i += gridDim.x) {
+        const int gi = a.blk0 + i;
+        const int n = block_len(a, gi);
+        if (n < 0 || n > 4096) continue;
+        const DictEnc dc = fxl_dict_of(a, gi, n);
+        if (dc.mode != kDictCtxLookup) continue;
+        const uint8_t* s = a.src + (int64_t)gi * a.srcStride;
+        if (a.rawMode) {
+            const int cap = a.dstCap ? a.dstCap[gi] : a.dstCapAll;
+            const int r = wave_encode_block_dict(s, n, a.dst + (int64_t)gi * a.dstStride, cap, dc, lds);
+            if ((threadIdx.x & 63u) == 0) a.result[gi] = r;
+            continue;
+        }
+        uint8_t* rec = a.dst + (int64_t)gi * a.dstStride;
+        int      c    = wave_encode_block_dict(s, n, rec + 4, a.bsz, dc, lds);
+        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
+        if (c == 0) { wave_copy(rec + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
+        int len = c + 4;
+        if (a.blockChecksum) {
+            WAVE_FENCE();
+            const uint32_t x = wave_xxh32(rec + 4, c);
+            if ((threadIdx.x & 63u) == 0) st32u(rec + 4 + c, x);
+            len += 4;
+        }
+        if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[gi] = len; }
     }
 }
 
@@ -1478,7 +1579,8 @@ struct plz4hip_ctx {
     // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
     // parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history outside the block (dictionary,
     // linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of a call cut into groups),
-    // [6] the groups of the last call that was cut into groups
+    // [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block (dictionary, linked)
+    // encoded by the few-block level-1 path (a subset of [0])
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
@@ -1732,7 +1834,7 @@ bool use_h12(const CodecArgs& a, int maxLen) { return a.level >= 12 && !a.hcEx &
 bool use_lazy(const CodecArgs& a, int maxLen) { return a.level >= 3 && (a.level <= 11 || getenv("PLZ4HIP_HC12_LAZY") != nullptr) && !a.hcEx && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_LAZY_OFF") == nullptr; }
 
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined = nullptr,
-              const CodecArgs* rider = nullptr);
+              const CodecArgs* rider = nullptr, bool hist = false);
 
 // Enqueue one HC call of nb blocks (a: everything but queue / workspace filled in) on s.  rawMode: LZ4 blocks, else records.
 int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked);
@@ -2037,6 +2139,16 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
 }
 
 // Enqueue one level-1 call of nb independent blocks without dictionary (a: everything but queue / workspace filled in) on s.
+// Whether a level-1 call of nb blocks with history outside the block (a dictionary, linked blocks) takes the few-block path:
+// at most PLZ4HIP_FX_MAX_BLOCKS blocks, the largest of kFxMinLen .. 4 MiB, and PLZ4HIP_FX_LINKED not 0 (read per call).
+bool fxl_wanted(int nb, int maxLen)
+{
+    if (const char* v = getenv("PLZ4HIP_FX_LINKED")) { if (atoi(v) == 0) return false; }
+    int fxMax = kFxMaxBlocks;
+    if (const char* v = getenv("PLZ4HIP_FX_MAX_BLOCKS")) fxMax = atoi(v);
+    return nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_L1_FUSED") == nullptr;
+}
+
 // rawMode: LZ4 blocks (result = bytes or 0), else records.  Blocks up to 4 MiB run in stages (lz4_seq_device.inl): the
 // workspace holds 8 bytes per possible sequence -- 2 bytes per input byte -- of one group of blocks; a call that does not fit
 // the memory set aside (half of what is free; PLZ4HIP_L1_BUDGET_GIB) runs in groups of equal size.  ws: the workspace to use
@@ -2046,10 +2158,20 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
 // be had, the caller then runs its one-kernel path.
 // rider: the record decode of another call (queue filled in) that shares the parse kernel's launch (k_l1_duplex); a call that
 // runs in groups carries it in its first group, one that takes the fused kernels launches it by itself.
+// hist: the blocks have history outside the block (a: dictionary / linked fields filled in, 64 KiB of room in front of every input
+// block).  Such a call is here for the few-block path's external-segment flavour (fxl_wanted has said yes); whenever that path
+// cannot be had -- no workspace, the fused kernels -- it runs k_encode_rec_dict / k_encode_raw_dict, one wave per block, as ever.
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined,
-              const CodecArgs* rider)
+              const CodecArgs* rider, bool hist)
 {
     hipError_t e;
+    const auto dict_kernels = [&]() -> int {
+        a.blk0 = 0; a.nBlocks = nb;
+        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (rawMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a); else ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
+        HIPCHK(c, hipGetLastError());
+        return PLZ4HIP_OK;
+    };
     const bool mid = midDeclined != nullptr;
     a.rawMode = rawMode; a.blk0 = 0; a.nBlocks = nb;
     const bool shared = (ws == nullptr);
@@ -2105,6 +2227,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         if (getenv("PLZ4HIP_VERBOSE"))
             fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, fused ? " (fused)" : "");
     }
+    if (fused && hist) return dict_kernels();
     if (fused && mid) { *midDeclined = true; return PLZ4HIP_OK; }
     if (fused && a.bodyOff) return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
     if (fused) {
@@ -2127,6 +2250,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     // chip (lz4_fx_device.inl) in pieces of PLZ4HIP_FX_PIECE_KIB, guessed starts PLZ4HIP_FX_WARMUP_KIB early.  Its workspace is sized
     // per call (a group of `per` blocks); when it cannot be had, the call parses as below.
     FxArgs fx{};
+    FxlBlk* xb = nullptr;                                                       // hist: per block of a group, its segment (k_fxl_prep)
     bool useFx = false;
     {
         int fxMax = kFxMaxBlocks;
@@ -2139,17 +2263,20 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             fx.P = (maxLen + fx.pb - 1) / fx.pb; fx.recStride = fx_rec_stride_host(fx.pb); fx.cnt = c->d_counters;
             const size_t nP = (size_t)per * fx.P;
             const size_t offIn = round_up(nP * sizeof(FxPiece), 256), offOut = offIn + nP * kFxTab * 4, offRec = offOut + 2 * nP * kFxTab * 4;
-            const size_t need = offRec + nP * (size_t)fx.recStride * 8;
+            const size_t offBlk = offRec + nP * (size_t)fx.recStride * 8;
+            const size_t need = offBlk + (hist ? round_up((size_t)per * sizeof(FxlBlk), 256) : 0);
             HIPCHK(c, c->fxOrder.wait(s));
             bool refused = false;  HIPCHK(c, c->fx.reserve(need, c->fxOrder, &refused));
             if (!refused) {
                 fx.meta = (FxPiece*)c->fx.d; fx.tabIn = (uint32_t*)(c->fx.d + offIn); fx.tabOut = (uint32_t*)(c->fx.d + offOut);
                 fx.rec = (uint64_t*)(c->fx.d + offRec);
+                if (hist) xb = (FxlBlk*)(c->fx.d + offBlk);
                 useFx = true;
                 fxJob.arm(c->fxOrder, s);
             }
         }
     }
+    if (hist && !useFx) return dict_kernels();
     for (int g0 = 0; g0 < nb; g0 += per) {
         const int ng = nb - g0 < per ? nb - g0 : per;
         a.blk0 = g0; a.nBlocks = ng;
@@ -2172,6 +2299,13 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         }
         if (mid && a.hcPfx) hipLaunchKernelGGL(k_hc_mid<true>, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
         else if (mid) hipLaunchKernelGGL(k_hc_mid<false>, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
+        else if (useFx && hist) {
+            // (every block reads block gi - 1's plaintext tail out of the call's input, whichever group that block is in)
+            if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
+            hipLaunchKernelGGL(k_fxl_prep, dim3(ng), dim3(64), 0, s, a, fx, xb);
+            for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fxl_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, (const FxlBlk*)xb, r);
+            hipLaunchKernelGGL(k_fxl_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx, (const FxlBlk*)xb);
+        }
         else if (useFx) {
             // P rounds are always enough (lz4_fx_device.inl); the rounds after the last change find nothing to do
             if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
@@ -2214,13 +2348,16 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         int wg = (16384 / ng) / 4;
         if (wg > (maxChunks + 3) / 4) wg = (maxChunks + 3) / 4;
         if (wg < 1) wg = 1;
-        if (mid) hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
+        if (hist) hipLaunchKernelGGL(k_fxl_sizes, dim3(wg, ng), dim3(256), 0, s, a, (const FxlBlk*)xb);
+        else if (mid) hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_l1_sizes<true>, dim3(wg, ng), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
         if (a.bodyOff) hipLaunchKernelGGL(k_scan_from, dim3(1), dim3(1024), 0, s, (const int32_t*)(a.result + g0), a.bodyOff + g0, ng, g0 == 0 ? 1 : 0);
-        if (mid) hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
+        if (hist) hipLaunchKernelGGL(k_fxl_write, dim3(wg, ng), dim3(256), 0, s, a, (const FxlBlk*)xb);
+        else if (mid) hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_l1_write<true>, dim3(wg, ng), dim3(256), 0, s, a);
         if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 3) / 4), dim3(256), 0, s, a);
+        if (hist && a.dictLen >= 8) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);   // (the blocks <= 4 KiB under the context)
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, job.leave());
@@ -2506,11 +2643,11 @@ int plz4hip_ctx_counters(plz4hip_ctx* c, int64_t* out, int n)
     if (!c || n < 0 || (n > 0 && !out)) return PLZ4HIP_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
-    unsigned long long v[7] = {0, 0, 0, 0, 0, 0, 0};
+    unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipDeviceSynchronize());                                      // (the ctx's work runs on the callers' streams)
     HIPCHK(c, copy_sync(c, v, c->d_counters, sizeof v, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n && i < 7; ++i) out[i] = (int64_t)v[i];
-    return 7;
+    for (int i = 0; i < n && i < 8; ++i) out[i] = (int64_t)v[i];
+    return 8;
 }
 
 const char* plz4hip_last_error(const plz4hip_ctx* c)
@@ -2953,12 +3090,14 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
         }
         switch (mode) {
         case 0: if (hcMode) { if (int rc = launch_hc(c, s, a, nb, maxIn, 1)) return rc; }
+                else if (dictMode && fxl_wanted(nb, maxIn)) { if (int rc = launch_l1(c, s, a, nb, maxIn, 1, &sl.l1, nullptr, nullptr, true)) return rc; }
                 else if (dictMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a);
                 else { if (int rc = launch_l1(c, s, a, nb, maxIn, 1, &sl.l1)) return rc; } break;
         case 1: if (int rc = launch_decode(c, s, a, nb, maxIn, maxOut, false, dictMode ? kHistDict : kHistNone)) return rc;
                 break;
         case 2: a.dstCap = nullptr;
                 if (hcMode) { if (int rc = launch_hc(c, s, a, nb, maxIn, 0)) return rc; }
+                else if (dictMode && fxl_wanted(nb, maxIn)) { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1, nullptr, nullptr, true)) return rc; }
                 else if (dictMode) ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
                 else { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1)) return rc; } break;
         case 3: a.dstCap = nullptr;
