@@ -349,6 +349,28 @@ func (c *Ctx) DecodeRecordsChains(chainFirst []int32, rec, dst [][]byte, bsz int
 	return
 }
 
+// DevPtr is an address in the ctx's device memory (what a HIP allocation or a GPU producer hands over); a stream is a hipStream_t,
+// nil being HIP's null stream.
+type DevPtr = unsafe.Pointer
+
+// DevEncodeRecordsEx == EncodeRecordsEx for plaintext that lies in device memory (plz4hip_dev_encode_records_ex): block i at
+// src + i*srcStride, srcStride == bsz for contiguous plaintext or >= bsz + 65536 with 64 KiB of the caller's scratch in front of
+// every block (the segment rule of plz4hip.h).  prevTailLen < 0: block 0 starts the frame.  The records land in stage at
+// plz4hip_dev_stage_stride(bsz), their lengths in recLen (int32 per block, device).  Enqueued on stream; nothing is waited for.
+func (c *Ctx) DevEncodeRecordsEx(src DevPtr, srcBytes, srcStride int64, bsz, level int, blockChecksum, linked bool, d *Dict,
+	prevTail DevPtr, prevTailLen int, stage, recLen DevPtr, stream unsafe.Pointer) error {
+	return c.chk(C.plz4hip_dev_encode_records_ex(c.p, src, C.int64_t(srcBytes), C.int64_t(srcStride), C.int(bsz), C.int(level), b2i(blockChecksum),
+		b2i(linked), d.ptr(), prevTail, C.int(prevTailLen), stage, (*C.int32_t)(recLen), stream))
+}
+
+// DevEncodeBodyEx: the same with the records back to back in body (plz4hip_dev_encode_body_ex; levels 1 and 2): record i at
+// body + recOff[i], recOff (int64 per block + 1, device) ends with the body's length, which exceeds bodyCap when records were left out.
+func (c *Ctx) DevEncodeBodyEx(src DevPtr, srcBytes, srcStride int64, bsz, level int, blockChecksum, linked bool, d *Dict,
+	prevTail DevPtr, prevTailLen int, body DevPtr, bodyCap int64, recOff, recLen DevPtr, stream unsafe.Pointer) error {
+	return c.chk(C.plz4hip_dev_encode_body_ex(c.p, src, C.int64_t(srcBytes), C.int64_t(srcStride), C.int(bsz), C.int(level), b2i(blockChecksum),
+		b2i(linked), d.ptr(), prevTail, C.int(prevTailLen), body, C.int64_t(bodyCap), (*C.int64_t)(recOff), (*C.int32_t)(recLen), stream))
+}
+
 func b2i(b bool) C.int {
 	if b {
 		return 1

@@ -60,6 +60,9 @@
  * previous block's tail or the dictionary -- is laid in front of every block and the table liblz4 starts the block with is the
  * first piece's entry state; every block of such a call may be shorter than a piece, only blocks <= 4 KiB under a dictionary
  * context keep their two-table encoder.  PLZ4HIP_FX_LINKED=0 (read per call) keeps such calls on one wavefront per block.
+ * The device-resident calls with history outside the block (dev_encode_records_ex, dev_encode_body_ex) take it likewise; a call of
+ * more blocks there runs the staged level-1 design with one wavefront per block and holds the level-1 workspace above (2.25 bytes
+ * per input byte of a group of blocks), PLZ4HIP_L1X=0 the one-kernel encoder (see section C).
  * Duplex calls and level 2 keep their kernels.  It keeps about 3 bytes per input byte of the call's blocks (the pieces' tables
  * and records) until plz4hip_ctx_trim.  plz4hip_ctx_counters reports what these few-block paths did.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
@@ -110,7 +113,9 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
  * in the last such call, [2] pieces it parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history
  * outside the block (dictionary, linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of
  * a call cut into groups), [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block encoded by
- * the few-block level-1 path (a subset of [0]).  Returns how many counters there are (8), or PLZ4HIP_E_*. */
+ * the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the staged one-wavefront-per-block
+ * route of plz4hip_dev_encode_records_ex / _body_ex (not those the one-kernel encoder took).  Returns how many counters there are (9),
+ * or PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */
@@ -303,6 +308,45 @@ int plz4hip_dev_duplex_body(plz4hip_ctx* ctx, const void* src, int64_t srcBytes,
                             void* body, int64_t bodyCap, int64_t* recOff, int32_t* recLen,
                             const void* decBody, const int64_t* decRecOff, int nDecBlocks, int decBsz, int decBlockChecksum,
                             void* dst, int64_t dstStride, int dstCap, int32_t* result, int32_t* status, void* stream);
+
+/* plz4hip_dev_encode_records_ex / plz4hip_dev_encode_body_ex: plz4hip_dev_encode_records / plz4hip_dev_encode_body for blocks with
+ * history outside the block -- what plz4hip_encode_records_ex does over host buffers (WithBlockLinked, WithDictionary; BASELINE
+ * config 5), for a producer whose plaintext is on the device.  Enqueued on `stream`, no synchronisation; every pointer is a device
+ * pointer.  Block i = src + i*srcStride, nBlocks = ceil(srcBytes / bsz), the last block is short.  srcStride == bsz: contiguous
+ * plaintext; srcStride >= bsz + 65536: gapped, 64 KiB of caller-owned scratch in front of every block; anything else: PLZ4HIP_E_ARG.
+ * `linked`, `dict`, prevTail / prevTailLen mean what they mean in plz4hip_encode_records_ex and prime a block exactly as there
+ * (prevTail is a device pointer; prevTailLen < 0: none, block 0 starts the frame; > 65536: PLZ4HIP_E_ARG).  prevTail either ends
+ * exactly at src or does not overlap [src - prevTailLen, src), where it is laid; anything else: PLZ4HIP_E_ARG.
+ * THE SEGMENT RULE.  The kernels read a block's external segment -- the previous block's last <= 64 KiB, prevTail, or the dictionary --
+ * immediately in front of the block.  Where the segment a block needs is not already the bytes lying there, the 64 KiB in front of
+ * that block must be writable scratch of the caller, and the engine lays the segment there:
+ *   linked = 1, contiguous : block i > 0 finds block i-1's tail in front of it: nothing is copied.  Only block 0 can need the
+ *                            scratch (src - 65536 .. src), for the dictionary or prevTail; when prevTail == src - prevTailLen -- a
+ *                            later call that continues one big buffer -- nothing is copied and nothing is written.
+ *   linked = 1, gapped     : every block's tail is copied from its predecessor into the block's gap.
+ *   linked = 0 with dict   : every block is against the dictionary; needs the gapped stride (contiguous: PLZ4HIP_E_ARG).
+ *   linked = 0, no dict    : PLZ4HIP_E_ARG (plz4hip_dev_encode_records / plz4hip_dev_encode_body).
+ * Outside those scratch regions the call writes no byte of src.
+ * Levels 1..12 (records_ex; levels 2..12 are the HC designs over segment + block, as in B'); body_ex takes levels 1 and 2 like
+ * plz4hip_dev_encode_body (level 2 with a block <= 4 KiB that starts under an attached dictionary of any length, which the
+ * one-thread parser writes as a staged record: PLZ4HIP_E_UNSUPPORTED, use records_ex + plz4hip_dev_compact_records).    A block that does not fit comes back as a stored record; the note in B' about the reference's
+ * linked HC writer applies unchanged.  These calls do not feed plz4hip_ctx_set_content_hash (plz4hip_dev_xxh32_stream_update takes
+ * the plaintext where it lies).
+ * Level 1: a call of few blocks (see ENCODE above) is cut across the chip like the host-buffer call.  A call of more blocks runs the
+ * staged design with one wavefront per block -- each block one exact run of the parser behind its segment, the table liblz4 starts
+ * the block with built in the wavefront's own LDS table, then the data-parallel emit stage; it keeps the level-1 workspace (2.25
+ * bytes per input byte of a group of blocks, like the independent call).  PLZ4HIP_L1X=0 (read per call), PLZ4HIP_L1_FUSED or a
+ * workspace that cannot be had: the one-kernel encoder of plz4hip_encode_records_ex instead (body_ex then stages its records in a
+ * buffer of the ctx's, nBlocks x plz4hip_dev_stage_stride(bsz), until plz4hip_ctx_trim; a refused workspace there: PLZ4HIP_E_NOMEM).
+ * The staged design is the default for many blocks: on linked 4 MiB blocks of text behind a 64 KiB dictionary body_ex takes 77 ms
+ * at 512 blocks and 256 ms at 6144 (94 GiB/s), the one-kernel encoder 154 and 461 ms, plz4hip_dev_encode_body on the same bytes as
+ * independent blocks 76 and 250 ms (profiles/l1x_rate.json, scripts/l1x_rate.py). */
+int plz4hip_dev_encode_records_ex(plz4hip_ctx* ctx, const void* src, int64_t srcBytes, int64_t srcStride, int bsz, int level,
+                                  int blockChecksum, int linked, const plz4hip_dict* dict, const void* prevTail, int prevTailLen,
+                                  void* stage, int32_t* recLen, void* stream);
+int plz4hip_dev_encode_body_ex(plz4hip_ctx* ctx, const void* src, int64_t srcBytes, int64_t srcStride, int bsz, int level,
+                               int blockChecksum, int linked, const plz4hip_dict* dict, const void* prevTail, int prevTailLen,
+                               void* body, int64_t bodyCap, int64_t* recOff, int32_t* recLen, void* stream);
 
 /* Raw LZ4 blocks on the device (no record framing): block i = src + i*srcStride (srcLen[i] bytes) ->
  * dst + i*dstStride (capacity dstCap[i]); result[i] as in A, levels 1..12.  srcLen/dstCap/result are device arrays.

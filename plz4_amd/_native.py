@@ -18,7 +18,7 @@ SYMBOLS = [
     "plz4hip_last_error", "plz4hip_compress_bound", "plz4hip_compress_batch", "plz4hip_decompress_batch",
     "plz4hip_xxh32_batch", "plz4hip_encode_records", "plz4hip_decode_records", "plz4hip_dev_stage_stride",
     "plz4hip_dev_encode_records", "plz4hip_dev_compact_records", "plz4hip_dev_scatter_records",
-    "plz4hip_dev_decode_records", "plz4hip_dev_decode_records_ex", "plz4hip_dev_duplex_records", "plz4hip_dev_encode_body", "plz4hip_dev_duplex_body", "plz4hip_dev_compress", "plz4hip_dev_decompress", "plz4hip_ctx_trim",
+    "plz4hip_dev_decode_records", "plz4hip_dev_decode_records_ex", "plz4hip_dev_duplex_records", "plz4hip_dev_encode_body", "plz4hip_dev_duplex_body", "plz4hip_dev_encode_records_ex", "plz4hip_dev_encode_body_ex", "plz4hip_dev_compress", "plz4hip_dev_decompress", "plz4hip_ctx_trim",
     "plz4hip_ctx_counters",
     "plz4hip_dev_resident_waves", "plz4hip_dict_create", "plz4hip_dict_destroy", "plz4hip_compress_batch_dict", "plz4hip_decode_records_chains",
     "plz4hip_decompress_batch_dict", "plz4hip_encode_records_ex", "plz4hip_decode_records_ex",
@@ -97,6 +97,11 @@ def load():
                                              vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp]
     L.plz4hip_dev_encode_body.restype = C.c_int
     L.plz4hip_dev_encode_body.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp]
+    L.plz4hip_dev_encode_records_ex.restype = C.c_int
+    L.plz4hip_dev_encode_records_ex.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.plz4hip_dev_encode_body_ex.restype = C.c_int
+    L.plz4hip_dev_encode_body_ex.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
+                                             vp, C.c_int64, vp, vp, vp]
     L.plz4hip_dev_duplex_body.restype = C.c_int
     L.plz4hip_dev_duplex_body.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp,
                                           vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp]
@@ -369,6 +374,20 @@ class Engine:
         self._chk(self.L.plz4hip_dev_encode_body(self.h, src_ptr, src_bytes, bsz, level, int(block_checksum), body_ptr, body_cap,
                                                  recoff_ptr, reclen_ptr, stream))
 
+    def dev_encode_records_ex(self, src_ptr, src_bytes, src_stride, bsz, block_checksum, stage_ptr, reclen_ptr, linked=False, d=None,
+                              prev_tail_ptr=None, prev_tail_len=-1, stream=0, level: int = 1):
+        """dev_encode_records for linked blocks and / or blocks under the dictionary d: block i at src + i * src_stride (bsz:
+        contiguous plaintext; >= bsz + 65536: 64 KiB of scratch in front of every block); prev_tail_ptr / prev_tail_len: the device
+        bytes block 0 of a linked call continues (-1: it starts the frame)"""
+        self._chk(self.L.plz4hip_dev_encode_records_ex(self.h, src_ptr, src_bytes, src_stride, bsz, level, int(block_checksum), int(linked), d,
+                                                       prev_tail_ptr, prev_tail_len, stage_ptr, reclen_ptr, stream))
+
+    def dev_encode_body_ex(self, src_ptr, src_bytes, src_stride, bsz, block_checksum, body_ptr, body_cap, recoff_ptr, reclen_ptr,
+                           linked=False, d=None, prev_tail_ptr=None, prev_tail_len=-1, stream=0, level: int = 1):
+        """dev_encode_records_ex with the records straight in the frame body (dev_encode_body's outputs); levels 1 and 2"""
+        self._chk(self.L.plz4hip_dev_encode_body_ex(self.h, src_ptr, src_bytes, src_stride, bsz, level, int(block_checksum), int(linked), d,
+                                                    prev_tail_ptr, prev_tail_len, body_ptr, body_cap, recoff_ptr, reclen_ptr, stream))
+
     def dev_duplex_body(self, src_ptr, src_bytes, bsz, block_checksum, body_ptr, body_cap, recoff_ptr, reclen_ptr,
                         dec_body_ptr, dec_recoff_ptr, ndec, dec_bsz, dec_block_checksum, dst_ptr, dst_stride, dst_cap,
                         result_ptr, status_ptr, stream=0):
@@ -411,13 +430,14 @@ class Engine:
         self._chk(self.L.plz4hip_ctx_trim(self.h))
 
     COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last", "dxl_groups_last",
-                "fxl_blocks")
+                "fxl_blocks", "l1x_blocks")
 
     def counters(self) -> dict:
         """plz4hip_ctx_counters (waits for the ctx's work): blocks encoded by the few-block level-1 path, its rounds in the last
         such call, pieces it parsed more than once, blocks answered by the few-block decoder, blocks with history outside the block
         (dictionary, linked) answered by it, its jump rounds in the last such call, the groups of the last linked call that was
-        cut into groups, blocks with history outside the block encoded by the few-block level-1 path (a subset of the first)."""
+        cut into groups, blocks with history outside the block encoded by the few-block level-1 path (a subset of the first), such
+        blocks parsed by the bulk staged route of the device-resident calls (k_l1x_parse)."""
         out = (C.c_int64 * len(self.COUNTERS))()
         rc = int(self.L.plz4hip_ctx_counters(self.h, out, len(self.COUNTERS)))
         if rc < 0:

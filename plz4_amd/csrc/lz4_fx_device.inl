@@ -159,22 +159,16 @@ DEV int fx_gather(int n, int k, int pb, const FxPiece* __restrict__ meta, const 
 // ---- blocks with history outside the block
 struct FxlBlk { int32_t pfx, bs; };       // the segment's bytes (-1: not this path's block) and liblz4's index of the block's first byte
 
-// One wave: how block `blk` of n bytes starts under `mode` (kDict*, lz4_device.inl; seg / segLen: the previous block's tail or the
-// dictionary, dictTable: the dictionary context's LZ4_loadDictSlow table).  The segment is copied right in front of the block --
-// the caller has left 64 KiB there -- and the table liblz4 starts the block with goes to tabG (16 KiB of global memory) as
-// index << 9 | tag: LZ4_loadDict over the segment, every 3rd position, the largest index per slot (lz4.c:1621-1628); the context's
-// table, copied and tagged (lz4.c:1762-1768); else every slot "index 0".  Indices: the segment ends at 64 KiB, so delta =
-// 64 KiB - segLen and every entry is 0 or a position of the segment.  lds: 16 KiB owned by the wave.
-DEV FxlBlk fxl_prep(uint8_t* blk, int n, int mode, const uint8_t* __restrict__ seg, int segLen, const uint32_t* __restrict__ dictTable,
-                    uint32_t* __restrict__ tabG, uint32_t* lds)
+// One wave: the table liblz4 starts a block with under `mode` (kDict*, lz4_device.inl), into `lds` (16 KiB owned by the wave) as
+// index << 9 | tag.  seg: the pfx bytes of the external segment (the previous block's tail or the dictionary; wherever they lie),
+// dictTable: the dictionary context's LZ4_loadDictSlow table.  LZ4_loadDict over the segment, every 3rd position, the largest index
+// per slot (lz4.c:1621-1628); the context's table, copied and tagged (lz4.c:1762-1768); else every slot "index 0".  Indices: the
+// segment ends at 64 KiB, so delta = 64 KiB - pfx and every entry is 0 or a position of the segment.
+DEV void fxl_table(const uint8_t* blk, int n, int mode, const uint8_t* __restrict__ seg, int pfx, const uint32_t* __restrict__ dictTable, uint32_t* lds)
 {
-    FxlBlk b; b.pfx = 0; b.bs = 65536;
-    if (mode == kDictCtxLookup) { b.pfx = -1; return b; }
     uint32_t e0 = 0;
-    if (mode == kDictFreshPrefix) { b.bs = 0; if (n >= 4) e0 = seq_tag(UNI(ld32u(blk))) & 0x1FFu; }       // "index 0" is the block's first byte
-    const bool withSeg = mode == kDictLoad || mode == kDictCtxCopy;
-    if (withSeg) b.pfx = segLen;
-    const uint32_t delta = 65536u - (uint32_t)b.pfx;
+    if (mode == kDictFreshPrefix && n >= 4) e0 = seq_tag(UNI(ld32u(blk))) & 0x1FFu;                      // "index 0" is the block's first byte
+    const uint32_t delta = 65536u - (uint32_t)pfx;
     if (mode == kDictCtxCopy) {
         LANES({ for (int i = LANE; i < kFxTab; i += 64) {
             const uint32_t idx = dictTable[i];
@@ -184,7 +178,7 @@ DEV FxlBlk fxl_prep(uint8_t* blk, int n, int mode, const uint8_t* __restrict__ s
         LANES({ for (int i = LANE; i < kFxTab; i += 64) lds[i] = e0; })
         if (mode == kDictLoad) {
             LDS_FENCE();
-            const int cnt = (segLen - 8) / 3 + 1;
+            const int cnt = (pfx - 8) / 3 + 1;
             LANES({ for (int k = LANE; k < cnt; k += 64) {
                 const uint64_t s8 = ld64u(seg + 3 * k);
                 lds_max(&lds[seq_hash<false>(s8)], (((uint32_t)(3 * k) + delta) << 9) | (seq_tag((uint32_t)s8) & 0x1FFu));
@@ -192,9 +186,53 @@ DEV FxlBlk fxl_prep(uint8_t* blk, int n, int mode, const uint8_t* __restrict__ s
         }
     }
     LDS_FENCE();
-    LANES({ for (int i = LANE; i < kFxTab; i += 64) tabG[i] = lds[i]; })
-    if (withSeg) wave_copy(blk - segLen, seg, segLen);
+}
+// pfx / bs of a block under `mode` with a segment of segLen bytes
+DEV FxlBlk fxl_blk_of(int mode, int segLen)
+{
+    FxlBlk b; b.pfx = 0; b.bs = 65536;
+    if (mode == kDictCtxLookup) { b.pfx = -1; return b; }
+    if (mode == kDictFreshPrefix) b.bs = 0;
+    if (mode == kDictLoad || mode == kDictCtxCopy) b.pfx = segLen;
     return b;
+}
+
+// One wave: how block `blk` of n bytes starts under `mode` (seg / segLen: the previous block's tail or the dictionary).  The segment
+// is copied right in front of the block -- the caller has left 64 KiB there; a segment that already lies there (the tail of the
+// block before in contiguous plaintext) stays where it is: its neighbours read it meanwhile -- and the table liblz4 starts the
+// block with (fxl_table) goes to tabG (16 KiB of global memory).  lds: 16 KiB owned by the wave.
+DEV FxlBlk fxl_prep(uint8_t* blk, int n, int mode, const uint8_t* __restrict__ seg, int segLen, const uint32_t* __restrict__ dictTable,
+                    uint32_t* __restrict__ tabG, uint32_t* lds)
+{
+    const FxlBlk b = fxl_blk_of(mode, segLen);
+    if (b.pfx < 0) return b;
+    fxl_table(blk, n, mode, seg, b.pfx, dictTable, lds);
+    LANES({ for (int i = LANE; i < kFxTab; i += 64) tabG[i] = lds[i]; })
+    if (b.pfx > 0 && seg != blk - b.pfx) wave_copy(blk - b.pfx, seg, b.pfx);
+    return b;
+}
+
+// ---- many blocks with history outside the block: one wave per block, the whole block in ONE exact run of the kExt parse (the
+// bulk flavour: no pieces, no rounds, no guessed states).  The segment is laid in front of the block unless it lies there already,
+// the table liblz4 starts the block with is built straight into the wave's LDS table (fxl_table; no trip through global memory),
+// and the parser takes it as it stands (kPrimed).  Records and lastAnchor are the staged path's, in the block's coordinates; the
+// kSeg emit stage runs behind it with b->pfx.  Returns the records (kSeqEngineFailed: the run did not reach the block's end, which
+// an exact run always does); a block that is not this path's (b->pfx < 0: <= 4 KiB under a dictionary context) has none.
+DEV int l1x_block(uint8_t* blk, int n, int mode, const uint8_t* __restrict__ seg, int segLen, const uint32_t* __restrict__ dictTable,
+                  uint64_t* __restrict__ rec, int seqCap, int* lastAnchor, FxlBlk* b, uint32_t* lds)
+{
+    *b = fxl_blk_of(mode, segLen);
+    *lastAnchor = 0;
+    if (b->pfx < 0) return 0;
+    if (b->pfx > 0 && seg != blk - b->pfx) { wave_copy(blk - b->pfx, seg, b->pfx); WAVE_FENCE(); }
+    fxl_table(blk, n, mode, blk - b->pfx, b->pfx, dictTable, lds);
+    FxRun run;
+    run.entryAnchor = -1; run.entryTab = nullptr; run.cp = -1; run.cpTab = nullptr; run.cpAnchor = -1;
+    run.end = b->bs + n; run.outTab = nullptr; run.outAnchor = -1;          // (no post-match state lies at the block's end: nothing is saved)
+    run.seqCap = seqCap; run.fin = 0; run.bs = b->bs;
+    const int ns = wave_parse_l1_tt<false, 2, true, true, true>(blk - b->bs, b->bs + n, lds, rec, lastAnchor, nullptr, &run);
+    if (n >= kMinLength && !run.fin) return kSeqEngineFailed;
+    return ns <= seqCap ? ns : kSeqEngineFailed;
 }
 
 }  // namespace plz4

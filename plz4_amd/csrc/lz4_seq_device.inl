@@ -37,6 +37,7 @@ enum : int {
 // per-block results of the parse / scan stages
 struct SeqInfo { int32_t nseq; int32_t lastAnchor; int32_t total; int32_t stored; };
 enum : int { kSeqEngineFailed = -2 };     // SeqInfo::nseq of a block whose parser had no input to trust (-1: not sized for; both: no records)
+enum : int { kSeqElsewhere = -3 };        // ... of a block whose bytes were made by another encoder and lie where its records would (total: how many; no records)
 
 // entries a block of n bytes can need: every sequence consumes at least MINMATCH input bytes.  The parser's array has one more
 // (a dump entry at index seq_capacity(n)).
@@ -250,15 +251,18 @@ DEV void fx_save_table(const void* tab, uint32_t* g)
 // (the dictSmall test of lz4.c:1085-1087 has nothing left to reject) -- the block is [run->bs, n), and entries are index << 9 | tag
 // (indices reach 4 MiB + 64 KiB).  Records keep the block's coordinates (index - bs): a match into the segment has offset > position.
 // The catch-up (lowLimit, lz4.c:1065-1079) belongs to the emit stage.
-template <bool U16, int kLdsWin = 0, bool kPiece = false, bool kExt = false>
+// kPrimed (with kExt): `tab` already holds the table the block starts with -- the wave that parses built it there (l1x_block,
+// lz4_fx_device.inl) -- and is left as it is.
+template <bool U16, int kLdsWin = 0, bool kPiece = false, bool kExt = false, bool kPrimed = false>
 DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab, uint64_t* __restrict__ seq, int* lastAnchor, uint8_t* scr = nullptr,
                          FxRun* run = nullptr)
 {
     static_assert(!kExt || (kPiece && !U16), "the external-segment flavour is a piece parse with byU32 tables");
+    static_assert(!kPrimed || kExt, "a table primed in place is the external-segment flavour's");
     const int      sh      = U16 ? 0 : (kExt ? 9 : 10);
     const int      bs      = kExt ? run->bs : 0;          // the block's first position
     const uint32_t tagMask = (1u << sh) - 1u;
-    {   // fresh table per block (LZ4_initStream, lz4.c:1384): every slot = "position 0"
+    if (!kPrimed) {   // fresh table per block (LZ4_initStream, lz4.c:1384): every slot = "position 0"
         const uint32_t e0 = (sh && n >= 4 && !kExt) ? (seq_tag(UNI(ld32u(src))) & tagMask) : 0u;
         uint32_t* t = (uint32_t*)tab;
         if (kPiece && run->entryTab) { const uint32_t* g = run->entryTab; LANES({ for (int i = LANE; i < kHashBytes / 4; i += 64) t[i] = g[i]; }) }

@@ -306,7 +306,10 @@ template <bool kBack, bool kSeg = false> __device__ __forceinline__ void l1_writ
         if (wave == 0 && (threadIdx.x & 63u) == 0)                                    // the size word, stored iff the encoder returned 0 (blk.go:78-92)
             st32u(out - 4, inf.total ? ((uint32_t)inf.total & 0x7FFFFFFFu) : (0x80000000u | ((uint32_t)n & 0x7FFFFFFFu)));
     }
-    if (inf.total > 0) {
+    if (kSeg && inf.nseq == kSeqElsewhere && inf.total > 0) {
+        // (a frame body's block <= 4 KiB under a dictionary context: k_fxl_small has left its bytes where its records would lie)
+        if (wave == 0) wave_copy(out, (const uint8_t*)(a.l1Seq + (int64_t)i * a.l1SeqStride), inf.total);
+    } else if (inf.total > 0) {
         const uint64_t* seq = a.l1Seq + (int64_t)i * a.l1SeqStride;
         const int nChunks = (inf.nseq + kSeqChunk - 1) / kSeqChunk;
         for (int c = wave; c < (nChunks ? nChunks : 1); c += nW)
@@ -349,8 +352,8 @@ __device__ __forceinline__ int encode_block_primed(const uint8_t* s, int n, uint
     int segLen = 0;
     if (dc.mode == kDictLoad || dc.mode == kDictCtxCopy) {
         segLen = dc.dictSize;
-        wave_copy(const_cast<uint8_t*>(s) - segLen, dc.dict, segLen);
-        WAVE_FENCE();
+        // (a segment that lies there already -- the tail of the block before in contiguous plaintext -- stays: its neighbours read it)
+        if (dc.dict != s - segLen) { wave_copy(const_cast<uint8_t*>(s) - segLen, dc.dict, segLen); WAVE_FENCE(); }
     }
     return wave_encode_block_ext(s, n, out, cap, dc.mode, segLen, dc.dictTable, lds);
 }
@@ -487,8 +490,18 @@ __global__ __launch_bounds__(64) void k_fxl_small(CodecArgs a)
             if ((threadIdx.x & 63u) == 0) a.result[gi] = r;
             continue;
         }
+        // records back to back (a.bodyOff): this launch runs between k_l1_scan and the scan over the records' lengths.  The block's
+        // bytes go where its records would lie (it has none; bsz + 8 <= 8 bytes per possible sequence), its length to result, and
+        // the emit stage's write and finish kernels lay it down as any other record (kSeqElsewhere).
         uint8_t* rec = a.dst + (int64_t)gi * a.dstStride;
-        int      c    = wave_encode_block_dict(s, n, rec + 4, a.bsz, dc, lds);
+        int      c    = wave_encode_block_dict(s, n, a.bodyOff ? (uint8_t*)(a.l1Seq + (int64_t)i * a.l1SeqStride) : rec + 4, a.bsz, dc, lds);
+        if (a.bodyOff) {
+            if ((threadIdx.x & 63u) == 0) {
+                SeqInfo inf; inf.nseq = kSeqElsewhere; inf.lastAnchor = 0; inf.total = c; inf.stored = (c == 0); a.l1Info[i] = inf;
+                a.result[gi] = (c ? c : n) + 4 + (a.blockChecksum ? 4 : 0);
+            }
+            continue;
+        }
         uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
         if (c == 0) { wave_copy(rec + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
         int len = c + 4;
@@ -500,6 +513,37 @@ __global__ __launch_bounds__(64) void k_fxl_small(CodecArgs a)
         }
         if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[gi] = len; }
     }
+}
+
+// ---- many level-1 blocks with history outside the block (a linked frame or a dictionary frame from device-resident plaintext):
+// the staged design with one wave per block, pulled from the block queue like k_l1_parse.  Each block is one exact whole-block run
+// of the kExt parser (l1x_block, lz4_fx_device.inl): the segment in front of the block (copied only where it does not lie there
+// already), the starting table built in the wave's own LDS table, the records into the level-1 workspace; xb[i] tells the kSeg emit
+// stage (k_fxl_sizes / k_fxl_write) the segment's bytes.  W waves per workgroup, each with its own 16 KiB table, never synchronised
+// (ENC_WAVE_TABLE): a whole-block run has none of the piece flow's live state (k_fxl_piece: 256 VGPRs + 94 AGPRs, one wave per SIMD)
+// and fits the register budget of ten waves per CU (W = 10: 85 VGPRs, no AGPRs, no scratch), so the LDS tables are what bounds it,
+// as with k_l1_parse.
+template <int W> __global__ __launch_bounds__(64 * W) void k_l1x_parse(CodecArgs a, FxlBlk* xb, unsigned long long* cnt)
+{
+    ENC_WAVE_TABLE(lds);
+    int parsed = 0;                                                          // (plz4hip_ctx_counters [8])
+    for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
+        const int gi = a.blk0 + i;
+        const int n  = block_len(a, gi);
+        int lastAnchor = 0, nseq = -1;                                       // -1: a block the workspace was not sized for
+        FxlBlk b; b.pfx = -2; b.bs = 0;
+        if (n >= 0 && n <= a.l1MaxLen) {
+            const DictEnc dc = fxl_dict_of(a, gi, n);
+            nseq = l1x_block(const_cast<uint8_t*>(a.src) + (int64_t)gi * a.srcStride, n, dc.mode, dc.dict, dc.dictSize, dc.dictTable,
+                             a.l1Seq + (int64_t)i * a.l1SeqStride, (int)a.l1SeqStride - 1, &lastAnchor, &b, lds);
+        }
+        if ((threadIdx.x & 63u) == 0) {
+            SeqInfo inf; inf.nseq = nseq; inf.lastAnchor = lastAnchor; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf;
+            xb[i] = b;
+        }
+        parsed += (b.pfx >= 0 && nseq >= 0);
+    }
+    if (parsed && (threadIdx.x & 63u) == 0) atomicAdd(&cnt[8], (unsigned long long)parsed);
 }
 
 // One record against an optional dictionary; shared by the independent and the linked decode kernels.
@@ -619,7 +663,7 @@ __device__ __forceinline__ HcDict hc_dict_of(const CodecArgs& a, int i, int n, c
     }
     if (segLen >= 0) {
         d.mode = kHcExt; d.len = segLen;
-        if (segLen > 0) { wave_copy(const_cast<uint8_t*>(s) - segLen, seg, segLen); WAVE_FENCE(); }
+        if (segLen > 0 && seg != s - segLen) { wave_copy(const_cast<uint8_t*>(s) - segLen, seg, segLen); WAVE_FENCE(); }   // (in place already: contiguous plaintext)
     }
     return d;
 }
@@ -1576,22 +1620,26 @@ struct plz4hip_ctx {
     hipStream_t  dxHashStream = nullptr; hipEvent_t evDxFork = nullptr, evDxHash = nullptr;   // records: the block checksums beside the decode
     // the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): pieces' states and records, sized per call
     DeviceBuffer fx;  StreamOrder fxOrder;
+    // plz4hip_dev_encode_body_ex on the one-kernel encoder (PLZ4HIP_L1X=0, PLZ4HIP_L1_FUSED): its records before they are compacted
+    DeviceBuffer xstage;  StreamOrder xstageOrder;
     // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
     // parsed more than once, [3] blocks answered by the few-block decoder, [4] blocks with history outside the block (dictionary,
     // linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of a call cut into groups),
     // [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block (dictionary, linked)
-    // encoded by the few-block level-1 path (a subset of [0])
+    // encoded by the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the bulk staged
+    // route (k_l1x_parse)
+    static constexpr int kCounters = 9;
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
     // plz4hip_dev_decode_records_ex: the chainFirst of the last call (int32 each), which that job's kernels read
     DeviceBuffer chainCopy;  StreamOrder chainOrder;
     struct Owned { DeviceBuffer* buf; StreamOrder* order; bool trimmed; };     // trimmed: plz4hip_ctx_trim gives it back
-    std::array<Owned, 9> owned()
+    std::array<Owned, 10> owned()
     {
         return {{{&hc, &hcOrder, true}, {&h12, &hcOrder, true}, {&hcPfx, &hcOrder, false}, {&l1[0], &l1Order[0], true},
                  {&l1[1], &l1Order[1], true}, {&dx, &dxOrder, true}, {&fx, &fxOrder, true}, {&lenCopy, &lenOrder, false},
-                 {&chainCopy, &chainOrder, false}}};
+                 {&chainCopy, &chainOrder, false}, {&xstage, &xstageOrder, true}}};
     }
 };
 
@@ -1713,10 +1761,10 @@ int grid_for(int nBlocks, int resident) { return nBlocks < resident ? nBlocks : 
 // workgroups of the level-1 encoder kernels (kEncWavesPerWg waves each) for nBlocks blocks and `resident` resident waves
 // Launch of a level-1 encoder kernel: ten-wave workgroups when the call has more blocks than nine-per-CU one-wave workgroups
 // could hold at once, one-wave workgroups otherwise.
-#define ENC_LAUNCH(kernel, nBlocks, c, s, a) do { \
+#define ENC_LAUNCH(kernel, nBlocks, c, s, ...) do { \
         const int waves_ = grid_for((nBlocks), (c)->encWaves); \
-        if (waves_ > 9 * (c)->cus) hipLaunchKernelGGL(kernel<kEncWavesPerWg>, dim3((waves_ + kEncWavesPerWg - 1) / kEncWavesPerWg), dim3(64 * kEncWavesPerWg), 0, s, a); \
-        else hipLaunchKernelGGL(kernel<1>, dim3(waves_), dim3(64), 0, s, a); \
+        if (waves_ > 9 * (c)->cus) hipLaunchKernelGGL(kernel<kEncWavesPerWg>, dim3((waves_ + kEncWavesPerWg - 1) / kEncWavesPerWg), dim3(64 * kEncWavesPerWg), 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel<1>, dim3(waves_), dim3(64), 0, s, __VA_ARGS__); \
     } while (0)
 
 bool is_hc_level(int level) { return level >= 2 && level <= 12; }        // every row of the level table (lz4hc.c:92-106): mid, hash chain, optimal
@@ -1834,7 +1882,7 @@ bool use_h12(const CodecArgs& a, int maxLen) { return a.level >= 12 && !a.hcEx &
 bool use_lazy(const CodecArgs& a, int maxLen) { return a.level >= 3 && (a.level <= 11 || getenv("PLZ4HIP_HC12_LAZY") != nullptr) && !a.hcEx && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_LAZY_OFF") == nullptr; }
 
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined = nullptr,
-              const CodecArgs* rider = nullptr, bool hist = false);
+              const CodecArgs* rider = nullptr, bool hist = false, bool l1x = false);
 
 // Enqueue one HC call of nb blocks (a: everything but queue / workspace filled in) on s.  rawMode: LZ4 blocks, else records.
 int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked);
@@ -2149,6 +2197,17 @@ bool fxl_wanted(int nb, int maxLen)
     return nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_L1_FUSED") == nullptr;
 }
 
+// Whether a level-1 call of MANY blocks with history outside the block, from device-resident plaintext, takes the staged design
+// (k_l1x_parse + the kSeg emit stage) or the one-kernel encoder k_encode_rec_dict: PLZ4HIP_L1X (read per call; 0: the one-kernel
+// encoder, anything else: staged).  The default is a measurement: profiles/l1x_rate.json, DESIGN 3.3.
+constexpr bool kL1xDefault = true;
+bool l1x_on()
+{
+    if (getenv("PLZ4HIP_L1_FUSED") != nullptr) return false;
+    if (const char* v = getenv("PLZ4HIP_L1X")) return atoi(v) != 0;
+    return kL1xDefault;
+}
+
 // rawMode: LZ4 blocks (result = bytes or 0), else records.  Blocks up to 4 MiB run in stages (lz4_seq_device.inl): the
 // workspace holds 8 bytes per possible sequence -- 2 bytes per input byte -- of one group of blocks; a call that does not fit
 // the memory set aside (half of what is free; PLZ4HIP_L1_BUDGET_GIB) runs in groups of equal size.  ws: the workspace to use
@@ -2161,11 +2220,16 @@ bool fxl_wanted(int nb, int maxLen)
 // hist: the blocks have history outside the block (a: dictionary / linked fields filled in, 64 KiB of room in front of every input
 // block).  Such a call is here for the few-block path's external-segment flavour (fxl_wanted has said yes); whenever that path
 // cannot be had -- no workspace, the fused kernels -- it runs k_encode_rec_dict / k_encode_raw_dict, one wave per block, as ever.
+// l1x (with hist; the device-resident entry points plz4hip_dev_encode_records_ex / _body_ex): fxl_wanted is asked here, and a call
+// that is not the few-block path's takes the staged design with one wave per block (k_l1x_parse, then the kSeg emit stage); the
+// workspace then carries one FxlBlk per block of a group behind the records.  Records straight into a frame body (a.bodyOff) have
+// no one-kernel form: PLZ4HIP_E_NOMEM when the workspace cannot be had.
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined,
-              const CodecArgs* rider, bool hist)
+              const CodecArgs* rider, bool hist, bool l1x)
 {
     hipError_t e;
     const auto dict_kernels = [&]() -> int {
+        if (a.bodyOff) return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
         a.blk0 = 0; a.nBlocks = nb;
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         if (rawMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a); else ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
@@ -2191,10 +2255,12 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         ws = &c->l1[wsi];
     }
     bool fused = maxLen <= 0 || maxLen > kSeqMaxBlock || getenv("PLZ4HIP_L1_FUSED") != nullptr;
+    if (hist && l1x && !l1x_on() && !fxl_wanted(nb, maxLen)) fused = true;              // (the one-kernel encoder: no workspace)
     const size_t seqStride = round_up((size_t)(maxLen > 0 ? maxLen : 0) / 4 + 3, 64);     // + the dump entry (lz4_seq_device.inl)
     const int    maxChunks = (int)((seqStride + kSeqChunk - 1) / kSeqChunk);
-    const size_t perBlock  = sizeof(SeqInfo) + (size_t)maxChunks * 8 + seqStride * 9;
-    const auto need_for = [&](int per) { return round_up((size_t)per * sizeof(SeqInfo), 256) + 2 * round_up((size_t)per * maxChunks * 4, 256) + (size_t)per * seqStride * 9; };
+    const size_t perBlock  = sizeof(SeqInfo) + (size_t)maxChunks * 8 + seqStride * 9 + (l1x ? sizeof(FxlBlk) : 0);
+    const auto need_for = [&](int per) { return round_up((size_t)per * sizeof(SeqInfo), 256) + 2 * round_up((size_t)per * maxChunks * 4, 256) + round_up((size_t)per * seqStride * 9, 8)
+                                                + (l1x ? (size_t)per * sizeof(FxlBlk) : 0); };
     int per = nb;
     if (shared && !fused && wsi != 0 && !ws->d && c->l1Refused > 0) { c->l1Refused--; wsi = 0; ws = &c->l1[0]; }   // (refused a moment ago)
     if (shared && !fused && wsi != 0 && !ws->d) {
@@ -2228,8 +2294,8 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, fused ? " (fused)" : "");
     }
     if (fused && hist) return dict_kernels();
-    if (fused && mid) { *midDeclined = true; return PLZ4HIP_OK; }
     if (fused && a.bodyOff) return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
+    if (fused && mid) { *midDeclined = true; return PLZ4HIP_OK; }            // (behind the refusal above: the one-thread parsers write staged records too)
     if (fused) {
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         if (rawMode) ENC_LAUNCH(k_encode_raw, nb, c, s, a); else ENC_LAUNCH(k_encode_rec, nb, c, s, a);
@@ -2255,7 +2321,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     {
         int fxMax = kFxMaxBlocks;
         if (const char* v = getenv("PLZ4HIP_FX_MAX_BLOCKS")) fxMax = atoi(v);
-        if (!mid && !rider && nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock) {
+        if (!mid && !rider && nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock && (!l1x || fxl_wanted(nb, maxLen))) {
             int pk = 64, wk = 64;
             if (const char* v = getenv("PLZ4HIP_FX_PIECE_KIB")) { const int x = atoi(v); if (x >= 1 && x <= 4096) pk = x; }
             if (const char* v = getenv("PLZ4HIP_FX_WARMUP_KIB")) { const int x = atoi(v); if (x >= 0 && x <= 4096) wk = x; }
@@ -2276,13 +2342,14 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             }
         }
     }
-    if (hist && !useFx) return dict_kernels();
+    if (hist && !useFx && !(l1x && l1x_on())) return dict_kernels();
+    if (hist && !useFx) xb = (FxlBlk*)(a.l1Bk + round_up((size_t)per * seqStride, 8));       // (the bulk route: behind the group's records)
     for (int g0 = 0; g0 < nb; g0 += per) {
         const int ng = nb - g0 < per ? nb - g0 : per;
         a.blk0 = g0; a.nBlocks = ng;
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         const bool signals = !mid && !getenv("PLZ4HIP_EXP_NO_GATE");            // (the level-1 parse and the duplex launch)
-        if (useFx) a.gate = nullptr;                                            // (neither waits for nor signals the gate)
+        if (useFx || hist) a.gate = nullptr;                                    // (neither waits for nor signals the gate)
         else if (signals) {
             // (only behind a launch that fills the device: the parse launches of the host-buffer calls' chunks -- a third of the
             // wave slots each -- are meant to share it, and behind the gate they would run one after the other: 2560 blocks through
@@ -2311,6 +2378,10 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
             for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fx_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, r);
             hipLaunchKernelGGL(k_fx_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx);
+        }
+        else if (hist) {
+            // one wave per block, every block one exact run
+            ENC_LAUNCH(k_l1x_parse, ng, c, s, a, xb, c->d_counters);
         }
         else if (rider && g0 == 0) {
             // workgroups: what the device holds at once, unless neither role has that much to do
@@ -2352,12 +2423,14 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         else if (mid) hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_l1_sizes<true>, dim3(wg, ng), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
+        const bool ctxSmall = hist && a.dictLen >= 8;                           // (the blocks <= 4 KiB under the context: k_fxl_small)
+        if (ctxSmall && a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);   // (their lengths, before the records are placed)
         if (a.bodyOff) hipLaunchKernelGGL(k_scan_from, dim3(1), dim3(1024), 0, s, (const int32_t*)(a.result + g0), a.bodyOff + g0, ng, g0 == 0 ? 1 : 0);
         if (hist) hipLaunchKernelGGL(k_fxl_write, dim3(wg, ng), dim3(256), 0, s, a, (const FxlBlk*)xb);
         else if (mid) hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_l1_write<true>, dim3(wg, ng), dim3(256), 0, s, a);
         if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 3) / 4), dim3(256), 0, s, a);
-        if (hist && a.dictLen >= 8) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);   // (the blocks <= 4 KiB under the context)
+        if (ctxSmall && !a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, job.leave());
@@ -2575,8 +2648,8 @@ int plz4hip_ctx_create(int device, plz4hip_ctx** out)
     // four hardware queues -- the staging slots of the host-buffer calls end up sharing queues and their chunks stop overlapping:
     // 2560 blocks 470 -> 790 ms, found with scripts/host_rate_ab.py)
     if (e == hipSuccess) e = zero_sync(c, c->d_gate, 256);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, 64);
-    if (e == hipSuccess) e = zero_sync(c, c->d_counters, 64);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_counters, plz4hip_ctx::kCounters * 8);
+    if (e == hipSuccess) e = zero_sync(c, c->d_counters, plz4hip_ctx::kCounters * 8);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device);
     int encPer = 0, decPer = 0;
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&encPer, k_encode_rec<kEncWavesPerWg>, 64 * kEncWavesPerWg, 0);
@@ -2643,11 +2716,12 @@ int plz4hip_ctx_counters(plz4hip_ctx* c, int64_t* out, int n)
     if (!c || n < 0 || (n > 0 && !out)) return PLZ4HIP_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
-    unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    constexpr int kCounters = plz4hip_ctx::kCounters;
+    unsigned long long v[kCounters] = {};
     HIPCHK(c, hipDeviceSynchronize());                                      // (the ctx's work runs on the callers' streams)
     HIPCHK(c, copy_sync(c, v, c->d_counters, sizeof v, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n && i < 8; ++i) out[i] = (int64_t)v[i];
-    return 8;
+    for (int i = 0; i < n && i < kCounters; ++i) out[i] = (int64_t)v[i];
+    return kCounters;
 }
 
 const char* plz4hip_last_error(const plz4hip_ctx* c)
@@ -2943,6 +3017,104 @@ int plz4hip_dev_duplex_body(plz4hip_ctx* c, const void* src, int64_t srcBytes, i
         return PLZ4HIP_OK;
     }
     return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nDecBlocks > 0 ? &d : nullptr);
+}
+
+// ---- records of blocks with history outside the block (linked blocks, a dictionary) from device-resident plaintext:
+// plz4hip_encode_records_ex for a producer whose plaintext is in device memory.  The kernels' one layout rule -- the external segment
+// lies immediately in front of the block -- holds by itself for a linked frame over contiguous plaintext (srcStride == bsz: block i's
+// segment is the tail of block i - 1); elsewhere the caller leaves 64 KiB of scratch in front of the block and the kernels lay the
+// segment there (block 0 of a contiguous call under a dictionary / after a prevTail that does not end at src; every block of a
+// gapped call).
+static int encode_ex_args(plz4hip_ctx* c, CodecArgs& a, const void* src, int64_t srcBytes, int64_t srcStride, int bsz, int level,
+                          int blockChecksum, int linked, const plz4hip_dict* dict, const void* prevTail, int prevTailLen,
+                          int32_t* recLen, int* nBlocksOut, const char* who)
+{
+    if (!c || srcBytes < 0 || (srcBytes > 0 && !src) || bsz <= 0 || !recLen) return fail(c, PLZ4HIP_E_ARG, who);
+    if (!linked && !dict) return fail(c, PLZ4HIP_E_ARG, "independent blocks without a dictionary: plz4hip_dev_encode_records / plz4hip_dev_encode_body");
+    if (srcStride != (int64_t)bsz && srcStride < (int64_t)bsz + 65536) return fail(c, PLZ4HIP_E_ARG, "srcStride: bsz (contiguous) or at least bsz + 65536 (64 KiB of scratch in front of every block)");
+    if (!linked && srcStride == (int64_t)bsz) return fail(c, PLZ4HIP_E_ARG, "independent blocks under a dictionary need 64 KiB of scratch in front of every block (srcStride >= bsz + 65536)");
+    if (prevTailLen > 65536 || (prevTailLen > 0 && !prevTail)) return fail(c, PLZ4HIP_E_ARG, "prevTail: a device pointer and at most 64 KiB");
+    if (linked && prevTailLen > 0) {
+        // laid at [src - prevTailLen, src) unless it is those bytes already: a tail that overlaps that range otherwise would be copied over itself
+        const uintptr_t t0 = (uintptr_t)prevTail, t1 = t0 + (uintptr_t)prevTailLen, s1 = (uintptr_t)src, s0 = s1 - (uintptr_t)prevTailLen;
+        if (t1 != s1 && t0 < s1 && t1 > s0) return fail(c, PLZ4HIP_E_ARG, "prevTail must end exactly at src or lie outside the bytes it is laid at, [src - prevTailLen, src)");
+    }
+    const int64_t nb64 = (srcBytes + bsz - 1) / bsz;
+    if (nb64 > 0x7FFFFFFF) return fail(c, PLZ4HIP_E_ARG, "too many blocks");
+    *nBlocksOut = (int)nb64;
+    a.src = (const uint8_t*)src; a.srcStride = srcStride; a.srcBytes = srcBytes; a.bsz = bsz;
+    a.result = recLen; a.nBlocks = *nBlocksOut; a.blockChecksum = blockChecksum;
+    a.dictLen = -1; a.prevTailLen = -1;
+    a.linked = linked ? 1 : 0;
+    if (dict) { a.dict = dict->d_bytes; a.dictLen = dict->len; a.dictTable = dict->d_table; }
+    if (linked && prevTailLen >= 0) { a.prevTail = (const uint8_t*)prevTail; a.prevTailLen = prevTailLen; }
+    if (is_hc_level(level)) {
+        a.level = level; a.hcEx = 1;
+        if (dict) {
+            const uint8_t* t = dict->d_hc + (level <= 2 ? 0 : (size_t)kHcWorkBytes);
+            a.hcDictHash = (const uint32_t*)t; a.hcDictChain = (const uint16_t*)(t + kHcHashEntries * 4);
+        }
+    }
+    return PLZ4HIP_OK;
+}
+
+int plz4hip_dev_encode_records_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes, int64_t srcStride, int bsz, int level,
+                                  int blockChecksum, int linked, const plz4hip_dict* dict, const void* prevTail, int prevTailLen,
+                                  void* stage, int32_t* recLen, void* stream)
+{
+    if (level != 1 && !is_hc_level(level)) return fail(c, PLZ4HIP_E_UNSUPPORTED, "levels 1..12 are built");
+    CodecArgs a{}; int nBlocks = 0;
+    if (int rc = encode_ex_args(c, a, src, srcBytes, srcStride, bsz, level, blockChecksum, linked, dict, prevTail, prevTailLen, recLen, &nBlocks,
+                                "plz4hip_dev_encode_records_ex: bad argument")) return rc;
+    if (!stage) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_encode_records_ex: bad argument");
+    if (nBlocks == 0) return PLZ4HIP_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    a.dst = (uint8_t*)stage; a.dstStride = plz4hip_dev_stage_stride(bsz);
+    if (is_hc_level(level)) return launch_hc(c, s, a, nBlocks, bsz, 0);
+    return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true);
+}
+
+int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes, int64_t srcStride, int bsz, int level,
+                               int blockChecksum, int linked, const plz4hip_dict* dict, const void* prevTail, int prevTailLen,
+                               void* body, int64_t bodyCap, int64_t* recOff, int32_t* recLen, void* stream)
+{
+    if (level != 1 && level != 2) return fail(c, PLZ4HIP_E_UNSUPPORTED, "plz4hip_dev_encode_body_ex: levels 1 and 2 (the others: plz4hip_dev_encode_records_ex + plz4hip_dev_compact_records)");
+    CodecArgs a{}; int nBlocks = 0;
+    if (int rc = encode_ex_args(c, a, src, srcBytes, srcStride, bsz, level, blockChecksum, linked, dict, prevTail, prevTailLen, recLen, &nBlocks,
+                                "plz4hip_dev_encode_body_ex: bad argument")) return rc;
+    if (bsz > kSeqMaxBlock || !body || bodyCap <= 0 || !recOff) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_encode_body_ex: bad argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (nBlocks == 0) { HIPCHK(c, hipMemsetAsync(recOff, 0, sizeof(int64_t), s)); return PLZ4HIP_OK; }
+    a.dst = (uint8_t*)body; a.dstStride = 0; a.bodyOff = recOff; a.bodyCap = bodyCap;
+    if (level == 2) {
+        // (a block <= 4 KiB under a dictionary context is written by the one-thread parser behind the emit stage, into a staged record)
+        const int lastLen = (int)(srcBytes - (int64_t)(nBlocks - 1) * bsz);
+        // (hc_dict_of: under ANY attached dictionary, whatever its length)
+        const bool ctxSmall = dict && (linked ? (a.prevTailLen < 0 && (nBlocks == 1 ? lastLen : bsz) <= 4096) : (lastLen <= 4096 || bsz <= 4096));
+        if (ctxSmall) return fail(c, PLZ4HIP_E_UNSUPPORTED, "plz4hip_dev_encode_body_ex: level 2 with a block <= 4 KiB under a dictionary context (plz4hip_dev_encode_records_ex + plz4hip_dev_compact_records)");
+        return launch_hc(c, s, a, nBlocks, bsz, 0);
+    }
+    if (!fxl_wanted(nBlocks, bsz) && !l1x_on()) {
+        // the one-kernel encoder writes staged records: a staging area of the ctx's, then the compaction of plz4hip_dev_compact_records
+        const int64_t stride = plz4hip_dev_stage_stride(bsz);
+        HIPCHK(c, c->xstageOrder.wait(s));
+        bool refused = false;  HIPCHK(c, c->xstage.reserve((size_t)nBlocks * (size_t)stride, c->xstageOrder, &refused));
+        if (refused) return fail(c, PLZ4HIP_E_NOMEM, "plz4hip_dev_encode_body_ex: the one-kernel encoder's staging area");
+        MarkOnExit job;  job.arm(c->xstageOrder, s);
+        a.dst = c->xstage.d; a.dstStride = stride; a.bodyOff = nullptr; a.bodyCap = 0;
+        if (int rc = launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true)) return rc;
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, (const int32_t*)recLen, recOff, nBlocks);
+        hipLaunchKernelGGL(k_move_records, dim3(nBlocks, move_slices((int)stride)), dim3(256), 0, s,
+                           (const uint8_t*)c->xstage.d, (const int64_t*)nullptr, stride, (const int32_t*)recLen, (const int64_t*)recOff, (uint8_t*)body, bodyCap);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, job.leave());
+        return PLZ4HIP_OK;
+    }
+    return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true);
 }
 
 // ---------------------------------------------------------------------------------------- host-buffer API
