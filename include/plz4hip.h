@@ -32,6 +32,14 @@
  * of a quarter of the device memory that is free when the call arrives, at most 64 GiB; a call whose blocks do not fit runs in
  * groups.  A caller that owns the GPU raises the budget with PLZ4HIP_HC_BUDGET_GIB (these kernels live on blocks in flight).
  * With a dictionary and / or linked blocks the HC levels run the same designs over segment + block (strides for 4 MiB + 64 KiB).
+ * A block of at most 4 KiB under an attached dictionary (compress_batch_dict, encode_records_ex, dev_encode_records_ex, the host
+ * layer's Writer with a dictionary: a short payload or a short last block) keeps its own empty tables and searches the dictionary
+ * context's behind them (lz4hc.c:1442-1463).  At levels 2..12 such a block is one wavefront's: its chain as lists in 17 KiB of LDS
+ * (level 2: its two direct-mapped tables, compacted to the hashes the block has, in 21 KiB),
+ * the dictionary's chain as lists built once by plz4hip_dict_create (256 KiB per dictionary), one candidate per lane, no workspace
+ * in device memory at levels 3..9 (levels 10..12: a price table, level 2: the sequence records, per wave out of the HC workspace); all such blocks of a call are
+ * one launch off the block queue.  PLZ4HIP_HCX=0 (read per call) keeps the one-thread parsers.  Bytes and results are the same
+ * either way.
  * A DECODE call of few blocks (decompress_batch, decode_records and their dev_ forms, up to PLZ4HIP_DX_MAX_BLOCKS = 128 blocks of up
  * to 4 MiB + 8 of output; 0 turns it off) is cut across the whole chip and keeps 8 bytes per input byte + 4 per output byte of
  * the call's blocks (about 50 MiB per 4 MiB block) until plz4hip_ctx_trim; results and error codes are LZ4_decompress_safe's
@@ -114,7 +122,8 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
  * outside the block (dictionary, linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of
  * a call cut into groups), [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block encoded by
  * the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the staged one-wavefront-per-block
- * route of plz4hip_dev_encode_records_ex / _body_ex (not those the one-kernel encoder took).  Returns how many counters there are (9),
+ * route of plz4hip_dev_encode_records_ex / _body_ex (not those the one-kernel encoder took), [9] blocks of at most 4 KiB under a
+ * dictionary context encoded by the wave-wide HC parser (levels 2..12).  Returns how many counters there are (10),
  * or PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
@@ -166,11 +175,20 @@ int plz4hip_decode_records(plz4hip_ctx* ctx, int nBlocks,
 /* ---------------------------------------------------------------------------------------------------------
  * B'. Dictionaries and linked blocks (levels 1..12; SURVEY.md §8a-11, BASELINE config 5).
  *    plz4hip_dict == clz4.DictCtx + clz4.DictCtxHC (clz4.go:96-147: private copy of the last 64 KiB, the LZ4_loadDictSlow
- *                   table for level 1, the LZ4_loadDictHC tables for level 2 (lz4mid) and for levels 3..12 (hash chain)).
+ *                   table for level 1, the LZ4_loadDictHC tables for level 2 (lz4mid) and for levels 3..12 (hash chain)),
+ *                   and the hash chain's positions once more as ascending runs per hash (256 KiB, built on the host by
+ *                   plz4hip_dict_create, freed by plz4hip_dict_destroy): what the wave-wide parser of small blocks reads
+ *                   one candidate per lane.  About 900 KiB of device memory per dictionary in all.
  *    *_batch_dict : level 1: clz4.StreamIndieCtx.Compress (clz4.go:160-179); levels 2..12: clz4.StreamCtxHC.Compress
  *                   (clz4.go:191-209 -> LZ4_compress_HC_continue under an attached dictionary, lz4hc.c:1438-1461);
  *                   clz4.DecompressSafeWithDict (clz4.go:62-78) per block -- i.e. CompressBlock/DecompressBlock with
  *                   WithBlockDictionary (plz4_block.go:48-53).
+ *                   HC levels: a block of at most 4 KiB keeps its own empty tables and searches the dictionary context's
+ *                   behind them (usingDictCtxHc, lz4hc.c:1442-1463).  Every such block of a call -- here, in
+ *                   encode_records_ex and in dev_encode_records_ex (block 0 of a linked frame without prevTail included) --
+ *                   is one wavefront's, all of them one launch off the block queue; a call of nothing but such blocks is
+ *                   that launch alone.  Levels 3..12: chain as lists in 17 KiB of LDS; level 2: its two tables in 21 KiB.
+ *                   PLZ4HIP_HCX=0 (read per call): the one-thread parsers; same bytes.  Counter [9] counts them.
  *    encode_records_ex: `dict` = WithDictionary; `linked` = WithBlockLinked: block i>0 is primed with the last <= 64 KiB of
  *                   src[i-1] (async/writer.go:412-437 -> LZ4_loadDict, clz4.go:224-241; levels 2..12: LZ4_loadDictHC,
  *                   clz4.go:262-283); block 0 with prevTail when the batch continues a frame (prevTail == NULL: block 0

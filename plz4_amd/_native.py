@@ -430,7 +430,7 @@ class Engine:
         self._chk(self.L.plz4hip_ctx_trim(self.h))
 
     COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last", "dxl_groups_last",
-                "fxl_blocks", "l1x_blocks")
+                "fxl_blocks", "l1x_blocks", "hcx_blocks")
 
     def counters(self) -> dict:
         """plz4hip_ctx_counters (waits for the ctx's work): blocks encoded by the few-block level-1 path, its rounds in the last

@@ -53,6 +53,10 @@ struct HcWork {
     // in it, the first position of a hash flagged): the candidates of a chain are consecutive entries, so a search looks at up to
     // 63 of them at once, one per lane (hc_find_wider_lists).  Null: one candidate after the other.
     const uint32_t* rank; const uint32_t* list;
+    // A block of at most 4 KiB under a dictionary context (lz4hcx_device.inl): the same chain as 16-bit lists in the wave's LDS --
+    // xlist: the positions of every hash as one ascending run, xrank[q]: where q sits in it; the low 12 bits of an entry are the
+    // value, the upper four of the two entries of a position together its place in its run, saturated at 255.  Null elsewhere.
+    const uint16_t* xrank = nullptr; const uint16_t* xlist = nullptr;
 };
 enum : int { kHcHashEntries = 32768, kHcChainEntries = 65536, kHcOptNum = 4096, kHcTrailing = 3,
              kHcWorkBytes = kHcHashEntries * 4 + kHcChainEntries * 2 + (kHcOptNum + kHcTrailing + 1) * 16 };
@@ -89,14 +93,25 @@ DEV int hc_count(const uint8_t* a, const uint8_t* b, const uint8_t* limit)
     return (int)(a - s);
 }
 
+// the chain built up front: distance from position q to the previous position with its hash (0: none).  kX: out of the 16-bit
+// lists in LDS (a compile-time choice: the kernels of every other path are the code they were)
+template <bool kX> DEV uint32_t hc_pre_at(const HcState& s, uint32_t q)
+{
+    if (kX) {
+        const uint32_t r = s.w.xrank[q], e = s.w.xlist[r & 0xFFFu];
+        return ((r | e) >> 12) ? q - (s.w.xlist[(r & 0xFFFu) - 1u] & 0xFFFu) : 0u;
+    }
+    return s.w.pre[q];
+}
 // LZ4HC_Insert (lz4hc.c:781-802): chain every position below `pos`
+template <bool kX = false>
 DEV uint32_t hc_link(const HcState& s, uint32_t idx)       // chain table entry of index idx (lz4hc.c:228 DELTANEXTU16)
 {
-    if (s.w.pre) {
+    if (kX || s.w.pre) {
         // (an external segment's last three positions are never inserted, lz4hc.c:1660-1678: their entries of the freshly zeroed
         // table -- LZ4_loadDictHC starts from LZ4_initStreamHC, :1626-1653 -- stay 0; the chain swap may read them, :964-987)
         if (s.d.mode == kHcExt && (kHcBase + (uint32_t)s.pfx - 1u) - idx < 3u) return 0u;
-        const uint32_t d = s.w.pre[idx - kHcBase]; return d ? d : 65535u;
+        const uint32_t d = hc_pre_at<kX>(s, idx - kHcBase); return d ? d : 65535u;
     }
     return s.w.chain[idx & 0xFFFFu];
 }
@@ -169,8 +184,20 @@ DEV bool hc_protect(uint32_t prefixIdx, uint32_t mi) { return (uint32_t)((prefix
 // kept: no 2-byte pre-check (:940-960), the look-back may go down to the segment's first byte while a candidate in the block stops
 // at the block's (:933 vs :953), and the pattern analysis never lands on the segment's last three positions (LZ4HC_protectDictEnd,
 // :876-879, :1003-1060).
-template <bool kD = false>
-DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit, int longest, int nbSearches, bool patternAnalysis, bool chainSwap)
+// kX: the lists are the 16-bit ones in LDS of a block of at most 4 KiB (HcWork::xrank / xlist; never with kD).  attemptsLeft: when
+// given, the attempts the walk left over (what a dictionary context's chain is then read with, :1067).
+template <bool kX> DEV uint32_t hc_lists_rank(const HcState& s, uint32_t q) { return kX ? ((uint32_t)s.w.xrank[q] & 0xFFFu) : s.w.rank[q]; }
+// entry i of the lists (i < 0: in front of them): position | chain's first position << 31
+template <bool kX> DEV uint32_t hc_lists_entry(const HcState& s, int i)
+{
+    if (!kX) return i >= -8 ? s.w.list[i] : 0x80000000u;
+    if (i < 0) return 0x80000000u;
+    const uint32_t e = s.w.xlist[i], q = e & 0xFFFu;
+    return q | ((((e | (uint32_t)s.w.xrank[q]) >> 12) == 0u) ? 0x80000000u : 0u);
+}
+template <bool kD = false, bool kX = false>
+DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit, int longest, int nbSearches, bool patternAnalysis, bool chainSwap,
+                                int* attemptsLeft = nullptr)
 {
     const uint8_t* const src = s.src;
     const int pfxPos = kD ? s.pfx : 0;
@@ -191,8 +218,8 @@ DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit
     const bool useFw = iHigh - ip >= 12;
     const uint64_t ip64 = useFw ? ld64u(ip + 4) : 0ull;
     HcMatch out;
-    const uint32_t head = UNI((uint32_t)s.w.pre[pos]);
-    const uint32_t rank0 = UNI(s.w.rank[pos]);               // (requested with the head: one memory round trip)
+    const uint32_t head = UNI(hc_pre_at<kX>(s, (uint32_t)pos));
+    const uint32_t rank0 = UNI(hc_lists_rank<kX>(s, (uint32_t)pos));   // (requested with the head: one memory round trip)
     if (head) {
         uint32_t mi = ipIndex - head;                        // the current candidate ...
         int cursor = (int)rank0 - 1;                         // ... and where it sits in the list
@@ -202,7 +229,7 @@ DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit
             LV(uint32_t, q); LV(int, fl); LV(int, pat); LV(uint32_t, ent);
             {
                 const int curL = cursor;
-                LANES({ const uint32_t e = (curL - LANE >= -8) ? s.w.list[curL - LANE] : 0x80000000u; ent[I_] = e; q[I_] = e & 0x7FFFFFFFu; fl[I_] = (int)(e >> 31); })
+                LANES({ const uint32_t e = hc_lists_entry<kX>(s, curL - LANE); ent[I_] = e; q[I_] = e & 0x7FFFFFFFu; fl[I_] = (int)(e >> 31); })
             }
             LV(uint32_t, qn);
             LANES({ qn[I_] = SHFL(ent, LANE + 1) & 0x7FFFFFFFu; })
@@ -287,15 +314,15 @@ DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit
                         const int end = longest - kMinMatch + 1;
                         int step = 1, accel = 1 << 4;
                         LV(uint32_t, links);
-                        { const uint32_t mi0 = mi; LANES({ links[I_] = (LANE < end) ? hc_link(s, mi0 + (uint32_t)LANE) : 0u; }) }
+                        { const uint32_t mi0 = mi; LANES({ links[I_] = (LANE < end) ? hc_link<kX>(s, mi0 + (uint32_t)LANE) : 0u; }) }
                         for (int p2 = 0; p2 < end; p2 += step) {
-                            const uint32_t cd = p2 < 64 ? RL(links, p2) : hc_link(s, mi + (uint32_t)p2);
+                            const uint32_t cd = p2 < 64 ? RL(links, p2) : hc_link<kX>(s, mi + (uint32_t)p2);
                             step = (accel++ >> 4);
                             if (cd > distNext) { distNext = cd; chainPos = (uint32_t)p2; accel = 1 << 4; }
                         }
                         if (distNext > 1) {
                             if (distNext > mi || distNext >= 65535u) { walkEnds = true; break; }   // (a saturated link leads below the window: the walk ends)
-                            cursor = (int)UNI(s.w.rank[mi - kHcBase + chainPos]) - 1;
+                            cursor = (int)UNI(hc_lists_rank<kX>(s, mi - kHcBase + chainPos)) - 1;
                             mi -= distNext;
                             nextRound = true;
                             break;
@@ -321,10 +348,10 @@ DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit
                             if (seg >= srcPatternLength && fwd <= srcPatternLength) {
                                 mi = mci + (uint32_t)fwd - (uint32_t)srcPatternLength;     // :1027-1036: looked at next
                                 if (kD && !hc_protect(prefixIdx, mi)) mi = prefixIdx;
-                                cursor = (int)UNI(s.w.rank[mi - kHcBase]);
+                                cursor = (int)UNI(hc_lists_rank<kX>(s, mi - kHcBase));
                             } else if (kD && !hc_protect(prefixIdx, mci - (uint32_t)back)) {
                                 mi = prefixIdx;                                            // :1040-1042
-                                cursor = (int)UNI(s.w.rank[mi - kHcBase]);
+                                cursor = (int)UNI(hc_lists_rank<kX>(s, mi - kHcBase));
                             } else {
                                 mi = mci - (uint32_t)back;                                 // :1038-1058
                                 if (lookBack == 0) {
@@ -333,12 +360,12 @@ DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit
                                         if (ipIndex - mi > 65535u) { walkEnds = true; break; }
                                         longest = (int)maxML; offset = (int)(ipIndex - mi);
                                     }
-                                    const uint32_t dp = hc_link(s, mi);
+                                    const uint32_t dp = hc_link<kX>(s, mi);
                                     if (dp > mi) { walkEnds = true; break; }
                                     const uint32_t at = mi - kHcBase;
-                                    mi -= dp; cursor = (int)UNI(s.w.rank[at]) - 1;
+                                    mi -= dp; cursor = (int)UNI(hc_lists_rank<kX>(s, at)) - 1;
                                     if (dp >= 65535u) { walkEnds = true; break; }
-                                } else cursor = (int)UNI(s.w.rank[mi - kHcBase]);
+                                } else cursor = (int)UNI(hc_lists_rank<kX>(s, mi - kHcBase));
                             }
                             nextRound = true;                                          // the walk goes on somewhere else
                             break;
@@ -357,6 +384,7 @@ DEV HcMatch hc_find_wider_lists(HcState& s, int pos, int lowLimit, int highLimit
             if (walkEnds) break;
         }
     }
+    if (attemptsLeft) *attemptsLeft = attempts;
     out.len = longest; out.off = offset; out.back = sBack;
     return out;
 }

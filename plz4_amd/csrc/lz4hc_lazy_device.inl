@@ -45,6 +45,7 @@
 #pragma once
 #include "lz4hc12_device.inl"
 #include "lz4_seq_device.inl"
+#include <type_traits>
 
 namespace plz4 {
 
@@ -176,6 +177,8 @@ struct LzNoHook { DEVM bool operator()(int, int, int) const { return false; } };
 // lists were built over segment + block (positions from the segment's first byte; the segment's last three positions left out,
 // :1660-1678).  The interface stays in positions of the BLOCK -- ipStart / anchorStart / ipStop, the hook's arguments, the records,
 // the LzRun that comes back -- so segments, stitching and the emit stage do not know.
+// TWIN: hcx_lazy_block (lz4hcx_device.inl) is this state machine with another finder (own lists in LDS, then a dictionary context's)
+// and another sink (bytes, not records), one segment, no hook.  A change to the decisions below belongs in both.
 template <bool kPa, bool kD, class Hook>
 DEV LzRun hc_lazy_run_t(const uint8_t* __restrict__ blk, const int pfxArg, const int n, const int level, HcWork w, uint64_t* seq,
                         const int ipStart, const int anchorStart, const int ipStopRel, Hook& hook)
@@ -313,6 +316,8 @@ DEV LzRun hc_lazy_run_t(const uint8_t* __restrict__ blk, const int pfxArg, const
 // kD: behind an external segment of pfx bytes (see hc_lazy_run_t).  There level 12 takes this route as well (its own design,
 // lz4hc12_device.inl, computes every position's search up front on the independent block): 16384 attempts, sufficient_len 4095
 // and the full update (:1406, :1929-1936: the skip test looks four positions ahead and every search starts from MINMATCH - 1).
+// TWIN: hcx_opt_block (lz4hcx_device.inl) is this price DP with another finder and another sink (see hc_lazy_run_t).  A change to
+// the DP below belongs in both.
 template <bool kD, class Hook>
 DEV LzRun hc_opt_run(const uint8_t* __restrict__ blk, const int pfxArg, const int n, const int level, HcWork w, uint64_t* seq,
                      const int ipStart, const int anchorStart, const int ipStopRel, Hook& hook)
@@ -664,17 +669,26 @@ DEV void hc_mid_prime(const uint8_t* __restrict__ src, const int size, uint32_t*
 // block > 4 KiB under an attached dictionary); positions count from the segment's first byte inside, records from the block's.  What
 // the reference does differently there: the tables start from LZ4MID_fillHTable over the segment; a candidate inside the segment
 // matches up to the segment's end only (safeLen, :587-596, :637-646) and gets neither the look at ip + 1 (:616) nor a catch-up (:673).
-template <bool kD = false>
-DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, uint32_t* h4t, uint32_t* h8t, uint64_t* seq, int* lastAnchor, const int pfxArg = 0)
+// Tab: the two tables -- uint32_t* (16384 entries each, zeroed here), or a type whose operator[] gives a readable and assignable entry
+// per hash of a position of the block and that comes in empty (lz4hcx_device.inl: the tables of a block of at most 4 KiB in LDS).
+// Ctx: a dictionary context attached to such a block (usingDictCtxHc, lz4hc.c:652-665): a position at which neither table has a
+// match asks ctx.find -- searchIntoDict -- while ipIndex - gDictEndIndex < LZ4_DISTANCE_MAX - 8; a match from there has no look at
+// ip + 1 and no catch-up (its distance is larger than the position).
+struct MidNoCtx { enum : bool { on = false }; DEVM HcMatch find(const uint8_t*, uint32_t, const uint8_t*) const { HcMatch m = {0, 0, 0}; return m; } };
+struct MidDictCtx { enum : bool { on = true }; HcDict d; DEVM HcMatch find(const uint8_t* ipp, uint32_t ipIndex, const uint8_t* mlim) const { return mid_search_ctx(d, ipp, ipIndex, mlim); } };
+template <bool kD = false, class Tab = uint32_t*, class Ctx = MidNoCtx>
+DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab h8t, uint64_t* seq, int* lastAnchor, const int pfxArg = 0, const Ctx ctx = Ctx())
 {
     const int pfx = kD ? pfxArg : 0;
     const uint8_t* const src = blk - pfx;
     const int N = pfx + n;
     const uint32_t prefixIdx = kHcBase + (uint32_t)pfx;
     *lastAnchor = 0;
-    LANES({ for (int i = LANE; i < 16384; i += 64) { h4t[i] = 0u; h8t[i] = 0u; } })            // LZ4_initStreamHC: everything zero, lz4hc.c:1582-1583
-    WAVE_FENCE();
-    if (kD) hc_mid_prime(src, pfx, h4t, h8t);
+    if constexpr (std::is_pointer<Tab>::value) {
+        LANES({ for (int i = LANE; i < 16384; i += 64) { h4t[i] = 0u; h8t[i] = 0u; } })        // LZ4_initStreamHC: everything zero, lz4hc.c:1582-1583
+        WAVE_FENCE();
+    }
+    if constexpr (kD) hc_mid_prime(src, pfx, h4t, h8t);
     SeqSink out; out.seq = seq; out.n = 0; out.bias = pfx;
     LANES({ out.buf[I_] = 0; })
     const int mflimit = N - kMfLimit, matchlimit = N - kLastLiterals;
@@ -738,7 +752,18 @@ DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, uint32_t* h4t
                 if (idx - t4[I_] <= 65535u && (!kD || t4[I_] >= prefixIdx || prefixIdx - t4[I_] >= 4u)) has4[I_] = ld32u(src + (t4[I_] - kHcBase)) == (uint32_t)a64[I_];
             }
         })
-        const uint64_t hit = BALLOT(act[I_] && (has8[I_] || has4[I_]));
+        LV(int, dml); LV(int, dof);                                                             // a match out of the attached context
+        LANES({ dml[I_] = 0; dof[I_] = 0; })
+        if constexpr (Ctx::on) {
+            LANES({
+                const uint32_t idx = (uint32_t)pk[I_] + kHcBase;
+                if (act[I_] && !has8[I_] && !has4[I_] && idx - kHcBase < 65535u - 8u) {            // :652-665
+                    const HcMatch dm = ctx.find(src + pk[I_], idx, src + matchlimit);
+                    if (dm.len >= kMinMatch) { dml[I_] = dm.len; dof[I_] = dm.off; }
+                }
+            })
+        }
+        const uint64_t hit = BALLOT(act[I_] && (has8[I_] || has4[I_] || dml[I_] > 0));
         const int m = hit ? ctz64(hit) : L;
         // the inserts of the lanes that were searched: the long table always (:575), the short one unless the long one matched (:604)
         {
@@ -763,13 +788,18 @@ DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, uint32_t* h4t
         // one look at ip + 1 for a longer one, :616-650 (only behind a short match inside the block, only at a candidate inside the block)
         const bool alt = !via8 && m2d <= 65535u && pos8 >= prefixIdx && cand >= prefixIdx && P < mflimit;
         const int lim1 = (kD && cand < prefixIdx) ? min_(matchlimit, P + (int)(prefixIdx - cand)) : matchlimit;
-        const MidMeasure mm = mid_measure(src, P, (int)dist, alt, P + 1, (int)m2d, anchor, matchlimit, lim1, pfx);
-        int ml = mm.ml1, back = mm.bk1;
-        if (alt && mm.ml2 > ml) {
-            const uint32_t hx = RL(h8x, m);
-            LANES({ if (LANE == 0) h8t[hx] = ipIndex + 1; })
-            LDS_ORDER();
-            P++; ml = mm.ml2; dist = m2d; back = mm.bk2;
+        const int viaCtx = RL(dml, m);
+        int ml = viaCtx, back = 0;
+        if (viaCtx) dist = (uint32_t)RL(dof, m);
+        else {
+            const MidMeasure mm = mid_measure(src, P, (int)dist, alt, P + 1, (int)m2d, anchor, matchlimit, lim1, pfx);
+            ml = mm.ml1; back = mm.bk1;
+            if (alt && mm.ml2 > ml) {
+                const uint32_t hx = RL(h8x, m);
+                LANES({ if (LANE == 0) h8t[hx] = ipIndex + 1; })
+                LDS_ORDER();
+                P++; ml = mm.ml2; dist = m2d; back = mm.bk2;
+            }
         }
         P -= back; ml += back;                                                                 // :673-675
         out.put(P, ml, (int)dist);

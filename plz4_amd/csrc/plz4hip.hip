@@ -26,6 +26,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4hc_device.inl"
 #include "lz4hc12_device.inl"
 #include "lz4hc_lazy_device.inl"
+#include "lz4hcx_device.inl"
 #include "lz4_dx_device.inl"
 #include "lz4_fx_device.inl"
 
@@ -56,6 +57,9 @@ struct CodecArgs {
     const uint32_t* hcDictHash;                     // HC + dictionary: the dictionary context's tables for this level's strategy
     const uint16_t* hcDictChain;                    //   (clz4.NewDictCtxHC, clz4.go:122-147), built by k_hc_dict_prime
     int             hcEx;                           // HC call with a dictionary and/or linked blocks: inputs have 64 KiB of scratch in front
+    // blocks <= 4 KiB under a dictionary context at levels 2..12 (lz4hcx_device.inl, k_hcx): the dictionary's lists (plz4hip_dict_create);
+    // hcx: the call's blocks of that kind are k_hcx's (the one-thread kernels pass them over)
+    const uint32_t* hcxStart;   const uint16_t* hcxList;   int hcx;
     int32_t*        hcPfx;                          // such a call on the list path (k_hc_ext_prep): per block, the bytes of the external segment that
                                                     // lies right in front of it (>= 0), or -1: a block <= 4 KiB under a dictionary context (k_encode_*_hc's)
     // level 12 in three phases (lz4hc12_device.inl): per-block chain and search results of the group [blk0, blk0 + nBlocks)
@@ -676,6 +680,13 @@ __device__ __forceinline__ HcWork hc_with_pre(HcWork w, const CodecArgs& a, int 
     w.list = (a.h12Chain && a.h12Rank) ? a.h12List + (int64_t)i * (a.h12ChainStride + 8) + 8 : nullptr;
     return w;
 }
+// whether block i of an HC call is a block <= 4 KiB under a dictionary context (hc_dict_of's kHcCtx), without laying anything out
+__device__ __forceinline__ bool hc_is_ctx(const CodecArgs& a, int i, int n, bool rawApi)
+{
+    if (n > kHcxMaxBlock) return false;
+    if (!rawApi && a.linked && (i > 0 || a.prevTailLen >= 0)) return false;
+    return a.dict != nullptr || a.dictLen >= 0;
+}
 __global__ __launch_bounds__(64) void k_encode_raw_hc(CodecArgs a)
 {
     const HcWork w = hc_work_of(a);
@@ -687,6 +698,7 @@ __global__ __launch_bounds__(64) void k_encode_raw_hc(CodecArgs a)
         const uint8_t* s = a.src + (int64_t)i * a.srcStride;
         int r;
         if (a.hcPfx && a.hcPfx[i] >= 0) continue;                          // (done on the list path)
+        if (a.hcx && hc_is_ctx(a, i, n, true)) continue;                   // (k_hcx's)
         if (dictMode) r = hc_compress(s, n, a.dst + (int64_t)i * a.dstStride, cap, a.level, w, hc_dict_of(a, i, n, s, true));
         else          r = hc_compress(s, n, a.dst + (int64_t)i * a.dstStride, cap, a.level, hc_with_pre(w, a, g));
         if ((threadIdx.x & 63u) == 0) a.result[i] = r;
@@ -703,6 +715,7 @@ __global__ __launch_bounds__(64) void k_encode_rec_hc(CodecArgs a)
         uint8_t*       rec = a.dst + (int64_t)i * a.dstStride;
         int c;                                                           // capacity == bsz (blk.go:73); indie.go:80-88
         if (a.hcPfx && a.hcPfx[i] >= 0) continue;                          // (done on the list path)
+        if (a.hcx && hc_is_ctx(a, i, n, false)) continue;                  // (k_hcx's)
         if (exMode) c = hc_compress(s, n, rec + 4, a.bsz, a.level, w, hc_dict_of(a, i, n, s, false));
         else        c = hc_compress(s, n, rec + 4, a.bsz, a.level, hc_with_pre(w, a, g));
         uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
@@ -717,6 +730,50 @@ __global__ __launch_bounds__(64) void k_encode_rec_hc(CodecArgs a)
         }
         if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[i] = len; }
     }
+}
+
+// HC levels 2..12, the blocks <= 4 KiB under a dictionary context (usingDictCtxHc) of a call: one wave per block off the block queue,
+// the block's lists in LDS (17 KiB: nine waves per CU), the dictionary's lists read-only, nothing else in device memory but the
+// price table of levels 10..12 (lz4hcx_device.inl).  kRaw: LZ4 blocks (dstCap per block), else records [size word][payload][xxh32?] with the stored fallback, as
+// k_encode_rec_hc writes them.  Blocks of any other kind are not its business.  cnt[9]: the blocks it encoded.
+// kMid: level 2 -- its two tables in LDS instead (21 KiB: seven waves per CU), its sequence records where the price table would be.
+template <bool kRaw, bool kMid> __global__ __launch_bounds__(64) void k_hcx(CodecArgs a, unsigned long long* cnt)
+{
+    __shared__ typename std::conditional<kMid, HcxMidLds, HcxLds>::type lds;
+    HcOpt* const opt = (kMid || a.level >= 10) ? hc_work_of(a).opt : nullptr;   // (levels 10..12: the wave's price table)
+    const auto compress = [&](const uint8_t* s, int n, uint8_t* out, int cap, const HcxDict& d) {
+        if constexpr (kMid) return hcx_mid_block(s, n, out, cap, lds, d, a.hcDictHash, (uint64_t*)opt);
+        else return hcx_compress(s, n, out, cap, a.level, lds, d, opt);
+    };
+    HcxDict d; d.bytes = a.dict; d.len = a.dictLen > 0 ? a.dictLen : 0; d.start = a.hcxStart; d.list = (a.dict && d.len > 0) ? a.hcxList : nullptr;
+    int done = 0;
+    for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
+        const int n = block_len(a, i);
+        if (a.hcPfx ? a.hcPfx[i] != -1 : !hc_is_ctx(a, i, n, kRaw)) continue;
+        if (n < 0) { if (kRaw && (threadIdx.x & 63u) == 0) a.result[i] = 0; continue; }      // (LZ4_compress_HC: 0)
+        const uint8_t* s = a.src + (int64_t)i * a.srcStride;
+        uint8_t* const out = a.dst + (int64_t)i * a.dstStride;
+        ++done;
+        if (kRaw) {
+            const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
+            const int r = compress(s, n, out, cap, d);
+            if ((threadIdx.x & 63u) == 0) a.result[i] = r;
+            continue;
+        }
+        int c = compress(s, n, out + 4, a.bsz, d);          // capacity == bsz (blk.go:73)
+        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
+        WAVE_FENCE();
+        if (c == 0) { wave_copy(out + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
+        int len = c + 4;
+        if (a.blockChecksum) {
+            WAVE_FENCE();
+            const uint32_t x = wave_xxh32(out + 4, c);
+            if ((threadIdx.x & 63u) == 0) st32u(out + 4 + c, x);
+            len += 4;
+        }
+        if ((threadIdx.x & 63u) == 0) { st32u(out, word); a.result[i] = len; }
+    }
+    if (done && (threadIdx.x & 63u) == 0) atomicAdd(&cnt[9], (unsigned long long)done);
 }
 
 // HC levels 3..12 with a dictionary and/or linked blocks on the list path (round 4): how every block of the call is primed
@@ -1615,6 +1672,7 @@ struct plz4hip_ctx {
     hipStream_t  hcBuildStream = nullptr; hipEvent_t evHcFork = nullptr, evHcHist = nullptr, evHcChain[2] = {nullptr, nullptr}, evHcFree[2] = {nullptr, nullptr};
     // HC levels 3..12 with a dictionary / linked blocks on the list path: the blocks' segment lengths (k_hc_ext_prep), int32 each
     DeviceBuffer hcPfx;  int hcLazyExWaves = 0;
+    int hcxWaves[4] = {0, 0, 0, 0};                     // resident waves of k_hcx<kRaw, kMid>, [kRaw + 2 * kMid]
     // LZ4_decompress_safe of a few blocks by the whole chip (lz4_dx_device.inl): its tables
     DeviceBuffer dx;  StreamOrder dxOrder;
     hipStream_t  dxHashStream = nullptr; hipEvent_t evDxFork = nullptr, evDxHash = nullptr;   // records: the block checksums beside the decode
@@ -1627,8 +1685,8 @@ struct plz4hip_ctx {
     // linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of a call cut into groups),
     // [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block (dictionary, linked)
     // encoded by the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the bulk staged
-    // route (k_l1x_parse)
-    static constexpr int kCounters = 9;
+    // route (k_l1x_parse), [9] blocks of at most 4 KiB under a dictionary context encoded by the wave-wide HC parser (k_hcx)
+    static constexpr int kCounters = 10;
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
@@ -1651,6 +1709,7 @@ struct plz4hip_dict {
     uint8_t*  d_bytes = nullptr;  int len = 0;      // len < 8: the dictionary is dropped by liblz4 (lz4.c:1613-1615)
     uint32_t* d_table = nullptr;
     uint8_t*  d_hc = nullptr;                       // clz4.DictCtxHC: [level-2 tables][hash-chain tables], kHcWorkBytes each
+    uint8_t*  d_hcx = nullptr;                      // the hash chain's positions as runs per hash (hcx_dict_build): [start][list], kHcxDictBytes
     std::vector<uint8_t> h_bytes;
 };
 
@@ -1915,10 +1974,44 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         hipLaunchKernelGGL(k_hc_ext_prep, dim3(grid_for(nb, c->cus * 8)), dim3(64), 0, s, a);
         return PLZ4HIP_OK;
     };
+    // levels 2..12: the blocks <= 4 KiB under a dictionary context go to the wave-wide parser (k_hcx) unless PLZ4HIP_HCX=0 (read per call)
+    {   const char* v = getenv("PLZ4HIP_HCX");
+        a.hcx = a.hcEx && (a.dict != nullptr || a.dictLen >= 0) && a.hcxStart && a.level >= kHcxMinLevel && a.level <= kHcxMaxLevel && !(v && atoi(v) == 0); }
+    const auto hcx_blocks = [&](CodecArgs x) -> int {                       // every block of the call that is k_hcx's, one launch
+        const bool mid = x.level == 2;
+        const void* const kernels[4] = {(const void*)k_hcx<false, false>, (const void*)k_hcx<true, false>, (const void*)k_hcx<false, true>, (const void*)k_hcx<true, true>};
+        const int which = (rawMode ? 1 : 0) + (mid ? 2 : 0);
+        if (!c->hcxWaves[which]) {                                           // (of the instantiation that is launched)
+            int per = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernels[which], 64, 0) != hipSuccess || per < 1) per = 7;
+            c->hcxWaves[which] = c->cus * per;
+        }
+        int waves = c->hcxWaves[which];
+        if (mid || x.level >= 10) {                                          // (a price table / the records per wave: the HC workspace's)
+            if (int rc = ensure_hc(c)) return rc;
+            x.hcWork = c->hc.d;
+            if (c->hcWaves < waves) waves = c->hcWaves;
+        }
+        x.blk0 = 0; x.nBlocks = nb;
+        x.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (mid) {
+            if (rawMode) hipLaunchKernelGGL((k_hcx<true, true>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
+            else         hipLaunchKernelGGL((k_hcx<false, true>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
+        } else {
+            if (rawMode) hipLaunchKernelGGL((k_hcx<true, false>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
+            else         hipLaunchKernelGGL((k_hcx<false, false>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
+        }
+        HIPCHK(c, hipGetLastError());
+        return PLZ4HIP_OK;
+    };
+    // a call of nothing but such blocks (many small records under one dictionary) is that one launch: no segments to lay out, no
+    // lists in device memory, no workspace
+    if (a.hcx && maxLen <= kHcxMaxBlock && (rawMode || !a.linked)) { a.hcPfx = nullptr; return hcx_blocks(a); }
     const auto ctx_blocks = [&](const CodecArgs& a0) -> int {
         // the blocks <= 4 KiB under a dictionary context (hcPfx < 0; the emit stage has laid them down as stored records in the
-        // meantime): the one-thread parser over the context's two sets of tables writes them now
+        // meantime): k_hcx, or the one-thread parser over the context's two sets of tables, writes them now
         if (a0.dict == nullptr && a0.dictLen < 0) return PLZ4HIP_OK;
+        if (a0.hcx) return hcx_blocks(a0);
         if (int rc = ensure_hc(c)) return rc;
         CodecArgs x = a0; x.hcWork = c->hc.d; x.blk0 = 0; x.nBlocks = nb; x.h12Chain = nullptr; x.h12Rank = nullptr; x.h12List = nullptr;
         x.queue = next_queue(c, s, &e); HIPCHK(c, e);
@@ -2182,6 +2275,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
             else         hipLaunchKernelGGL(k_encode_rec_hc, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
             HIPCHK(c, hipGetLastError());
         }
+        if (a.hcx) { a.hcPfx = nullptr; if (int rc = hcx_blocks(a)) return rc; }   // (the one-thread kernels passed them over)
     }
     return PLZ4HIP_OK;
 }
@@ -3053,6 +3147,7 @@ static int encode_ex_args(plz4hip_ctx* c, CodecArgs& a, const void* src, int64_t
         if (dict) {
             const uint8_t* t = dict->d_hc + (level <= 2 ? 0 : (size_t)kHcWorkBytes);
             a.hcDictHash = (const uint32_t*)t; a.hcDictChain = (const uint16_t*)(t + kHcHashEntries * 4);
+            a.hcxStart = (const uint32_t*)dict->d_hcx; a.hcxList = (const uint16_t*)(dict->d_hcx + kHcxDictStartBytes);
         }
     }
     return PLZ4HIP_OK;
@@ -3238,6 +3333,7 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
                 if (dj->dict) {
                     const uint8_t* t = dj->dict->d_hc + (dj->level <= 2 ? 0 : (size_t)kHcWorkBytes);
                     a.hcDictHash = (const uint32_t*)t; a.hcDictChain = (const uint16_t*)(t + kHcHashEntries * 4);
+                    a.hcxStart = (const uint32_t*)dj->dict->d_hcx; a.hcxList = (const uint16_t*)(dj->dict->d_hcx + kHcxDictStartBytes);
                 }
             }
             a.linked = dj->linked;
@@ -3510,12 +3606,18 @@ int plz4hip_dict_create(plz4hip_ctx* c, const void* dict, int dictLen, plz4hip_d
     if (e == hipSuccess && dictLen) e = copy_sync(c, d->d_bytes, d->h_bytes.data(), (size_t)dictLen, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = copy_sync(c, d->d_table, tab.data(), 4096 * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void**)&d->d_hc, 2 * (size_t)kHcWorkBytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d->d_hcx, (size_t)kHcxDictBytes);
+    if (e == hipSuccess) {                                                       // ... and the hash chain as lists, for k_hcx
+        std::vector<uint8_t> lists((size_t)kHcxDictBytes, 0);
+        hcx_dict_build(d->h_bytes.data(), dictLen, (uint32_t*)lists.data(), (uint16_t*)(lists.data() + kHcxDictStartBytes));
+        e = copy_sync(c, d->d_hcx, lists.data(), lists.size(), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess) {                                                       // clz4.NewDictCtxHC for both table strategies
         hipLaunchKernelGGL(k_hc_dict_prime, dim3(2), dim3(64), 0, c->stream, (const uint8_t*)d->d_bytes, dictLen, d->d_hc);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    if (e != hipSuccess) { if (d->d_bytes) hipFree(d->d_bytes); if (d->d_table) hipFree(d->d_table); if (d->d_hc) hipFree(d->d_hc); delete d; return fail(c, PLZ4HIP_E_DEVICE, "plz4hip_dict_create", e); }
+    if (e != hipSuccess) { if (d->d_bytes) hipFree(d->d_bytes); if (d->d_table) hipFree(d->d_table); if (d->d_hc) hipFree(d->d_hc); if (d->d_hcx) hipFree(d->d_hcx); delete d; return fail(c, PLZ4HIP_E_DEVICE, "plz4hip_dict_create", e); }
     *out = d;
     return PLZ4HIP_OK;
 }
@@ -3527,6 +3629,7 @@ void plz4hip_dict_destroy(plz4hip_ctx* c, plz4hip_dict* d)
     if (d->d_bytes) hipFree(d->d_bytes);
     if (d->d_table) hipFree(d->d_table);
     if (d->d_hc) hipFree(d->d_hc);
+    if (d->d_hcx) hipFree(d->d_hcx);
     delete d;
 }
 
