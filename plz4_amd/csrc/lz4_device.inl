@@ -172,6 +172,98 @@ DEV uint32_t wave_xxh32_staged(const uint8_t* p, int n, uint8_t* lds)
     return h;
 }
 
+// The same digest of up to SIXTEEN buffers at once: lane 4g + l owns accumulator l of buffer g (p and n: per lane, the same in the
+// four lanes of a group; n < 0: the group has no buffer and does nothing).  A buffer's four chains stay what they are -- there is
+// no combine operator -- but sixteen buffers' chains run side by side in one instruction stream, where the forms above keep four of
+// 64 lanes busy.  No LDS: every lane keeps kX16Depth of its own dwords in flight in registers (a ring: the register a round has
+// consumed takes the load of the stripe kX16Depth further on), so that the chain and not a memory round trip sets the pace.
+// Buffers may start at any byte, and no load touches a byte at or beyond p + n: the ring is refilled only where all of its
+// stripes lie inside the buffer, and the rest is read stripe by stripe.  Groups with shorter buffers stop early (their lanes
+// leave the loops).  h: the digest, valid in the group's first lane.
+constexpr int kX16Depth = 64;
+DEV uint32_t xxh32_round(uint32_t a, uint32_t x) { return rotl32(a + x * XP2, 13) * XP1; }
+DEV void wave_xxh32_x16(LVREF(const uint8_t*, p), LVREF(int, n), LVREF(uint32_t, h))
+{
+    LV(uint32_t, acc);
+    LANES({
+        const int l = LANE & 3;
+        uint32_t a = (l == 0) ? XP1 + XP2 : (l == 1) ? XP2 : (l == 2) ? 0u : 0u - XP1;
+        const int stripes = n[I_] >> 4;                                     // (n < 0: negative, no loop runs)
+        if (stripes > 0) {
+            const uint8_t* q = p[I_] + 4 * l;
+            int s = 0;
+            if (stripes >= kX16Depth) {
+                uint32_t x[kX16Depth];
+                _Pragma("unroll")
+                for (int j = 0; j < kX16Depth; ++j) x[j] = ld32u(q + 16 * j);
+                for (; s + 2 * kX16Depth <= stripes; s += kX16Depth) {      // stripes s + D .. s + 2D - 1 exist: refill as we go
+                    const uint8_t* const qn = q + 16 * (size_t)kX16Depth;
+                    _Pragma("unroll")
+                    for (int j = 0; j < kX16Depth; ++j) { a = xxh32_round(a, x[j]); x[j] = ld32u(qn + 16 * j); }
+                    q = qn;
+                }
+                _Pragma("unroll")
+                for (int j = 0; j < kX16Depth; ++j) a = xxh32_round(a, x[j]);
+                q += 16 * (size_t)kX16Depth; s += kX16Depth;
+            }
+            for (; s + 8 <= stripes; s += 8) {                              // fewer than 2 * depth left: 8 loads in flight
+                const uint32_t x0 = ld32u(q), x1 = ld32u(q + 16), x2 = ld32u(q + 32), x3 = ld32u(q + 48);
+                const uint32_t x4 = ld32u(q + 64), x5 = ld32u(q + 80), x6 = ld32u(q + 96), x7 = ld32u(q + 112);
+                a = xxh32_round(a, x0); a = xxh32_round(a, x1); a = xxh32_round(a, x2); a = xxh32_round(a, x3);
+                a = xxh32_round(a, x4); a = xxh32_round(a, x5); a = xxh32_round(a, x6); a = xxh32_round(a, x7);
+                q += 128;
+            }
+            for (; s < stripes; ++s) { a = xxh32_round(a, ld32u(q)); q += 16; }
+        }
+        acc[I_] = a;
+    })
+    // the group's first lane gathers the four chains, then the < 16 tail bytes and the avalanche
+    LV(uint32_t, a1); LV(uint32_t, a2); LV(uint32_t, a3);
+    LANES({ a1[I_] = SHFL(acc, (LANE & ~3) + 1); })
+    LANES({ a2[I_] = SHFL(acc, (LANE & ~3) + 2); })
+    LANES({ a3[I_] = SHFL(acc, (LANE & ~3) + 3); })
+    LANES({
+        h[I_] = 0;
+        const int nn = n[I_];
+        if ((LANE & 3) == 0 && nn >= 0) {
+            uint32_t v = (uint32_t)nn;
+            if (nn >= 16) v += rotl32(acc[I_], 1) + rotl32(a1[I_], 7) + rotl32(a2[I_], 12) + rotl32(a3[I_], 18);
+            else v += XP5;
+            const uint8_t* t = p[I_] + ((size_t)(nn >> 4) << 4);
+            int rem = nn & 15;
+            for (; rem >= 4; rem -= 4) { v = rotl32(v + ld32u(t) * XP3, 17) * XP4; t += 4; }
+            for (; rem; --rem)         { v = rotl32(v + (uint32_t)*t * XP5, 11) * XP1; t++; }
+            v ^= v >> 15; v *= XP2; v ^= v >> 13; v *= XP3; v ^= v >> 16;
+            h[I_] = v;
+        }
+    })
+}
+
+// Exclusive prefix sum of n lengths (int32 -> int64) by one wave, no LDS: every lane sums a contiguous share, the lane totals are
+// scanned on the DPP network in 64 bits, every lane writes its share's offsets.  off[i] = base + len[0] + .. + len[i - 1], off[n] =
+// the total; base = 0 when `first`, else what off[0] holds (the total the scan of the part before left there).  kClamp: lengths
+// that are not positive (an engine failure code) count as 0.
+template <bool kClamp>
+DEV void wave_scan_lengths(const int32_t* len, int64_t* off, int n, int first)
+{
+    const int per = (n + 63) / 64;
+    const int64_t base = first ? 0 : (int64_t)UNI((uint64_t)off[0]);       // (lane 0 writes the same value back there)
+    LV(int64_t, tot); LV(int64_t, own);
+    LANES({
+        const int64_t lo = min_((int64_t)LANE * per, (int64_t)n), hi = min_(lo + per, (int64_t)n);
+        int64_t s = 0;
+        for (int64_t i = lo; i < hi; ++i) s += (kClamp && len[i] <= 0) ? 0 : len[i];
+        tot[I_] = s; own[I_] = s;
+    })
+    SCAN_INCL64(tot);
+    LANES({
+        const int64_t lo = min_((int64_t)LANE * per, (int64_t)n), hi = min_(lo + per, (int64_t)n);
+        int64_t run = base + tot[I_] - own[I_];
+        for (int64_t i = lo; i < hi; ++i) { off[i] = run; run += (kClamp && len[i] <= 0) ? 0 : len[i]; }
+        if (LANE == 63) off[n] = base + tot[I_];
+    })
+}
+
 // Streaming xxHash32, seed 0 (xxh32.XXHZero, internal/pkg/xxh32/xxh32zero.go:58-86 Write, :204-235 Sum32; fed in block order by
 // async/hash.go:99-111).  The state lives in device memory between calls; Write is what the wave does, Sum32 is finished by
 // whoever reads the state back (it does not disturb it).  There is no combine operator for XXH32: the four chains are strictly

@@ -327,23 +327,35 @@ template <bool kBack, bool kSeg = false> __device__ __forceinline__ void l1_writ
 }
 template <bool kBack> __global__ __launch_bounds__(256) void k_l1_write(CodecArgs a) { l1_write_body<kBack>(a); }
 
-// records with block checksums: xxh32 over the payload as stored (blk.go:98-102), one wave per block
-__global__ __launch_bounds__(256) void k_l1_finish(CodecArgs a)
+// records with block checksums: xxh32 over the payload as stored (blk.go:98-102), one wave per 16 blocks (wave_xxh32_x16: four
+// lanes per block); no LDS, so the kernel runs beside a parse launch that holds all of it
+__global__ __launch_bounds__(64) void k_l1_finish(CodecArgs a)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stagebuf[4][4096];
-    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (i >= a.nBlocks) return;
-    const int gi = a.blk0 + i;
-    const SeqInfo inf = a.l1Info[i];
-    const int c = inf.total ? inf.total : block_len(a, gi);
-    uint8_t* rec = a.dst + (int64_t)gi * a.dstStride;
-    if (a.bodyOff) {
-        const int64_t off = a.bodyOff[gi];
-        if (inf.nseq == kSeqEngineFailed || off + (int64_t)c + 8 > a.bodyCap) return;     // (not written: k_l1_write)
-        rec = a.dst + off;
+    const int i = blockIdx.x * 16 + (int)((threadIdx.x & 63u) >> 2);
+    const uint8_t* p[1] = {nullptr};
+    int n[1] = {-1};
+    uint32_t x[1];
+    int gi = 0;
+    bool failed = false;
+    if (i < a.nBlocks) {
+        gi = a.blk0 + i;
+        const SeqInfo inf = a.l1Info[i];
+        const int c = inf.total ? inf.total : block_len(a, gi);
+        failed = inf.nseq == kSeqEngineFailed;
+        const uint8_t* rec = a.dst + (int64_t)gi * a.dstStride;
+        bool written = true;
+        if (a.bodyOff) {
+            const int64_t off = a.bodyOff[gi];
+            written = !failed && off + (int64_t)c + 8 <= a.bodyCap;           // (not written: k_l1_write)
+            rec = a.dst + off;
+        }
+        if (written) { p[0] = rec + 4; n[0] = c; }
     }
-    const uint32_t x = wave_xxh32_staged(rec + 4, c, stagebuf[threadIdx.x >> 6]);
-    if ((threadIdx.x & 63u) == 0) { st32u(rec + 4 + c, x); if (!a.bodyOff) a.result[gi] = inf.nseq == kSeqEngineFailed ? PLZ4HIP_E_DEVICE : c + 8; }
+    wave_xxh32_x16(p, n, x);
+    if ((threadIdx.x & 3u) == 0 && n[0] >= 0) {
+        st32u(const_cast<uint8_t*>(p[0]) + n[0], x[0]);
+        if (!a.bodyOff) a.result[gi] = failed ? PLZ4HIP_E_DEVICE : n[0] + 8;
+    }
 }
 
 // One level-1 block under a dictionary context and/or after another linked block.  Every input block of such a call has
@@ -1458,7 +1470,9 @@ __device__ __forceinline__ void decode_rec_loop(const CodecArgs& a, uint8_t* dl)
         if (sz > a.bsz || (int64_t)sz + 4 + (a.blockChecksum ? 4 : 0) > recLen) {
             st = PLZ4HIP_BLK_SIZE_OVERFLOW;
         } else {
-            if (a.blockChecksum) {
+            // the bulk path: k_rec_verify16 has run in front of this launch and left its verdict; what it rejected is not decoded
+            if (!kDx && a.blockChecksum) st = plz4_readfirstlane(a.status[i]);
+            if (kDx && a.blockChecksum) {
                 const uint32_t want = plz4_readfirstlane(ld32u(rec + 4 + sz));
                 if (wave_xxh32(rec + 4, sz) != want) st = PLZ4HIP_BLK_HASH_MISMATCH;
             }
@@ -1474,6 +1488,32 @@ __device__ __forceinline__ void decode_rec_loop(const CodecArgs& a, uint8_t* dl)
             }
         }
         if ((threadIdx.x & 63u) == 0) { a.result[i] = r; a.status[i] = st; }
+    }
+}
+// The block checksums of the bulk decoder's records, ahead of the decode (frame.go:114-127 rejects before it decodes): one wave per
+// 16 records, four lanes each (wave_xxh32_x16), no LDS -- enqueued in front of every launch of decode_rec_loop<false> with block
+// checksums.  FrameReader._read's size checks and the comparison; status[i] <- OK / HASH_MISMATCH / SIZE_OVERFLOW, result[i] <- 0
+// where it is not OK.  The decoder then skips what is not OK and carries no checksum pass of its own.
+__global__ __launch_bounds__(64) void k_rec_verify16(CodecArgs a)
+{
+    const int i = blockIdx.x * 16 + (int)((threadIdx.x & 63u) >> 2);
+    const uint8_t* p[1] = {nullptr};
+    int n[1] = {-1};
+    uint32_t x[1];
+    uint32_t want = 0;
+    if (i < a.nBlocks) {
+        const uint8_t* rec    = a.recOff ? a.src + a.recOff[i] : a.src + (int64_t)i * a.srcStride;
+        const int64_t  recLen = a.recOff ? a.recOff[i + 1] - a.recOff[i] : (int64_t)a.srcLen[i];
+        if (recLen >= 8) {                                                   // (less: no room for the size word and the checksum)
+            const int sz = (int)(ld32u(rec) & 0x7FFFFFFFu);
+            if (sz <= a.bsz && (int64_t)sz + 8 <= recLen) { p[0] = rec + 4; n[0] = sz; want = ld32u(rec + 4 + sz); }
+        }
+    }
+    wave_xxh32_x16(p, n, x);
+    if ((threadIdx.x & 3u) == 0 && i < a.nBlocks) {
+        const int st = n[0] < 0 ? PLZ4HIP_BLK_SIZE_OVERFLOW : x[0] != want ? PLZ4HIP_BLK_HASH_MISMATCH : PLZ4HIP_BLK_OK;
+        a.status[i] = st;
+        if (st != PLZ4HIP_BLK_OK) a.result[i] = 0;
     }
 }
 #if defined(PLZ4_EXP_DEC_EU)
@@ -1544,50 +1584,17 @@ __global__ __launch_bounds__(64) void k_xxh32_stream(XxhStream* st, const uint8_
     }
 }
 
-// Exclusive prefix sum int32 -> int64, one workgroup.
-__global__ __launch_bounds__(1024) void k_scan(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n)
+// Exclusive prefix sum int32 -> int64, one wave, no LDS (wave_scan_lengths).
+__global__ __launch_bounds__(64) void k_scan(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n)
 {
-    __shared__ int64_t part[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = min(t * per, n), hi = min(lo + per, n);
-    int64_t s = 0;
-    for (int i = lo; i < hi; ++i) s += len[i];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int64_t v = (t >= d) ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int64_t run = part[t] - s;
-    for (int i = lo; i < hi; ++i) { off[i] = run; run += len[i]; }
-    if (t == 1023) off[n] = part[1023];
+    wave_scan_lengths<false>(len, off, n, 1);
 }
 
 // ... continued behind an earlier part: off[0] holds where this part starts (the total the scan of the part before left there);
 // lengths that are not positive (an engine failure code) count as 0
-__global__ __launch_bounds__(1024) void k_scan_from(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n, int first)
+__global__ __launch_bounds__(64) void k_scan_from(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n, int first)
 {
-    __shared__ int64_t part[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = min(t * per, n), hi = min(lo + per, n);
-    const int64_t base = first ? 0 : off[0];
-    int64_t s = 0;
-    for (int i = lo; i < hi; ++i) s += len[i] > 0 ? len[i] : 0;
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int64_t v = (t >= d) ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int64_t run = base + part[t] - s;
-    for (int i = lo; i < hi; ++i) { off[i] = run; run += len[i] > 0 ? len[i] : 0; }
-    if (t == 1023) off[n] = base + part[1023];
+    wave_scan_lengths<true>(len, off, n, first);
 }
 
 // Bytes to hand back per block of a host call: the result if positive (sizes), nothing for 0 / error codes.
@@ -1940,6 +1947,12 @@ bool use_h12(const CodecArgs& a, int maxLen) { return a.level >= 12 && !a.hcEx &
 // wave-wide, instead of every position's search up front, lz4hc12_device.inl)
 bool use_lazy(const CodecArgs& a, int maxLen) { return a.level >= 3 && (a.level <= 11 || getenv("PLZ4HIP_HC12_LAZY") != nullptr) && !a.hcEx && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_LAZY_OFF") == nullptr; }
 
+// The block checksums of a record decode on the bulk path, in front of its launch (k_rec_verify16): every launch of k_decode_rec and
+// of k_l1_duplex's decode side goes through here first.
+void launch_rec_verify(hipStream_t s, const CodecArgs& d)
+{
+    if (d.blockChecksum && d.nBlocks > 0) hipLaunchKernelGGL(k_rec_verify16, dim3((d.nBlocks + 15) / 16), dim3(64), 0, s, d);
+}
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined = nullptr,
               const CodecArgs* rider = nullptr, bool hist = false, bool l1x = false);
 
@@ -2180,7 +2193,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
                 hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
                 hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
                 hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
-                if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 3) / 4), dim3(256), 0, s, a);
+                if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 15) / 16), dim3(64), 0, s, a);
             }
             HIPCHK(c, hipGetLastError());
             if (overlap && gi + 2 < nGroups) {
@@ -2393,7 +2406,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     if (fused) {
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         if (rawMode) ENC_LAUNCH(k_encode_raw, nb, c, s, a); else ENC_LAUNCH(k_encode_rec, nb, c, s, a);
-        if (rider) hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(rider->nBlocks, c->decWaves)), dim3(64), 0, s, *rider);
+        if (rider) { launch_rec_verify(s, *rider); hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(rider->nBlocks, c->decWaves)), dim3(64), 0, s, *rider); }
         HIPCHK(c, hipGetLastError());
         return PLZ4HIP_OK;
     }
@@ -2442,6 +2455,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         const int ng = nb - g0 < per ? nb - g0 : per;
         a.blk0 = g0; a.nBlocks = ng;
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (rider && g0 == 0) launch_rec_verify(s, *rider);                     // (in front of the gate: beside the other stream's launch)
         const bool signals = !mid && !getenv("PLZ4HIP_EXP_NO_GATE");            // (the level-1 parse and the duplex launch)
         if (useFx || hist) a.gate = nullptr;                                    // (neither waits for nor signals the gate)
         else if (signals) {
@@ -2519,11 +2533,11 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
         const bool ctxSmall = hist && a.dictLen >= 8;                           // (the blocks <= 4 KiB under the context: k_fxl_small)
         if (ctxSmall && a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);   // (their lengths, before the records are placed)
-        if (a.bodyOff) hipLaunchKernelGGL(k_scan_from, dim3(1), dim3(1024), 0, s, (const int32_t*)(a.result + g0), a.bodyOff + g0, ng, g0 == 0 ? 1 : 0);
+        if (a.bodyOff) hipLaunchKernelGGL(k_scan_from, dim3(1), dim3(64), 0, s, (const int32_t*)(a.result + g0), a.bodyOff + g0, ng, g0 == 0 ? 1 : 0);
         if (hist) hipLaunchKernelGGL(k_fxl_write, dim3(wg, ng), dim3(256), 0, s, a, (const FxlBlk*)xb);
         else if (mid) hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_l1_write<true>, dim3(wg, ng), dim3(256), 0, s, a);
-        if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 3) / 4), dim3(256), 0, s, a);
+        if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 15) / 16), dim3(64), 0, s, a);
         if (ctxSmall && !a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
@@ -2688,7 +2702,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
     else if (hist && records) hipLaunchKernelGGL(k_decode_rec_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     else if (hist)            hipLaunchKernelGGL(k_decode_raw_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     else if (records && dx) hipLaunchKernelGGL(k_decode_rec_dx, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
-    else if (records)  hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
+    else if (records)  { launch_rec_verify(s, a); hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a); }
     else               hipLaunchKernelGGL(k_decode_raw, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, job.leave());
@@ -2923,7 +2937,7 @@ int plz4hip_dev_compact_records(plz4hip_ctx* c, const void* stage, int64_t stage
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, recLen, recOff, nBlocks);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(64), 0, s, recLen, recOff, nBlocks);
     HIPCHK(c, hipGetLastError());
     if (body) {
         hipLaunchKernelGGL(k_move_records, dim3(nBlocks, move_slices((int)stageStride)), dim3(256), 0, s,
@@ -3043,6 +3057,7 @@ int plz4hip_dev_duplex_records(plz4hip_ctx* c, const void* src, int64_t srcBytes
     d.dictLen = -1; d.prevTailLen = -1;
     if (nDecBlocks > 0) { hipError_t e; d.queue = next_queue(c, s, &e); HIPCHK(c, e); }
     if (nBlocks == 0) {
+        launch_rec_verify(s, d);
         hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nDecBlocks, c->decWaves)), dim3(64), 0, s, d);
         HIPCHK(c, hipGetLastError());
         return PLZ4HIP_OK;
@@ -3106,6 +3121,7 @@ int plz4hip_dev_duplex_body(plz4hip_ctx* c, const void* src, int64_t srcBytes, i
     if (nDecBlocks > 0) { hipError_t e; d.queue = next_queue(c, s, &e); HIPCHK(c, e); }
     if (nBlocks == 0) {
         HIPCHK(c, hipMemsetAsync(recOff, 0, sizeof(int64_t), s));
+        launch_rec_verify(s, d);
         hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nDecBlocks, c->decWaves)), dim3(64), 0, s, d);
         HIPCHK(c, hipGetLastError());
         return PLZ4HIP_OK;
@@ -3202,7 +3218,7 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes
         MarkOnExit job;  job.arm(c->xstageOrder, s);
         a.dst = c->xstage.d; a.dstStride = stride; a.bodyOff = nullptr; a.bodyCap = 0;
         if (int rc = launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true)) return rc;
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, (const int32_t*)recLen, recOff, nBlocks);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(64), 0, s, (const int32_t*)recLen, recOff, nBlocks);
         hipLaunchKernelGGL(k_move_records, dim3(nBlocks, move_slices((int)stride)), dim3(256), 0, s,
                            (const uint8_t*)c->xstage.d, (const int64_t*)nullptr, stride, (const int32_t*)recLen, (const int64_t*)recOff, (uint8_t*)body, bodyCap);
         HIPCHK(c, hipGetLastError());
@@ -3394,7 +3410,7 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
         if (mode != 4) {                                       // pack the outputs: sizes -> offsets -> back to back
             int32_t* dLen = (int32_t*)(sl.d + st.offLen); int64_t* dOff = (int64_t*)(sl.d + st.offOff);
             hipLaunchKernelGGL(k_out_len, dim3((nb + 255) / 256), dim3(256), 0, s, (const int32_t*)a.result, dLen, nb);
-            hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, (const int32_t*)dLen, dOff, nb);
+            hipLaunchKernelGGL(k_scan, dim3(1), dim3(64), 0, s, (const int32_t*)dLen, dOff, nb);
             hipLaunchKernelGGL(k_move_records, dim3(nb, move_slices((int)st.outStride)), dim3(256), 0, s,
                                (const uint8_t*)(sl.d + st.offOut), (const int64_t*)nullptr, st.outStride, (const int32_t*)dLen,
                                (const int64_t*)dOff, sl.d + st.offPack, (int64_t)nb * st.outStride);

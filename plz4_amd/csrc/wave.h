@@ -38,6 +38,7 @@
 #define SCAN_INCL(x)   do { for (int s_ = 1; s_ < 64; ++s_) (x)[s_] += (x)[s_ - 1]; } while (0)   /* inclusive prefix sum over lanes */
 /* x[l] <- max of x over the lanes strictly below l (0 for lane 0); x >= 0 */
 #define SCAN_MAX_EXCL(x) do { int m_ = 0; for (int s_ = 0; s_ < 64; ++s_) { const int v_ = (x)[s_]; (x)[s_] = m_; if (v_ > m_) m_ = v_; } } while (0)
+#define SCAN_INCL64(x) SCAN_INCL(x)                      /* the same over 64-bit values */
 #define UNI_OPAQUE(x)  do {} while (0)
 #define BITSET64(m, b) do { (m) |= 1ull << ((b) & 63); } while (0)   /* set bit (b & 63) of a wave-uniform 64-bit mask */
 #define WAVE_FENCE()   do {} while (0)
@@ -76,6 +77,7 @@ static inline int plz4_emu_step()  { return plz4_emu_descending ? -1 : 1; }
 #define LANE_IN(mask)  (__builtin_amdgcn_inverse_ballot_w64((uint64_t)(mask)))
 #define LVREF(T, x)    T (&x)[1]
 #define SCAN_INCL(x)   do { (x)[0] = plz4_scan_incl((x)[0]); } while (0)
+#define SCAN_INCL64(x) do { (x)[0] = plz4_scan_incl64((x)[0]); } while (0)
 #define SCAN_MAX_EXCL(x) do { (x)[0] = plz4_scan_max_excl((x)[0]); } while (0)
 // Same-wave producer/consumer through memory needs no cache action on CDNA (one TCP, in-order VMEM
 // queue); the fence only stops the compiler from reordering the accesses.
@@ -103,6 +105,23 @@ __device__ __forceinline__ int plz4_scan_incl(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);     // row_shr:8
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);    // row_bcast15 -> rows 1, 3
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);    // row_bcast31 -> rows 2, 3
+    return v;
+}
+// The same over 64-bit values: a DPP move of both halves is a move of the value, the add is 64 bits wide.
+template <int kCtrl, int kRows, bool kBound> __device__ __forceinline__ int64_t plz4_dpp_mov64(int64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, kCtrl, kRows, 0xF, kBound);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)((uint64_t)v >> 32), kCtrl, kRows, 0xF, kBound);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ int64_t plz4_scan_incl64(int64_t v)
+{
+    v += plz4_dpp_mov64<0x111, 0xF, true>(v);
+    v += plz4_dpp_mov64<0x112, 0xF, true>(v);
+    v += plz4_dpp_mov64<0x114, 0xF, true>(v);
+    v += plz4_dpp_mov64<0x118, 0xF, true>(v);
+    v += plz4_dpp_mov64<0x142, 0xA, false>(v);
+    v += plz4_dpp_mov64<0x143, 0xC, false>(v);
     return v;
 }
 // Exclusive prefix maximum of non-negative values, same network; the final step moves everything up one lane (wave_shr:1).
