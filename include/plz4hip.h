@@ -48,7 +48,9 @@
  * with a dictionary and / or linked = 1, decode_records_chains): the call has one pointer space, a match that starts in front of
  * its block points into an earlier block's output, the window the call came in with or the dictionary, and the jump rounds follow
  * the call's total output (up to 32).  A chain is answered up to its first block that is not plainly good; the one-wavefront chain
- * walk goes on from there inside the call, from the window the good blocks leave.  PLZ4HIP_DX_LINKED=0 keeps such calls on the
+ * walk goes on from there inside the call, from the window the good blocks leave.  The blocks of a chain behind a record that
+ * fails the frame reader's checks (PLZ4HIP_BLK_SIZE_OVERFLOW) are not decoded on this path either: their output stays as it was,
+ * as on the walk.  PLZ4HIP_DX_LINKED=0 keeps such calls on the
  * one-wavefront kernels (a switch for tests and A/B runs; PLZ4HIP_DX_MAX_BLOCKS=0 does so too).
  * A LINKED call of more blocks than that (decode_records_ex with linked = 1, decode_records_chains, dev_decode_records_ex) is cut
  * into groups of PLZ4HIP_DXL_GROUP_BLOCKS consecutive blocks (default 128; read per call), each group the same path across the whole
@@ -139,6 +141,8 @@ int plz4hip_compress_bound(int n);
  *           take the same levels.
  *    result[i]: encode  > 0 bytes written into dst[i], 0 = liblz4 "does not fit dstCap[i]";
  *               decode >= 0 bytes written, < 0 liblz4 error code.
+ *    Decode, whatever the input holds: a call reads no byte outside the srcLen[i] bytes of src[i] and the dictionary, and it
+ *    writes no byte outside the dstCap[i] bytes of dst[i].
  * ------------------------------------------------------------------------------------------------------- */
 int plz4hip_compress_batch(plz4hip_ctx* ctx, int nBlocks,
                            const void* const* src, const int32_t* srcLen,
@@ -161,6 +165,8 @@ int plz4hip_xxh32_batch(plz4hip_ctx* ctx, int n, const void* const* buf, const i
  *    decode: rec[i]/recLen[i] is one such record (size word included); dst[i] has bsz+8 bytes like the
  *            reference's pooled block (blk/pool.go:23-26); status[i] = PLZ4HIP_BLK_*, result[i] = plaintext bytes
  *            (or liblz4's negative code when status is PLZ4HIP_BLK_CORRUPT).
+ *            Whatever the record holds -- a size word that lies, fewer bytes than a size word -- a decode call reads no byte
+ *            outside rec[i]'s recLen[i] bytes and the dictionary or window, and writes no byte outside dst[i]'s bsz+8 bytes.
  * ------------------------------------------------------------------------------------------------------- */
 int plz4hip_encode_records(plz4hip_ctx* ctx, int nBlocks,
                            const void* const* src, const int32_t* srcLen,
@@ -263,6 +269,9 @@ int  plz4hip_ctx_set_content_hash(plz4hip_ctx* ctx, plz4hip_xxh32_stream* h);
  *      recLen  int32[nBlocks]   record i length (4 + payload + 4 if checksums)
  *      recOff  int64[nBlocks+1] exclusive prefix sum of recLen (recOff[nBlocks] = body bytes)
  *      body    the records, compacted back to back: exactly the frame's block section
+ *    Decode (dev_decompress, dev_decode_records*, the decode side of dev_duplex_*), whatever the input holds: a call reads no
+ *    byte outside the srcLen[i] bytes of a block / the recOff[i+1] - recOff[i] bytes of a record and the dictionary or the
+ *    chain's window, and it writes no byte outside the dstCap bytes of that block's output (and the window).
  *    plz4hip_dev_encode_records  : the encode kernel; fills stage + recLen.
  *    plz4hip_dev_compact_records : exclusive scan of recLen -> recOff, then moves every record to body+recOff[i];
  *                                  records that would end past bodyCap are skipped (recOff[nBlocks] > bodyCap tells).

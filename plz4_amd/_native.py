@@ -343,6 +343,11 @@ class Engine:
         self._chk(self.L.plz4hip_dev_scatter_records(self.h, src_ptr, srcoff_ptr, len_ptr, dstoff_ptr, n, max_len, dst_ptr,
                                                      dst_cap, stream))
 
+    def dev_decompress(self, nblocks, src_ptr, src_stride, srclen_ptr, dst_ptr, dst_stride, dstcap_ptr, result_ptr, stream=0):
+        """raw blocks at src + i * src_stride -> dst + i * dst_stride; lengths, capacities and results (int32) on the device"""
+        self._chk(self.L.plz4hip_dev_decompress(self.h, nblocks, src_ptr, src_stride, srclen_ptr, dst_ptr, dst_stride, dstcap_ptr,
+                                                result_ptr, stream))
+
     def dev_decode_records(self, body_ptr, recoff_ptr, nblocks, bsz, block_checksum, dst_ptr, dst_stride, dst_cap,
                            result_ptr, status_ptr, stream=0):
         self._chk(self.L.plz4hip_dev_decode_records(self.h, body_ptr, recoff_ptr, nblocks, bsz, int(block_checksum), dst_ptr,

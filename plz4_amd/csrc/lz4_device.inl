@@ -1377,7 +1377,7 @@ DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __rest
         // the offset sits at bytes 1+l, 2+l of the lane's 16: pick the 8-byte word that holds both (l <= 13)
         const uint64_t sel = (l <= 5) ? w0 : (l <= 9 ? ((w0 >> 32) | (w1 << 32)) : w1);
         const int      sft = 8 * (1 + l - (l <= 5 ? 0 : (l <= 9 ? 4 : 8)));
-        const uint32_t o16 = (uint32_t)((sel >> sft) & 0xFFFF);
+        const uint32_t o16 = (uint32_t)((sel >> (sft & 63)) & 0xFFFF);  // (l == 15: sft is 64, the value unused; the shift takes six bits)
         // a long match (nibble 15) with a single extension byte, byte 3+l of the 16 (l <= 12)
         const bool     lng = (mn == 15);
         const int      ek  = 3 + l;
@@ -1765,6 +1765,23 @@ dict_copy:                                                                   // 
     }
     STAT_FLUSH();
     return (int)op;
+}
+
+// ------------------------------------------------------------------------------------------ frame records
+// The head of a frame record, [LE32 size | stored bit][payload][LE32 xxh32?] in recLen bytes (FrameReader._read's checks,
+// blk/frame.go:79-85), for every kernel that parses one: the payload's size, or -1 -- PLZ4HIP_BLK_SIZE_OVERFLOW -- where the record
+// has no room for its size word, the size is above bsz, or payload and checksum do not fit in recLen.  The word is read only when
+// recLen holds it, and a caller reads payload and checksum only behind a size that is not -1: no byte outside the record's recLen
+// is touched.  *word: the size word (stored bit included); a record shorter than four bytes reads as the size no record may have.
+// kUni: the record is the whole wave's (the word is taken from the first lane, as the decoders keep it in scalar registers).
+template <bool kUni>
+DEV int rec_head(const uint8_t* __restrict__ rec, const int64_t recLen, const int bsz, const bool checksum, uint32_t* word)
+{
+    uint32_t w = 0x7FFFFFFFu;
+    if (recLen >= 4) w = kUni ? UNI(ld32u(rec)) : ld32u(rec);
+    *word = w;
+    const int sz = (int)(w & 0x7FFFFFFFu);
+    return (sz > bsz || (int64_t)sz + 4 + (checksum ? 4 : 0) > recLen) ? -1 : sz;
 }
 
 }  // namespace plz4

@@ -40,6 +40,11 @@ DEV bool     dx_slow(uint64_t e) { return (((uint32_t)e) >> 31) != 0u; }
 DEV uint32_t dx_sum(uint64_t e) { return (uint32_t)(e >> 32); }
 DEV int dx_segments(int n) { return n > 0 ? (n + kDxSeg - 1) / kDxSeg : 1; }
 DEV int dx_tail_from(int nseg) { return nseg >= 2 ? nseg - 2 : 0; }           // the last two segments are one unit (the block's end rules)
+// What a call reserves per block (launch_decode; the bounds program of tests/emu allocates exactly this): table entries for blocks
+// of up to maxIn input bytes, pointer entries for outputs of up to maxOut bytes, units.
+static inline size_t dx_t_stride(const int64_t maxIn) { return ((size_t)maxIn + 64 + 63) / 64 * 64; }
+static inline size_t dx_ptr_stride(const int64_t maxOut) { return ((size_t)(maxOut < kDxMaxOut ? maxOut : (int64_t)kDxMaxOut) + 64 + 1023) / 1024 * 1024; }
+static inline int    dx_max_seg(const int64_t maxIn) { return (int)((maxIn + kDxSeg - 1) / kDxSeg); }
 
 // One lane: the sequence that would start at input position p.  *next = where the one behind it starts, *outLen = the bytes it
 // produces.  false: not to be told here (too close to the input's end -- the tail unit walks there itself -- or more than kDxExt
@@ -184,7 +189,7 @@ DEV int dx_plain_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ ds
         const int offAt = LANE + 1 + l;
         const uint64_t sel = (l <= 5) ? w0 : (l <= 9 ? ((w0 >> 32) | (w1 << 32)) : w1);
         const int      sft = 8 * (1 + l - (l <= 5 ? 0 : (l <= 9 ? 4 : 8)));
-        const uint32_t o16 = (uint32_t)((sel >> sft) & 0xFFFF);
+        const uint32_t o16 = (uint32_t)((sel >> (sft & 63)) & 0xFFFF);  // (l == 15: sft is 64, the value unused)
         const bool     lng = (mn == 15);
         const int      ek  = 3 + l;
         const uint32_t e   = (uint32_t)(((ek < 8) ? (w0 >> (8 * ek)) : (w1 >> (8 * (ek & 7)))) & 0xFF);
@@ -535,6 +540,27 @@ DEV int dxl_chain_lo(const int32_t* chainFirst, const int blk0, const int nb, co
 // window (hist, histLen): its result, its status (0: ok), and whether it was a stored block (copied out; it does not enter the
 // window).  DxlFin: what the stage reads beside the DxlCall (checksum verdicts, the blocks' rows of moved flags, the rounds
 // launched) and where the blocks' answers go.
+// Records on this path (k_dx_rec_prep): what the path keeps as a record's length -- the payload's size where the record is a
+// compressed payload of a sane size (FrameReader._read's checks, blk/frame.go:79-85), -1 for a stored block that fits its output,
+// kDxRecBad for a record the frame reader turns away (rec_head's -1, or a stored block above dstCap): both are the one-wave decoder's.
+enum : int { kDxRecBad = -2 };
+DEV int dx_rec_len(const uint8_t* __restrict__ rec, const int64_t recLen, const int bsz, const bool checksum, const int dstCap)
+{
+    uint32_t word;
+    const int sz = rec_head<false>(rec, recLen, bsz, checksum, &word);
+    const bool stored = (word & 0x80000000u) != 0;
+    return (sz < 0 || (stored && sz > dstCap)) ? (int)kDxRecBad : (stored ? -1 : sz);
+}
+// A chain ends at its first bad block.  What is known of that before the decode -- a record in front of block i that the frame
+// reader turns away, or a bad block in an earlier group of a cut call (deadIn) -- keeps the stages off block i (k_dxl_link flags
+// it), so its output stays as it was, as on the one-wave walk; dxl_finish answers it CORRUPT.  first: the chain's first block.
+DEV bool dxl_chain_dead(const int32_t* __restrict__ len, const int first, const int i, const int deadIn)
+{
+    int dead = deadIn;
+    for (int j = first; j < i; ++j) dead |= len[j] == kDxRecBad;
+    return dead != 0;
+}
+
 enum : int { kDxlStCorrupt = 3 };                                   // PLZ4HIP_BLK_CORRUPT: what a block behind a bad block of its chain gets
 
 struct DxlFin {

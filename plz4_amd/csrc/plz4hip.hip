@@ -96,7 +96,7 @@ struct CodecArgs {
     // the staged level-1 parse tells when its block queue has run dry (its last blocks are under way, workgroups begin to leave):
     // gate <- max(gate, gateSeq); the parse of the next call on ANOTHER stream waits for that behind k_parse_gate (launch_l1)
     uint32_t*       gate;       uint32_t gateSeq;
-    const int64_t*  dxSrcOff;   const int32_t* dxLen;                       // records: where a block's payload starts in src and its size (-1: not this path's)
+    const int64_t*  dxSrcOff;   const int32_t* dxLen;                       // records: where a block's payload starts in src and its size (-1: not this path's; -2, kDxRecBad: it fails the frame reader's checks)
     int32_t*        dxHashBad;                                              // records: the payload's xxh32 does not match (k_dx_rec_hash)
     // ... with history outside the block (dxl_*, lz4_dx_device.inl): per block the first block and the number of its chain, its row
     // of moved flags (kDxlMaxRounds + 1), whether the path has answered it; the jump rounds launched
@@ -568,11 +568,11 @@ __device__ __forceinline__ void decode_one_record(const CodecArgs& a, int i, con
     const uint8_t* rec    = a.recOff ? a.src + a.recOff[i] : a.src + (int64_t)i * a.srcStride;
     const int64_t  recLen = a.recOff ? a.recOff[i + 1] - a.recOff[i] : (int64_t)a.srcLen[i];
     uint8_t*       out    = a.dst + (int64_t)i * a.dstStride;
-    const uint32_t word   = plz4_readfirstlane(ld32u(rec));
-    const int      sz     = (int)(word & 0x7FFFFFFFu);
+    uint32_t       word;
+    const int      sz     = rec_head<true>(rec, recLen, a.bsz, a.blockChecksum != 0, &word);
     int st = PLZ4HIP_BLK_OK, r = 0;
     *stored = false;
-    if (sz > a.bsz || (int64_t)sz + 4 + (a.blockChecksum ? 4 : 0) > recLen) {
+    if (sz < 0) {
         st = PLZ4HIP_BLK_SIZE_OVERFLOW;
     } else {
         if (a.blockChecksum) {
@@ -1308,13 +1308,8 @@ __global__ __launch_bounds__(256) void k_dx_rec_prep(CodecArgs a, int64_t* srcOf
     if (i >= a.nBlocks) return;
     const int64_t off = a.recOff ? a.recOff[i] : (int64_t)i * a.srcStride;
     const int64_t recLen = a.recOff ? a.recOff[i + 1] - a.recOff[i] : (int64_t)a.srcLen[i];
-    int n = -1;
-    if (recLen >= 4) {
-        const uint32_t word = ld32u(a.src + off);
-        const int sz = (int)(word & 0x7FFFFFFFu);
-        if (!(word & 0x80000000u) && sz <= a.bsz && (int64_t)sz + 4 + (a.blockChecksum ? 4 : 0) <= recLen) n = sz;
-    }
-    srcOff[i] = off + 4; len[i] = n;
+    // (k_dx_rec_hash reads payload and checksum where this is >= 0; k_dxl_link leaves a chain's blocks behind a kDxRecBad one alone)
+    srcOff[i] = off + 4; len[i] = dx_rec_len(a.src + off, recLen, a.bsz, a.blockChecksum != 0, a.dstCapAll);
 }
 // ... and their block checksums (frame.go:114-127), one wave per record, on a stream of its own beside the decode
 __global__ __launch_bounds__(64) void k_dx_rec_hash(CodecArgs a)
@@ -1364,6 +1359,8 @@ __global__ __launch_bounds__(256) void k_dxl_link(CodecArgs a, unsigned long lon
         if (a.chainFirst) { while (ch + 1 < a.nChains && chain_lo(a, ch + 1) <= i) ++ch; first = chain_lo(a, ch); }
     }
     a.dxlFirst[i] = first; a.dxlChain[i] = ch; a.dxlGood[i] = 0;
+    // (a chain that is known to have ended in front of this block: the stages stay off it, its output stays as it was)
+    if (a.linked && dxl_chain_dead(a.dxLen, first, i, a.dxlDead ? a.dxlDead[ch] : 0)) a.dxInfo[i].bad = 1;
     for (int r = 0; r <= kDxlMaxRounds; ++r) a.dxlMoved[(int64_t)i * (kDxlMaxRounds + 1) + r] = 0;
 }
 __global__ __launch_bounds__(64) void k_dxl_fill(CodecArgs a)
@@ -1464,10 +1461,10 @@ __device__ __forceinline__ void decode_rec_loop(const CodecArgs& a, uint8_t* dl)
         const uint8_t* rec    = a.recOff ? a.src + a.recOff[i] : a.src + (int64_t)i * a.srcStride;
         const int64_t  recLen = a.recOff ? a.recOff[i + 1] - a.recOff[i] : (int64_t)a.srcLen[i];
         uint8_t*       out    = a.dst + (int64_t)i * a.dstStride;
-        const uint32_t word   = plz4_readfirstlane(ld32u(rec));
-        const int      sz     = (int)(word & 0x7FFFFFFFu);
+        uint32_t       word;
+        const int      sz     = rec_head<true>(rec, recLen, a.bsz, a.blockChecksum != 0, &word);
         int st = PLZ4HIP_BLK_OK, r = 0;
-        if (sz > a.bsz || (int64_t)sz + 4 + (a.blockChecksum ? 4 : 0) > recLen) {
+        if (sz < 0) {
             st = PLZ4HIP_BLK_SIZE_OVERFLOW;
         } else {
             // the bulk path: k_rec_verify16 has run in front of this launch and left its verdict; what it rejected is not decoded
@@ -1504,10 +1501,9 @@ __global__ __launch_bounds__(64) void k_rec_verify16(CodecArgs a)
     if (i < a.nBlocks) {
         const uint8_t* rec    = a.recOff ? a.src + a.recOff[i] : a.src + (int64_t)i * a.srcStride;
         const int64_t  recLen = a.recOff ? a.recOff[i + 1] - a.recOff[i] : (int64_t)a.srcLen[i];
-        if (recLen >= 8) {                                                   // (less: no room for the size word and the checksum)
-            const int sz = (int)(ld32u(rec) & 0x7FFFFFFFu);
-            if (sz <= a.bsz && (int64_t)sz + 8 <= recLen) { p[0] = rec + 4; n[0] = sz; want = ld32u(rec + 4 + sz); }
-        }
+        uint32_t word;
+        const int sz = rec_head<false>(rec, recLen, a.bsz, true, &word);
+        if (sz >= 0) { p[0] = rec + 4; n[0] = sz; want = ld32u(rec + 4 + sz); }
     }
     wave_xxh32_x16(p, n, x);
     if ((threadIdx.x & 3u) == 0 && i < a.nBlocks) {
@@ -2586,7 +2582,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
     }
     const int nCh = hist == kHistLinked ? a.nChains : 0;
     const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
-    const size_t tStride = round_up((size_t)maxIn + 64, 64), pStride = round_up((size_t)outB + 64, 1024);
+    const size_t tStride = dx_t_stride(maxIn), pStride = dx_ptr_stride(maxOut);
     // groups: [g0, g1) blocks and [ch0, ch1) chains each
     std::vector<DxlGroup> groups;
     int gMax = nb;
@@ -2617,7 +2613,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
     a.dxInfo = nullptr; a.dxSrcOff = nullptr; a.dxLen = nullptr; a.dxHashBad = nullptr; a.dxlGood = nullptr;
     a.dxlDead = nullptr; a.dxlBlk0 = 0; a.dxlGroup = 0; a.dxlGroups = 0;
     if (dx) {
-        const int maxSeg = (int)((maxIn + kDxSeg - 1) / kDxSeg);
+        const int maxSeg = dx_max_seg(maxIn);
         const size_t wb = (size_t)gMax;                                         // blocks the workspace is laid out for: the call, or one group
         const size_t offPtr = round_up(wb * tStride * 8, 256), offUnits = offPtr + round_up(wb * pStride * 4, 256);
         const size_t offInfo = offUnits + round_up(wb * maxSeg * sizeof(DxUnit), 256), offRec = offInfo + round_up(wb * sizeof(DxInfo), 256);

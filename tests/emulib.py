@@ -23,6 +23,24 @@ def build_emu():
                                "-o", EMU_SO, EMU_SRC])
 
 
+SENTINEL = 0xA5
+
+
+def _guarded(cap: int, slack: int) -> np.ndarray:
+    """A decode destination: max(cap, 1) bytes of zeros and `slack` bytes of sentinel behind them."""
+    dst = np.zeros(max(cap, 1) + slack, dtype=np.uint8)
+    dst[max(cap, 0):] = SENTINEL
+    return dst
+
+
+def _check_guard(dst: np.ndarray, cap: int, what: str):
+    """A decoder writes no byte outside [dst, dst + cap): the bytes behind cap still hold the sentinel."""
+    tail = dst[max(cap, 0):]
+    if not np.all(tail == SENTINEL):
+        at = int(np.flatnonzero(tail != SENTINEL)[0])
+        raise AssertionError("%s wrote %d bytes past its capacity of %d" % (what, at + 1, cap))
+
+
 class Emu:
     def __init__(self):
         build_emu()
@@ -48,8 +66,9 @@ class Emu:
         return r, dst[:max(r, 0)]
 
     def decompress_dict(self, src, cap, dct):
-        dst = np.zeros(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, 32)
         r = int(self.L.emu_decode_block_dict(_ptr(src), src.size, _ptr(dst), cap, _ptr(dct), dct.size))
+        _check_guard(dst, cap, "emu_decode_block_dict")
         return r, dst[:max(r, 0)]
 
     def compress_hc(self, src, cap, level):
@@ -93,8 +112,9 @@ class Emu:
         return r, dst[:max(r, 0)]
 
     def decompress_safe(self, src: np.ndarray, cap: int):
-        dst = np.zeros(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, 32)
         r = int(self.L.emu_decode_block(_ptr(src), src.size, _ptr(dst), cap))
+        _check_guard(dst, cap, "emu_decode_block")
         return r, dst[:max(r, 0)]
 
     def dx_decode(self, src: np.ndarray, cap: int):
@@ -102,9 +122,10 @@ class Emu:
         size -999999: the block is left to the one-wave decoder."""
         self.L.emu_dx_decode.restype = C.c_int
         self.L.emu_dx_decode.argtypes = [u8p, C.c_int, u8p, C.c_int, C.POINTER(C.c_int)]
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, 64)
         rounds = C.c_int(0)
         r = int(self.L.emu_dx_decode(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, C.byref(rounds)))
+        _check_guard(dst, cap, "emu_dx_decode")
         return r, dst[:max(r, 0)], rounds.value
 
     def xxh32(self, a: np.ndarray) -> int:
