@@ -44,6 +44,17 @@
  * to 4 MiB + 8 of output; 0 turns it off) is cut across the whole chip and keeps 8 bytes per input byte + 4 per output byte of
  * the call's blocks (about 50 MiB per 4 MiB block) until plz4hip_ctx_trim; results and error codes are LZ4_decompress_safe's
  * either way (a block that path will not answer for is decoded by the one-wavefront decoder inside the call).
+ * RAW blocks above 4 MiB + 8 of capacity without history outside the block (decompress_batch, dev_decompress, the host layer's
+ * DecompressBlock; a frame's block stops at 4 MiB) take the path as well: a call of up to PLZ4HIP_DX_MAX_BLOCKS blocks whose largest
+ * capacity is above 4 MiB + 8 and at most PLZ4HIP_DX_BIG_MAX_MIB MiB + 8 (default and ceiling 1024; read per call) runs every block
+ * of the call, the small ones beside the large, through the stages cut once more -- the stitch in groups of segments, length bytes
+ * 64 a step, literal runs and matches of 64 KiB or more by the whole grid, ceil(log2(capacity)) + 1 jump rounds.  PLZ4HIP_DX_BIG=0
+ * keeps every block above 4 MiB + 8 on the one-wavefront decoder (for tests and A/B runs).  The workspace is 8 bytes per input byte
+ * + 4 per output byte of the call's largest block per block, and some 3 % of that for the groups and the run list: ONE 1 GiB BLOCK
+ * OF TEXT KEEPS ABOUT 7 GiB (4 GiB of pointers, 8 B x its compressed length), an incompressible one 12 GiB, until plz4hip_ctx_trim;
+ * a workspace that cannot be had leaves the call to one wavefront per block.  Left to the one-wavefront decoder: blocks above the
+ * limit, blocks above 4 MiB under a dictionary (decompress_batch_dict: their pointer space tags bit 31), and every block the path
+ * finds less than plainly valid -- an output beyond the capacity among them.  Records stay at 4 MiB, and so do all encoders.
  * Blocks with history outside the block take the same path under the same conditions (decompress_batch_dict, decode_records_ex
  * with a dictionary and / or linked = 1, decode_records_chains): the call has one pointer space, a match that starts in front of
  * its block points into an earlier block's output, the window the call came in with or the dictionary, and the jump rounds follow
@@ -125,8 +136,9 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
  * a call cut into groups), [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block encoded by
  * the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the staged one-wavefront-per-block
  * route of plz4hip_dev_encode_records_ex / _body_ex (not those the one-kernel encoder took), [9] blocks of at most 4 KiB under a
- * dictionary context encoded by the wave-wide HC parser (levels 2..12).  Returns how many counters there are (10),
- * or PLZ4HIP_E_*. */
+ * dictionary context encoded by the wave-wide HC parser (levels 2..12), [10] raw blocks above 4 MiB + 8 of capacity answered by the
+ * few-block decoder (they count in [3] as well), [11] the jump rounds launched for the last call with such a block, [12] the literal
+ * runs and matches that call handed to its grid-wide stage.  Returns how many counters there are (13), or PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */
@@ -272,6 +284,11 @@ int  plz4hip_ctx_set_content_hash(plz4hip_ctx* ctx, plz4hip_xxh32_stream* h);
  *    Decode (dev_decompress, dev_decode_records*, the decode side of dev_duplex_*), whatever the input holds: a call reads no
  *    byte outside the srcLen[i] bytes of a block / the recOff[i+1] - recOff[i] bytes of a record and the dictionary or the
  *    chain's window, and it writes no byte outside the dstCap bytes of that block's output (and the window).
+ *    plz4hip_dev_decompress does not know the blocks' sizes on the host: the strides bound them.  With nBlocks == 1 strides of zero
+ *    (or small ones) mean a block of at most 6 MiB in and 4 MiB + 8 out, as ever; a caller with ONE block above that passes
+ *    srcStride >= its compressed length and dstStride >= its capacity, which send the call down the few-block path for large blocks
+ *    (see DECODE above).  With several blocks a dstStride above 6 MiB does the same; up to there the call is what it was (4 MiB
+ *    blocks at a padded stride), and a block above 4 MiB + 8 of capacity in it is one wavefront's.
  *    plz4hip_dev_encode_records  : the encode kernel; fills stage + recLen.
  *    plz4hip_dev_compact_records : exclusive scan of recLen -> recOff, then moves every record to body+recOff[i];
  *                                  records that would end past bodyCap are skipped (recOff[nBlocks] > bodyCap tells).

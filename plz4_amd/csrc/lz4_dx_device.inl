@@ -20,7 +20,10 @@
 //                        chain: 8-12 rounds on text, 22 on a 4 MiB run of one byte): every byte then points at the literal it is.
 //   E  dx_gather         out[p] <- out[ptr[p]].
 //
-// Compiled for the CPU as-is by tests/emu (emu_dx_decode) and checked there against the oracle on valid and corrupt blocks.
+// Raw blocks above kDxMaxOut (up to 1 GiB) take the same stages with B cut once more, long runs handed to the whole grid and more
+// jump rounds: dxb_* at the end of this file.
+//
+// Compiled for the CPU as-is by tests/emu (emu_dx_decode, emu_dx_big) and checked there against the oracle on valid and corrupt blocks.
 #pragma once
 #include "lz4_device.inl"
 
@@ -155,6 +158,47 @@ DEV int dx_stitch(const uint8_t* __restrict__ in, const int n, const int cap, co
     return 0;
 }
 
+// ---- Blocks above kDxMaxOut (the big path, dxb_* below): what the fill must not do by itself there.  A literal run or a match of
+// `thr` bytes or more is not executed by the unit that meets it but written down -- kind 0: literals, from = input position;
+// kind 1: a match, from = offset -- and a grid-wide stage behind the fill copies the literals and writes the pointers (dxb_run_piece).
+// A run of L bytes consumes L input or L output bytes, so a block has at most in / thr + out / thr of them: `room` is sized from
+// that, and a unit that finds the list full flags its block.  Length bytes are scanned 64 a step.
+struct DxRun  { uint32_t op, from, len, kind; };
+struct DxRuns { DxRun* list; uint32_t* count; int room; int thr; };
+#if defined(PLZ4_EMU)
+DEV uint32_t dx_count_up(uint32_t* p) { return (*p)++; }
+#else
+DEV uint32_t dx_count_up(uint32_t* p) { return atomicAdd(p, 1u); }
+#endif
+DEV bool dxb_note(const DxRuns* r, const uint32_t kind, const int64_t op, const int64_t from, const int64_t len)
+{
+    uint32_t at = 0;
+    LANES({ if (LANE == 0) at = dx_count_up(r->count); })
+    at = UNI(at);
+    if (at >= (uint32_t)r->room) return false;
+    DxRun x; x.op = (uint32_t)op; x.from = (uint32_t)from; x.len = (uint32_t)len; x.kind = kind;
+    LANES({ if (LANE == 0) r->list[at] = x; })
+    return true;
+}
+// read_more_len (lz4_device.inl) 64 length bytes a step: the first byte that is not 255 ends the length.  No byte at or behind
+// src + n is read; a length that runs there fails as read_more_len's does (its ip has then passed ilimit <= n).
+DEV int64_t dxb_more_len(const uint8_t* __restrict__ src, const int n, int* ip, const int ilimit, const bool initialCheck)
+{
+    int64_t len = 0;
+    if (initialCheck && *ip >= ilimit) return -1;
+    for (;;) {
+        const int q = *ip;
+        LV(uint32_t, b);
+        LANES({ b[I_] = (q + LANE < n) ? (uint32_t)src[q + LANE] : 0u; })
+        const uint64_t ends = BALLOT(b[I_] != 255u);
+        if (!ends) { len += 255 * 64; *ip = q + 64; if (*ip > ilimit) return -1; continue; }
+        const int k = ctz64(ends);
+        len += (int64_t)255 * k + (int64_t)RL(b, k);
+        *ip = q + k + 1;
+        return *ip > ilimit ? -1 : len;
+    }
+}
+
 // a match as pointers: ptr[op + i] = op + i - offset.  An overlapping match (offset < len) points into itself, which is what
 // its bytes are (lz4.c:2406-2414).
 // kHist (blocks with history outside the block, see dxl_* below): a source before the block's start is written down as the distance
@@ -169,6 +213,20 @@ DEV void dx_fill_match(uint32_t* __restrict__ ptr, const int64_t op, const int o
             ptr[op + i] = kHist ? (uint32_t)(sp ^ ((sp >> 31) & 0x7FFFFFFF)) : (uint32_t)sp;
         }
     })
+}
+
+// a literal run / a match of the big path's fill: executed here, or (thr bytes or more) written down; false: the list is full
+DEV bool dxb_put_literals(const DxRuns* runs, uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, const int64_t op, const int ip, const int64_t ll)
+{
+    if (ll >= (int64_t)runs->thr) return dxb_note(runs, 0u, op, ip, ll);
+    wave_copy(dst + op, src + ip, (int)ll);
+    return true;
+}
+DEV bool dxb_put_match(const DxRuns* runs, uint32_t* __restrict__ ptr, const int64_t op, const int offset, const int64_t ml)
+{
+    if (ml >= (int64_t)runs->thr) return dxb_note(runs, 1u, op, offset, ml);
+    dx_fill_match<false>(ptr, op, offset, (int)ml);
+    return true;
 }
 
 // The vector path of the one-wave decoder (wave_decode_plain_batch, lz4_device.inl) with the copies taken out: 64 lanes look at
@@ -269,9 +327,9 @@ DEV int dx_plain_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ ds
 // a match may start up to 65535 bytes before the block.  Its end-of-output test (op + length > oend - LASTLITERALS) is the one the
 // safe loop makes for every match, and the fast loop only sees matches that end 64 bytes before oend; whether the history is long
 // enough for the offset (checkOffset, :2161, :2356) is told by dxl_resolve.
-template <bool kHist = false>
+template <bool kHist = false, bool kBig = false>
 DEV int64_t wave_dx_fill(const uint8_t* __restrict__ src, const int n, uint8_t* __restrict__ dst, const int cap, uint32_t* __restrict__ ptr,
-                         const int ip0, const int64_t op0, const int ipStop, const bool tail)
+                         const int ip0, const int64_t op0, const int ipStop, const bool tail, const DxRuns* runs = nullptr)
 {
     const int iend = n;
     const int64_t oend = cap;
@@ -291,7 +349,7 @@ DEV int64_t wave_dx_fill(const uint8_t* __restrict__ src, const int n, uint8_t* 
         if (fast) {
             bool toSafeLit = false;
             if (ll == 15) {
-                const int64_t a = read_more_len(src, &ip, iend - 15, true);
+                const int64_t a = (kBig ? dxb_more_len(src, iend, &ip, iend - 15, true) : read_more_len(src, &ip, iend - 15, true));
                 if (a < 0) return -1;
                 ll += a;
                 if (op + ll > oend - 32 || (int64_t)ip + ll > iend - 32) toSafeLit = true;
@@ -299,19 +357,19 @@ DEV int64_t wave_dx_fill(const uint8_t* __restrict__ src, const int n, uint8_t* 
                 toSafeLit = true;
             }
             if (toSafeLit) { if (!tail) return -1; fast = false; goto safe_literals; }
-            wave_copy(dst + op, src + ip, (int)ll);
+            if (kBig) { if (!dxb_put_literals(runs, dst, src, op, ip, ll)) return -1; } else wave_copy(dst + op, src + ip, (int)ll);
             ip += (int)ll; op += ll;
             offset = (int)UNI((uint32_t)ld16u(src + ip)); ip += 2;
             mpos = op - offset;
             ml = token & 15;
             if (ml == 15) {
-                const int64_t a = read_more_len(src, &ip, iend - kLastLiterals + 1, false);
+                const int64_t a = (kBig ? dxb_more_len(src, iend, &ip, iend - kLastLiterals + 1, false) : read_more_len(src, &ip, iend - kLastLiterals + 1, false));
                 if (a < 0) return -1;
                 ml += a + kMinMatch;
             } else ml += kMinMatch;
             if (op + ml >= oend - 64) { if (!tail) return -1; fast = false; goto safe_match; }
             if ((!kHist && mpos < 0) || offset == 0) return -1;                // lz4.c:2161
-            dx_fill_match<kHist>(ptr, op, offset, (int)ml);
+            if (kBig) { if (!dxb_put_match(runs, ptr, op, offset, ml)) return -1; } else dx_fill_match<kHist>(ptr, op, offset, (int)ml);
             op += ml;
             continue;
         }
@@ -329,25 +387,25 @@ DEV int64_t wave_dx_fill(const uint8_t* __restrict__ src, const int n, uint8_t* 
             goto match_len;
         }
         if (ll == 15) {
-            const int64_t a = read_more_len(src, &ip, iend - 15, true);
+            const int64_t a = (kBig ? dxb_more_len(src, iend, &ip, iend - 15, true) : read_more_len(src, &ip, iend - 15, true));
             if (a < 0) return -1;
             ll += a;
         }
 safe_literals:
         if (op + ll > oend - kMfLimit || (int64_t)ip + ll > iend - (2 + 1 + kLastLiterals)) {
             if ((int64_t)ip + ll != iend || op + ll > oend) return -1;         // lz4.c:2312-2318
-            wave_copy(dst + op, src + ip, (int)ll);
+            if (kBig) { if (!dxb_put_literals(runs, dst, src, op, ip, ll)) return -1; } else wave_copy(dst + op, src + ip, (int)ll);
             ip += (int)ll; op += ll;
             break;
         }
-        wave_copy(dst + op, src + ip, (int)ll);
+        if (kBig) { if (!dxb_put_literals(runs, dst, src, op, ip, ll)) return -1; } else wave_copy(dst + op, src + ip, (int)ll);
         ip += (int)ll; op += ll;
         offset = (int)UNI((uint32_t)ld16u(src + ip)); ip += 2;
         mpos = op - offset;
         ml = token & 15;
 match_len:
         if (ml == 15) {
-            const int64_t a = read_more_len(src, &ip, iend - kLastLiterals + 1, false);
+            const int64_t a = (kBig ? dxb_more_len(src, iend, &ip, iend - kLastLiterals + 1, false) : read_more_len(src, &ip, iend - kLastLiterals + 1, false));
             if (a < 0) return -1;
             ml += a;
         }
@@ -355,7 +413,7 @@ match_len:
 safe_match:
         if ((!kHist && mpos < 0) || offset == 0) return -1;                    // lz4.c:2356
         if (op + ml > oend - kLastLiterals) return -1;                         // lz4.c:2421-2423 (== :2360-2363 for a match out of the history)
-        dx_fill_match<kHist>(ptr, op, offset, (int)ml);
+        if (kBig) { if (!dxb_put_match(runs, ptr, op, offset, ml)) return -1; } else dx_fill_match<kHist>(ptr, op, offset, (int)ml);
         op += ml;
     }
     return op;
@@ -646,5 +704,150 @@ DEV void dxl_finish(const DxlCall& c, const DxlFin& f, Rec& rec, const int first
     *takenOut = taken; *roundsOut = rounds;
     dxl_walk(c, f, rec, i, last, win0, winA, winB, winLen, dead, winLenIO, deadIO);
 }
+
+// ---- Raw blocks above kDxMaxOut without history outside the block (the big path; launch_decode takes it for a call of few blocks
+// of which one may be larger than that, up to PLZ4HIP_DX_BIG_MAX_MIB).  A, C, D and E are the stages above; what one wave did there
+// for a whole block is cut once more:
+//   B1 dxb_compose     the segments in groups of G: for every position p of a group's FIRST segment, where the chain from p leaves
+//                      the group and the output it passes -- up to G lookups of the base table per position, every position of
+//                      every group at once.  An entry the base table could not tell (slow) stops a composition where it stands.
+//   B2 dxb_hop         one wave per block hops from group to group -- one lookup of the composed table where the chain enters a
+//                      group in its first segment, which is the rule; the base table otherwise -- and writes down where the chain
+//                      enters every group, the tail unit, and whether the output fits the capacity.
+//   B3 dxb_group_units one wave per group walks its own segments with the base table, all groups at once: the units.
+//                      The serial depth is segments / G + G where it was the segments.
+//   C  wave_dx_fill<false, true>: length bytes 64 a step; runs of thr bytes or more are written down, not executed (DxRuns)
+//   C2 dxb_run_piece   the runs, 16 KiB a wave, over the whole grid
+//   D  dx_jump for ceil(log2(output)) + 1 rounds, at most kDxlMaxRounds (16 MiB of one byte value needs 25)
+// Positions are 31-bit (dx_ent), sums 32-bit: a segment passes at most 8192 / 35 x 8179 < 2 MiB of output through sequences the
+// table can tell, a group of at most kDxbMaxGroup segments 512 MiB.
+enum : int { kDxbMaxGroup = 256, kDxbPiece = 16384, kDxbThr = 65536, kDxbTailRoom = 256 };
+struct DxbEntry { int32_t ip, op; };                                       // where the chain enters a group (ip < 0: it does not), the output position there
+struct DxbInfo  { uint32_t runs, pad; uint32_t moved[kDxlMaxRounds + 1]; };
+static inline int    dxb_groups(const int64_t maxSeg, const int G) { return (int)((maxSeg + G - 1) / G); }
+static inline size_t dxb_ptr_stride(const int64_t maxOut) { return ((size_t)maxOut + 64 + 1023) / 1024 * 1024; }
+static inline int    dxb_run_room(const int64_t maxIn, const int64_t maxOut, const int thr) { return (int)(maxIn / thr + maxOut / thr + 2); }
+static inline int    dxb_rounds(const int64_t maxOut) { int r = 1; while (r < kDxlMaxRounds && ((int64_t)1 << (r - 1)) < maxOut) ++r; return r; }
+// the group size a call is laid out for: the power of two next to the square root of its segments
+static inline int    dxb_group_for(const int64_t maxSeg) { int g = 2; while (g < kDxbMaxGroup && (int64_t)g * g < maxSeg) g *= 2; return g; }
+
+// dx_parse_uniform with the length bytes 64 a step
+DEV bool dxb_len_bytes(const uint8_t* __restrict__ in, const int n, int* qq, int64_t* len)
+{
+    for (;;) {
+        const int q = *qq;
+        LV(uint32_t, b);
+        LANES({ b[I_] = (q + LANE + 24 <= n) ? (uint32_t)in[q + LANE] : 256u; })         // (256: the check in front of that byte fails)
+        const uint64_t ends = BALLOT(b[I_] != 255u);
+        if (!ends) { *len += 255 * 64; *qq = q + 64; continue; }
+        const int k = ctz64(ends);
+        const uint32_t v = RL(b, k);
+        if (v > 255u) return false;
+        *len += (int64_t)255 * k + (int64_t)v; *qq = q + k + 1;
+        return true;
+    }
+}
+DEV bool dxb_parse_uniform(const uint8_t* __restrict__ in, const int n, const int e, int* next, int64_t* outLen)
+{
+    if (e + 24 > n) return false;
+    const uint32_t t = UNI((uint32_t)in[e]);
+    int64_t l = (int64_t)(t >> 4); int q = e + 1;
+    if (l == 15 && !dxb_len_bytes(in, n, &q, &l)) return false;
+    if ((int64_t)q + l + 24 > (int64_t)n) return false;
+    q += (int)l;
+    int64_t m = (int64_t)(t & 15u) + kMinMatch;
+    q += 2;
+    if ((t & 15u) == 15u && !dxb_len_bytes(in, n, &q, &m)) return false;
+    // a long sequence that ends within kDxbTailRoom bytes of the input's end: its match may end where the reference has left its fast
+    // loop (less than 64 bytes of output to come), which only the tail unit may walk -- it starts here, then
+    if (q + kDxbTailRoom > n) return false;
+    *next = q; *outLen = l + m;
+    return true;
+}
+
+// B1.  TG[g * kDxSeg + i] for the 64 positions i = 64 * sub + lane of group g's first segment (groups that have all their G
+// segments in front of the tail unit: g < jt / G)
+DEV void dxb_compose(const uint64_t* __restrict__ T, uint64_t* __restrict__ TG, const int n, const int g, const int G, const int sub)
+{
+    const int64_t g0 = (int64_t)g * G * kDxSeg, g1 = g0 + (int64_t)G * kDxSeg;
+    LANES({
+        const int64_t p = g0 + 64 * sub + LANE;
+        if (p < (int64_t)n) {
+            int64_t e = p; uint32_t sum = 0; bool slow = false;
+            while (e < g1 && !slow) { const uint64_t x = T[e]; sum += dx_sum(x); e = (int64_t)dx_exit(x); slow = dx_slow(x); }
+            TG[(int64_t)g * kDxSeg + 64 * sub + LANE] = dx_ent((uint32_t)e, sum, slow);
+        }
+    })
+}
+// the chain from (e, O) on up to `end` (a segment's or a group's end): false when it stands at a sequence that runs into the block's
+// end (everything from there on is the tail unit's).  tg: the composed row of the group that starts at tgFrom and ends at `end`
+// (null: none) -- taken wherever the chain stands in that group's first segment.
+DEV bool dxb_chain_to(const uint8_t* __restrict__ in, const int n, const uint64_t* __restrict__ T, const uint64_t* __restrict__ tg,
+                      const int64_t tgFrom, const int64_t end, int* ep, int64_t* Op)
+{
+    int e = *ep; int64_t O = *Op; bool ok = true;
+    while ((int64_t)e < end) {
+        const bool hop = tg && (int64_t)e >= tgFrom && (int64_t)e < tgFrom + kDxSeg;
+        const uint64_t x = UNI(hop ? tg[(int64_t)e - tgFrom] : T[e]);
+        O += dx_sum(x); e = (int)dx_exit(x);
+        if (dx_slow(x)) {
+            int nx = 0; int64_t ol = 0;
+            if (!dxb_parse_uniform(in, n, e, &nx, &ol)) { ok = false; break; }
+            O += ol; e = nx;
+        }
+    }
+    *ep = e; *Op = O;
+    return ok;
+}
+// B2.  ent[0 .. groups), units[tailFrom].  Returns 0, or 1 when the block is left to the one-wave decoder.
+DEV int dxb_hop(const uint8_t* __restrict__ in, const int n, const int cap, const uint64_t* __restrict__ T, const uint64_t* __restrict__ TG,
+                DxbEntry* ent, DxUnit* units, const int nseg, const int G)
+{
+    if (n <= 0 || cap <= 0) return 1;
+    const int jt = dx_tail_from(nseg), ngrp = (jt + G - 1) / G;
+    int e = 0; int64_t O = 0; bool early = false;
+    for (int g = 0; g < ngrp; ++g) {
+        const int64_t g0 = (int64_t)g * G * kDxSeg, gEnd = (int64_t)min_((g + 1) * G, jt) * kDxSeg;
+        DxbEntry x; x.ip = -1; x.op = 0;
+        if (!early && (int64_t)e < gEnd) {
+            x.ip = e; x.op = (int)O;
+            const bool full = (g + 1) * G <= jt;                             // (the composed table is the group's: all G segments)
+            if (!dxb_chain_to(in, n, T, full ? TG + (int64_t)g * kDxSeg : nullptr, g0, gEnd, &e, &O)) early = true;
+            if (O > (int64_t)cap) return 1;
+        }
+        LANES({ if (LANE == 0) ent[g] = x; })
+    }
+    if (e >= n) return 1;
+    DxUnit u; u.ip = e; u.op = (int)O; u.stop = n; u.pad = 0;
+    LANES({ if (LANE == 0) units[jt] = u; })
+    return 0;
+}
+// B3.  units[j] for group g's segments in front of the tail unit (dx_stitch's loop from the group's entry on)
+DEV void dxb_group_units(const uint8_t* __restrict__ in, const int n, const uint64_t* __restrict__ T, const DxbEntry* ent, DxUnit* units,
+                         const int nseg, const int G, const int g)
+{
+    const int jt = dx_tail_from(nseg), j1 = min_((g + 1) * G, jt);
+    const DxbEntry x = ent[g];
+    int e = UNI(x.ip); int64_t O = UNI(x.op);
+    bool early = e < 0;
+    for (int j = g * G; j < j1; ++j) {
+        const int s1 = (j + 1) * kDxSeg;
+        DxUnit u; u.ip = -1; u.op = 0; u.stop = s1; u.pad = 0;
+        if (!early && e < s1) {
+            u.ip = e; u.op = (int)O;
+            if (!dxb_chain_to(in, n, T, nullptr, 0, s1, &e, &O)) { early = true; u.stop = e; if (u.ip >= e) u.ip = -1; }
+        }
+        LANES({ if (LANE == 0) units[j] = u; })
+    }
+}
+// C2.  Piece c (kDxbPiece bytes) of a run
+DEV void dxb_run_piece(const DxRun& r, const uint32_t c, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint32_t* __restrict__ ptr)
+{
+    const int64_t at = (int64_t)c * kDxbPiece;
+    const int len = (int)min_((int64_t)kDxbPiece, (int64_t)r.len - at);
+    if (r.kind == 0u) wave_copy(dst + r.op + at, src + r.from + at, len);
+    else dx_fill_match<false>(ptr, (int64_t)r.op + at, (int)r.from, len);
+}
+DEV uint32_t dxb_run_pieces(const DxRun& r) { return (r.len + (uint32_t)kDxbPiece - 1u) / (uint32_t)kDxbPiece; }
 
 }  // namespace plz4

@@ -106,6 +106,11 @@ struct CodecArgs {
     // dxlBlk0 comes off it.  dxlDead: per chain, an earlier group has met a bad block of it (null: the call is one group).
     // dxlGroup / dxlGroups: this group's number / how many the call has (0: not a grouped call).
     int32_t*        dxlDead;    int dxlBlk0;    int dxlGroup;   int dxlGroups;
+    // raw blocks above kDxMaxOut (dxb_*, lz4_dx_device.inl): per block the composed rows of its groups of dxbG segments (one row of
+    // kDxSeg entries per group), where the chain enters each group, the list of its long runs (dxbRunRoom entries), its state; the
+    // run threshold and the jump rounds launched
+    uint64_t*       dxbTG;      int64_t dxbTGStride;   DxbEntry* dxbEnt;   int dxbGroups;   int dxbG;
+    DxRun*          dxbRuns;    int dxbRunRoom;   int dxbThr;   DxbInfo* dxbInfo;   int dxbRounds;
 };
 
 __device__ __forceinline__ int next_block(uint32_t* q)
@@ -1300,6 +1305,110 @@ __global__ __launch_bounds__(256) void k_dx_gather(CodecArgs a, unsigned long lo
     dx_gather(a.dst + (int64_t)b * a.dstStride, a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen);
 }
 
+// ---- ... of raw blocks above kDxMaxOut (dxb_*, lz4_dx_device.inl): k_dx_tables as above, then the stitch in three steps, the fill
+// with its long runs written down, the runs over the whole grid, the jump rounds the call's largest capacity asks for, the gather.
+// Kernels of their own: the ones above stay what they are for blocks up to 4 MiB.
+__device__ __forceinline__ bool dxb_misfit(const CodecArgs& a, int b, int n)
+{
+    return dx_segments(n) > a.dxMaxSeg || n > a.dxTStride - 64 || dx_cap(a, b) > a.dxPtrStride - 64;
+}
+__global__ __launch_bounds__(256) void k_dxb_compose(CodecArgs a)
+{
+    const int b = blockIdx.y, w = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);     // 128 waves to a group
+    const int g = w >> 7, sub = w & 127;
+    const int n = dx_len(a, b);
+    if (n <= 0 || dxb_misfit(a, b, n)) return;
+    if ((g + 1) * a.dxbG > dx_tail_from(dx_segments(n))) return;                     // (only groups with all their segments are hopped over)
+    dxb_compose(a.dxT + (int64_t)b * a.dxTStride, a.dxbTG + (int64_t)b * a.dxbTGStride, n, g, a.dxbG, sub);
+}
+__global__ __launch_bounds__(64) void k_dxb_hop(CodecArgs a, unsigned long long* cnt)
+{
+    const int b = blockIdx.x;
+    const int n = dx_len(a, b);
+    const int nseg = dx_segments(n);
+    const int bad = dxb_misfit(a, b, n) ? 1 : dxb_hop(dx_src(a, b), n, dx_cap(a, b), a.dxT + (int64_t)b * a.dxTStride, a.dxbTG + (int64_t)b * a.dxbTGStride,
+                                                      a.dxbEnt + (int64_t)b * a.dxbGroups, a.dxUnits + (int64_t)b * a.dxMaxSeg, nseg, a.dxbG);
+    if ((threadIdx.x & 63u) == 0) {
+        DxInfo inf; inf.bad = bad; inf.outLen = 0; inf.tailFrom = dx_tail_from(nseg); inf.pad = 0;
+        for (int r = 0; r <= kDxRounds; ++r) inf.moved[r] = 0;
+        a.dxInfo[b] = inf;
+        DxbInfo bi; bi.runs = 0; bi.pad = 0;
+        for (int r = 0; r <= kDxlMaxRounds; ++r) bi.moved[r] = 0;
+        a.dxbInfo[b] = bi;
+        if (b == 0) { cnt[11] = (unsigned long long)a.dxbRounds; cnt[12] = 0ull; }   // (plz4hip_ctx_counters: the last call of this kind)
+    }
+}
+__global__ __launch_bounds__(64) void k_dxb_units(CodecArgs a)
+{
+    const int g = blockIdx.x, b = blockIdx.y;
+    if (a.dxInfo[b].bad) return;
+    const int n = dx_len(a, b), nseg = dx_segments(n);
+    if (g * a.dxbG >= dx_tail_from(nseg)) return;
+    dxb_group_units(dx_src(a, b), n, a.dxT + (int64_t)b * a.dxTStride, a.dxbEnt + (int64_t)b * a.dxbGroups,
+                    a.dxUnits + (int64_t)b * a.dxMaxSeg, nseg, a.dxbG, g);
+}
+__global__ __launch_bounds__(64) void k_dxb_fill(CodecArgs a)
+{
+    const int j = blockIdx.x, b = blockIdx.y;
+    DxInfo* const inf = a.dxInfo + b;
+    if (inf->bad || j > inf->tailFrom) return;
+    const int jt = inf->tailFrom;
+    const DxUnit* const units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
+    const DxUnit u = units[j];
+    if (j < jt && u.ip < 0) return;
+    DxRuns runs; runs.list = a.dxbRuns + (int64_t)b * a.dxbRunRoom; runs.count = &a.dxbInfo[b].runs; runs.room = a.dxbRunRoom; runs.thr = a.dxbThr;
+    const int64_t r = wave_dx_fill<false, true>(dx_src(a, b), dx_len(a, b), a.dst + (int64_t)b * a.dstStride, dx_cap(a, b),
+                                                a.dxPtr + (int64_t)b * a.dxPtrStride, u.ip, u.op, u.stop, j == jt, &runs);
+    bool ok = r >= 0;
+    if (ok && j < jt) {                                              // where this unit stops is where the next one starts
+        int k = j + 1; while (k < jt && units[k].ip < 0) ++k;
+        ok = units[k].op == (int)r;
+    }
+    if ((threadIdx.x & 63u) == 0) { if (!ok) atomicOr(&inf->bad, 1); else if (j == jt) inf->outLen = (int)r; }
+}
+__global__ __launch_bounds__(256) void k_dxb_runs(CodecArgs a)
+{
+    const int b = blockIdx.y;
+    if (a.dxInfo[b].bad) return;
+    const uint32_t nr = min_(a.dxbInfo[b].runs, (uint32_t)a.dxbRunRoom);
+    const uint32_t W = gridDim.x * 4u, w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const DxRun* const list = a.dxbRuns + (int64_t)b * a.dxbRunRoom;
+    uint32_t first = w;                                              // the wave that takes a run's first piece moves on from run to run
+    for (uint32_t i = 0; i < nr; ++i) {
+        DxRun r;
+        r.op = plz4_readfirstlane(list[i].op); r.from = plz4_readfirstlane(list[i].from);
+        r.len = plz4_readfirstlane(list[i].len); r.kind = plz4_readfirstlane(list[i].kind);
+        const uint32_t pieces = dxb_run_pieces(r);
+        for (uint32_t c = first; c < pieces; c += W) dxb_run_piece(r, c, dx_src(a, b), a.dst + (int64_t)b * a.dstStride, a.dxPtr + (int64_t)b * a.dxPtrStride);
+        first = (first + W - pieces % W) % W;
+    }
+}
+__global__ __launch_bounds__(256) void k_dxb_jump(CodecArgs a)
+{
+    const int b = blockIdx.y, r = a.dxRound;
+    const DxInfo* const inf = a.dxInfo + b;
+    DxbInfo* const bi = a.dxbInfo + b;
+    if (inf->bad || (r > 0 && !bi->moved[r - 1])) return;
+    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    if (p0 >= outLen) return;
+    if (dx_jump(a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen) && (threadIdx.x & 63u) == 0) bi->moved[r] = 1u;
+}
+__global__ __launch_bounds__(256) void k_dxb_gather(CodecArgs a, unsigned long long* cnt)
+{
+    const int b = blockIdx.y;
+    const DxInfo* const inf = a.dxInfo + b;
+    if (inf->bad) return;
+    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicAdd(&cnt[3], 1ull);                                           // (plz4hip_ctx_counters: blocks this path answered)
+        if (dx_cap(a, b) > kDxMaxOut) { atomicAdd(&cnt[10], 1ull); atomicAdd(&cnt[12], (unsigned long long)min_(a.dxbInfo[b].runs, (uint32_t)a.dxbRunRoom)); }
+        a.result[b] = outLen;
+        if (a.status) a.status[b] = PLZ4HIP_BLK_OK;
+    }
+    if (p0 >= outLen) return;
+    dx_gather(a.dst + (int64_t)b * a.dstStride, a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen);
+}
+
 // records on the few-block path: which records are compressed payloads of a sane size (FrameReader._read's checks, blk/frame.go:
 // 79-85; everything else -- stored blocks, size overflows -- is the one-wave kernel's, which runs for the flagged blocks behind)
 __global__ __launch_bounds__(256) void k_dx_rec_prep(CodecArgs a, int64_t* srcOff, int32_t* len)
@@ -1689,7 +1798,7 @@ struct plz4hip_ctx {
     // [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block (dictionary, linked)
     // encoded by the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the bulk staged
     // route (k_l1x_parse), [9] blocks of at most 4 KiB under a dictionary context encoded by the wave-wide HC parser (k_hcx)
-    static constexpr int kCounters = 10;
+    static constexpr int kCounters = 13;
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
@@ -2612,6 +2721,57 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
     }
     a.dxInfo = nullptr; a.dxSrcOff = nullptr; a.dxLen = nullptr; a.dxHashBad = nullptr; a.dxlGood = nullptr;
     a.dxlDead = nullptr; a.dxlBlk0 = 0; a.dxlGroup = 0; a.dxlGroups = 0;
+    // Raw blocks above 4 MiB + 8 (the raw block API only: a frame's block stops at 4 MiB): a call of few blocks whose largest
+    // capacity is above kDxMaxOut takes the same path with the stages that were one wave per block cut once more (dxb_*,
+    // lz4_dx_device.inl) -- every block of the call, the small ones beside the large.  PLZ4HIP_DX_BIG=0: no such call does (blocks up
+    // to kDxMaxOut of it keep the path above, the others one wave each); PLZ4HIP_DX_BIG_MAX_MIB (default 1024): the largest capacity
+    // bound, + 8, the path is taken for.  PLZ4HIP_DX_BIG_GROUP / PLZ4HIP_DX_BIG_RUN_KIB: segments per group of the stitch (default:
+    // about the square root of the segments) and the length from which a run goes to the grid-wide stage (default 64), for tests
+    // and A/B runs.  The workspace -- 8 B per input byte and 4 B per output byte of the call's strides, 8 B x 8192 per group, 16 B per
+    // segment and per listed run -- is the ctx's dx buffer: kept until plz4hip_ctx_trim.
+    if (!hist && !records && nb <= dxMax && maxOut > (int64_t)kDxMaxOut && maxIn >= 16384) {
+        int64_t bigMax = 1024; bool on = true;
+        if (const char* v = getenv("PLZ4HIP_DX_BIG")) on = atoi(v) != 0;
+        if (const char* v = getenv("PLZ4HIP_DX_BIG_MAX_MIB")) bigMax = atoll(v);
+        if (bigMax > 1024) bigMax = 1024;                                   // (positions are 31-bit)
+        const int64_t capMax = (bigMax << 20) + 8;
+        if (on && maxOut <= capMax && maxIn <= capMax + capMax / 255 + 64) {
+            const int maxSeg = dx_max_seg(maxIn);
+            int G = dxb_group_for(maxSeg), thr = kDxbThr;
+            if (const char* v = getenv("PLZ4HIP_DX_BIG_GROUP")) { const int g = atoi(v); if (g >= 2 && g <= kDxbMaxGroup) G = g; }
+            if (const char* v = getenv("PLZ4HIP_DX_BIG_RUN_KIB")) { const int k = atoi(v); if (k >= 1 && k <= (1 << 20)) thr = k << 10; }
+            const int groups = dxb_groups(maxSeg, G), room = dxb_run_room(maxIn, maxOut, thr), rounds = dxb_rounds(maxOut);
+            const size_t tStrideB = dx_t_stride(maxIn), pStrideB = dxb_ptr_stride(maxOut), tgStride = (size_t)groups * kDxSeg, wb = (size_t)nb;
+            const size_t offPtr = round_up(wb * tStrideB * 8, 256), offUnits = offPtr + round_up(wb * pStrideB * 4, 256);
+            const size_t offInfo = offUnits + round_up(wb * maxSeg * sizeof(DxUnit), 256), offTG = offInfo + round_up(wb * sizeof(DxInfo), 256);
+            const size_t offEnt = offTG + round_up(wb * tgStride * 8, 256), offRuns = offEnt + round_up(wb * groups * sizeof(DxbEntry), 256);
+            const size_t offBi = offRuns + round_up(wb * (size_t)room * sizeof(DxRun), 256), need = offBi + round_up(wb * sizeof(DxbInfo), 256);
+            HIPCHK(c, c->dxOrder.wait(s));
+            bool refused = false;  HIPCHK(c, c->dx.reserve(need, c->dxOrder, &refused));
+            dx = false;                                                         // (no room: one wave per block)
+            if (!refused) {
+                job.arm(c->dxOrder, s);
+                a.dxT = (uint64_t*)c->dx.d; a.dxTStride = (int64_t)tStrideB;
+                a.dxPtr = (uint32_t*)(c->dx.d + offPtr); a.dxPtrStride = (int64_t)pStrideB;
+                a.dxUnits = (DxUnit*)(c->dx.d + offUnits); a.dxMaxSeg = maxSeg;
+                a.dxInfo = (DxInfo*)(c->dx.d + offInfo);
+                a.dxbTG = (uint64_t*)(c->dx.d + offTG); a.dxbTGStride = (int64_t)tgStride;
+                a.dxbEnt = (DxbEntry*)(c->dx.d + offEnt); a.dxbGroups = groups; a.dxbG = G;
+                a.dxbRuns = (DxRun*)(c->dx.d + offRuns); a.dxbRunRoom = room; a.dxbThr = thr;
+                a.dxbInfo = (DxbInfo*)(c->dx.d + offBi); a.dxbRounds = rounds;
+                const int chunks = (int)((maxOut + 1023) / 1024);
+                hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_dxb_compose, dim3(groups * 32, nb), dim3(256), 0, s, a);
+                hipLaunchKernelGGL(k_dxb_hop, dim3(nb), dim3(64), 0, s, a, c->d_counters);
+                hipLaunchKernelGGL(k_dxb_units, dim3(groups, nb), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_dxb_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+                hipLaunchKernelGGL(k_dxb_runs, dim3(1024, nb), dim3(256), 0, s, a);
+                for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxb_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+                hipLaunchKernelGGL(k_dxb_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+                HIPCHK(c, hipGetLastError());
+            }
+        }
+    }
     if (dx) {
         const int maxSeg = dx_max_seg(maxIn);
         const size_t wb = (size_t)gMax;                                         // blocks the workspace is laid out for: the call, or one group
@@ -2895,7 +3055,13 @@ int plz4hip_dev_decompress(plz4hip_ctx* c, int nBlocks, const void* src, int64_t
     a.result = result; a.nBlocks = nBlocks;
     a.dictLen = -1; a.prevTailLen = -1;
     // (the lengths live on the device: the strides bound them)
-    return launch_decode(c, s, a, nBlocks, nBlocks > 1 ? srcStride : (int64_t)(6 << 20), nBlocks > 1 ? dstStride : (int64_t)kDxMaxOut, false);
+    // (one block: the strides are the bounds where they are above the few-block path's defaults -- a caller with one block above
+    // 4 MiB says so by passing strides no smaller than its compressed length and its capacity.  Several blocks: the strides bound
+    // them, as ever; an output stride of up to 6 MiB -- 4 MiB blocks with padding -- says nothing of blocks above kDxMaxOut and the
+    // call is what it was, a larger one sends it down the big path of launch_decode.)
+    const int64_t in1 = srcStride > (int64_t)(6 << 20) ? srcStride : (int64_t)(6 << 20), out1 = dstStride > (int64_t)kDxMaxOut ? dstStride : (int64_t)kDxMaxOut;
+    const int64_t outN = dstStride > (int64_t)(6 << 20) || dstStride < (int64_t)kDxMaxOut ? dstStride : (int64_t)kDxMaxOut;
+    return launch_decode(c, s, a, nBlocks, nBlocks > 1 ? srcStride : in1, nBlocks > 1 ? outN : out1, false);
 }
 
 int plz4hip_dev_encode_records(plz4hip_ctx* c, const void* src, int64_t srcBytes, int bsz, int level,
