@@ -155,6 +155,8 @@ int plz4hip_compress_bound(int n);
  *               decode >= 0 bytes written, < 0 liblz4 error code.
  *    Decode, whatever the input holds: a call reads no byte outside the srcLen[i] bytes of src[i] and the dictionary, and it
  *    writes no byte outside the dstCap[i] bytes of dst[i].
+ *    Encode, whatever its verdict: a call writes no byte outside the dstCap[i] bytes of dst[i] -- a block that does not fit
+ *    (result 0) may leave anything inside them, nothing behind them.
  * ------------------------------------------------------------------------------------------------------- */
 int plz4hip_compress_batch(plz4hip_ctx* ctx, int nBlocks,
                            const void* const* src, const int32_t* srcLen,
@@ -394,6 +396,8 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* ctx, const void* src, int64_t srcByt
 
 /* Raw LZ4 blocks on the device (no record framing): block i = src + i*srcStride (srcLen[i] bytes) ->
  * dst + i*dstStride (capacity dstCap[i]); result[i] as in A, levels 1..12.  srcLen/dstCap/result are device arrays.
+ * Whatever result[i] is, the call writes no byte of dst outside the dstCap[i] bytes at dst + i*dstStride (the rest of a stride
+ * wider than the capacity is left as it was), and none of src.
  * maxLen is a host value the per-block workspaces are sized from, at EVERY level: it must be >= every srcLen[i]; a block whose
  * device-side length is outside [0, maxLen] is not touched and gets result[i] = PLZ4HIP_E_ARG (its neighbours are unaffected).
  * maxLen <= 0 means "unknown to the host": allowed at level 1 only, where it selects the one-kernel encoder that needs no

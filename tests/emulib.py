@@ -24,17 +24,18 @@ def build_emu():
 
 
 SENTINEL = 0xA5
+ENC_SLACK = 64                  # sentinel bytes behind an encoder's capacity
 
 
 def _guarded(cap: int, slack: int) -> np.ndarray:
-    """A decode destination: max(cap, 1) bytes of zeros and `slack` bytes of sentinel behind them."""
+    """A destination of capacity `cap`: max(cap, 1) bytes of zeros and `slack` bytes of sentinel behind them."""
     dst = np.zeros(max(cap, 1) + slack, dtype=np.uint8)
     dst[max(cap, 0):] = SENTINEL
     return dst
 
 
 def _check_guard(dst: np.ndarray, cap: int, what: str):
-    """A decoder writes no byte outside [dst, dst + cap): the bytes behind cap still hold the sentinel."""
+    """Neither a decoder nor an encoder writes a byte outside [dst, dst + cap): the bytes behind cap still hold the sentinel."""
     tail = dst[max(cap, 0):]
     if not np.all(tail == SENTINEL):
         at = int(np.flatnonzero(tail != SENTINEL)[0])
@@ -58,11 +59,12 @@ class Emu:
         L.emu_decode_block_dict.argtypes = [u8p, C.c_int, u8p, C.c_int, u8p, C.c_int]
 
     def compress_dict(self, src, cap, dct, mode, table=None):
-        dst = np.empty(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         tp = table.ctypes.data if table is not None else None
         r = int(self.L.emu_encode_block_dict(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap,
                                              _ptr(dct) if dct is not None and dct.size else C.cast(None, u8p),
                                              0 if dct is None else dct.size, mode, tp))
+        _check_guard(dst, cap, "emu_encode_block_dict")
         return r, dst[:max(r, 0)]
 
     def decompress_dict(self, src, cap, dct):
@@ -74,8 +76,9 @@ class Emu:
     def compress_hc(self, src, cap, level):
         self.L.emu_compress_hc.restype = C.c_int
         self.L.emu_compress_hc.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int]
-        dst = np.empty(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_compress_hc(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, level))
+        _check_guard(dst, cap, "emu_compress_hc")
         return r, dst[:max(r, 0)]
 
     def compress_hc_dict(self, src, cap, level, seg, mode):
@@ -83,10 +86,11 @@ class Emu:
         mode 2: `seg` is the dictionary of an attached context (block <= 4 KiB)."""
         self.L.emu_compress_hc_dict.restype = C.c_int
         self.L.emu_compress_hc_dict.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int]
-        dst = np.empty(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         nul = C.cast(None, u8p)
         r = int(self.L.emu_compress_hc_dict(_ptr(src) if src.size else nul, src.size, _ptr(dst), cap, level,
                                             _ptr(seg) if seg.size else nul, seg.size, mode))
+        _check_guard(dst, cap, "emu_compress_hc_dict")
         return r, dst[:max(r, 0)]
 
     def set_old_dict(self, d: bool):
@@ -99,16 +103,18 @@ class Emu:
 
     def compress_fast(self, src: np.ndarray, cap: int):
         """Level 1 as the kernels run it: parse -> emit for blocks up to 4 MiB, the fused encoder above."""
-        dst = np.empty(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_encode_block(_ptr(src), src.size, _ptr(dst), cap))
+        _check_guard(dst, cap, "emu_encode_block")
         return r, dst[:max(r, 0)]
 
     def compress_fast_fused(self, src: np.ndarray, cap: int):
         """The fused encoder of lz4_device.inl (blocks above 4 MiB; dictionary modes run it in its external-segment form)."""
         self.L.emu_encode_block_fused.restype = C.c_int
         self.L.emu_encode_block_fused.argtypes = [u8p, C.c_int, u8p, C.c_int]
-        dst = np.empty(max(cap, 1) + 32, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_encode_block_fused(_ptr(src), src.size, _ptr(dst), cap))
+        _check_guard(dst, cap, "emu_encode_block_fused")
         return r, dst[:max(r, 0)]
 
     def decompress_safe(self, src: np.ndarray, cap: int):
@@ -135,8 +141,9 @@ class Emu:
         """Level 12 through the three device phases of lz4hc12_device.inl (chain, per-position search, parser)."""
         self.L.emu_compress_hc12.restype = C.c_int
         self.L.emu_compress_hc12.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-        dst = np.empty(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_compress_hc12(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, nc_every, nl, max_segs, min_seg))
+        _check_guard(dst, cap, "emu_compress_hc12")
         return r, dst[:max(r, 0)]
 
     def hc12_search_check(self, src):
@@ -149,8 +156,9 @@ class Emu:
         """Levels 3..9 as the kernels run them: segments walked independently, stitched, record emit (lz4hc_lazy_device.inl)."""
         self.L.emu_compress_hc_lazy.restype = C.c_int
         self.L.emu_compress_hc_lazy.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int]
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_compress_hc_lazy(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, level, max_segs, min_seg))
+        _check_guard(dst, cap, "emu_compress_hc_lazy")
         return r, dst[:max(r, 0)]
 
     def compress_hc_lazy_ext(self, src, cap, level, seg, max_segs=1, min_seg=65536):
@@ -160,41 +168,46 @@ class Emu:
             return self.compress_hc_mid_ext(src, cap, seg)
         self.L.emu_compress_hc_lazy_ext.restype = C.c_int
         self.L.emu_compress_hc_lazy_ext.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int, C.c_int]
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         nul = C.cast(None, u8p)
         r = int(self.L.emu_compress_hc_lazy_ext(_ptr(src) if src.size else nul, src.size, _ptr(dst), cap, level,
                                                 _ptr(seg) if seg.size else nul, seg.size, max_segs, min_seg))
+        _check_guard(dst, cap, "emu_compress_hc_lazy_ext")
         return r, dst[:max(r, 0)]
 
     def compress_hc_mid_ext(self, src, cap, seg):
         """Level 2 behind an external segment as the kernels run it (hc_mid_parse<true>: tables primed over the segment)."""
         self.L.emu_compress_hc_mid_ext.restype = C.c_int
         self.L.emu_compress_hc_mid_ext.argtypes = [u8p, C.c_int, u8p, C.c_int, u8p, C.c_int]
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         nul = C.cast(None, u8p)
         r = int(self.L.emu_compress_hc_mid_ext(_ptr(src) if src.size else nul, src.size, _ptr(dst), cap, _ptr(seg) if seg.size else nul, seg.size))
+        _check_guard(dst, cap, "emu_compress_hc_mid_ext")
         return r, dst[:max(r, 0)]
 
     def compress_hc_mid(self, src, cap):
         """Level 2 as the kernels run it: batches of a literal run over the two tables, records, emit (lz4hc_lazy_device.inl)."""
         self.L.emu_compress_hc_mid.restype = C.c_int
         self.L.emu_compress_hc_mid.argtypes = [u8p, C.c_int, u8p, C.c_int]
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_compress_hc_mid(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap))
+        _check_guard(dst, cap, "emu_compress_hc_mid")
         return r, dst[:max(r, 0)]
 
     def compress_hc_pre(self, src, cap, level):
         """HC levels 3..11 with the chain built up front (what the kernels run for independent blocks without dictionary)."""
         self.L.emu_compress_hc_pre.restype = C.c_int
         self.L.emu_compress_hc_pre.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int]
-        dst = np.empty(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_compress_hc_pre(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, level))
+        _check_guard(dst, cap, "emu_compress_hc_pre")
         return r, dst[:max(r, 0)]
 
     def compress_hc_lists(self, src, cap, level):
         """HC levels on the chain AND the per-hash lists built up front (levels 4..12: up to 63 candidates per round)."""
         self.L.emu_compress_hc_lists.restype = C.c_int
         self.L.emu_compress_hc_lists.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int]
-        dst = np.empty(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_compress_hc_lists(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, level))
+        _check_guard(dst, cap, "emu_compress_hc_lists")
         return r, dst[:max(r, 0)]

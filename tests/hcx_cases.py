@@ -148,7 +148,8 @@ def fuzz_cases():
     out = []
     for i in range(FUZZ_BLOCKS):
         n = int(rng.integers(0, 4097)) if i >= 4 else (0, 4096, 13, 12)[i]
-        buf = np.empty(n + 600, np.uint8)
+        buf = np.empty(n + 600, np.uint8)                   # (the block being spliced: the last piece may run past n.  No encoder
+                                                            # writes here -- HcxEmu.compress has its own guarded destination)
         at = 0
         while at < n:
             kind = int(rng.integers(0, 4))

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import corpus
+from emulib import ENC_SLACK, _check_guard, _guarded
 from orclib import ROOT, _ptr, u8p
 from plz4_amd import synth
 
@@ -35,11 +36,12 @@ class FxEmu:
         L.emu_fx_set_descending.argtypes = [C.c_int]
 
     def encode(self, src, cap, piece_kib=64, warm_kib=64, order=0, records=False):
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         st = (C.c_longlong * 4)()
         seq = np.zeros(src.size // 4 + 2, dtype=np.uint64) if records else None
         r = int(self.L.emu_fx_encode(_ptr(src), src.size, _ptr(dst), cap, piece_kib << 10, warm_kib << 10, order, st,
                                      seq.ctypes.data if records else None))
+        _check_guard(dst, cap, "emu_fx_encode")
         stats = {"rounds": st[0], "again": st[1], "pieces": st[2], "nseq": st[3]}
         return r, dst[:max(r, 0)], stats, (seq[:st[3]] if records and r >= 0 else None)
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import corpus
+from emulib import ENC_SLACK, _check_guard, _guarded
 from orclib import ROOT, _ptr, u8p
 from plz4_amd import synth
 
@@ -49,10 +50,11 @@ class FxlEmu:
                 seg, table = d64, C.cast(C.byref(dctx), C.c_void_p)
         else:
             mode = NONE if raw else FRESH
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         st = (C.c_longlong * 5)()
         r = int(self.L.emu_fxl_encode(_ptr(src) if n else C.cast(None, u8p), n, _ptr(seg), 0 if seg is None else seg.size, mode, table,
                                       _ptr(dst), cap, piece_kib << 10, warm_kib << 10, order, st))
+        _check_guard(dst, cap, "emu_fxl_encode")
         return r, dst[:max(r, 0)], {"rounds": st[0], "again": st[1], "pieces": st[2], "nseq": st[3], "path": st[4]}
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import hcx_cases as hc
+from emulib import ENC_SLACK, _check_guard, _guarded
 from orclib import ROOT, _ptr, u8p
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_hcx.cpp")
@@ -31,14 +32,14 @@ class HcxEmu:
         L.emu_hcx_set_descending.argtypes = [C.c_int]
 
     def compress(self, src, cap, level, dct, descending=False):
-        dst = np.full(max(cap, 1) + 32, 0xA7, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         nul = C.cast(None, u8p)
         self.L.emu_hcx_set_descending(int(descending))
         try:
             r = int(self.L.emu_hcx_compress(_ptr(src) if src.size else nul, src.size, _ptr(dst), cap, level, _ptr(dct) if dct.size else nul, dct.size))
         finally:
             self.L.emu_hcx_set_descending(0)
-        assert np.all(dst[max(cap, 0):] == 0xA7), "wrote past the capacity"
+        _check_guard(dst, cap, "emu_hcx_compress")
         return r, dst[:max(r, 0)]
 
 

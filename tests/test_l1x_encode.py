@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from emulib import ENC_SLACK, SENTINEL
 from orclib import ROOT, _ptr, u8p
 from plz4_amd import synth
 
@@ -35,8 +36,8 @@ class L1xEmu:
     def encode(self, buf, total, bsz, dct=None, dctx=None, prev_tail=None, order=0):
         """buf: PAD bytes of scratch, `total` bytes of plaintext, room to read past the end.  Returns the blocks' (ret, bytes)."""
         nb = -(-total // bsz)
-        stride = bsz + 64
-        dst = np.zeros(max(nb, 1) * stride, dtype=np.uint8)
+        stride = bsz + ENC_SLACK                                         # block i's capacity is bsz: sentinel bytes behind it
+        dst = np.full(max(nb, 1) * stride, SENTINEL, dtype=np.uint8)
         res = np.zeros(max(nb, 1), dtype=np.int32)
         d64 = None if dct is None else np.ascontiguousarray(dct[-65536:])
         null = C.cast(None, u8p)
@@ -45,6 +46,8 @@ class L1xEmu:
                                    int(dct is not None), null if prev_tail is None or not prev_tail.size else _ptr(prev_tail),
                                    -1 if prev_tail is None else prev_tail.size, _ptr(dst), stride, res.ctypes.data_as(i32p), order)
         assert rc == 0, rc
+        for i in range(nb):
+            assert np.all(dst[i * stride + bsz:(i + 1) * stride] == SENTINEL), "emu_l1x_encode wrote past block %d's capacity of %d" % (i, bsz)
         return [(int(res[i]), dst[i * stride:i * stride + max(int(res[i]), 0)].copy()) for i in range(nb)]
 
 

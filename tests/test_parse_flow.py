@@ -14,6 +14,7 @@ import pytest
 
 import corpus
 import pwcases
+from emulib import ENC_SLACK, _check_guard, _guarded
 from orclib import ROOT, _ptr, u8p
 from plz4_amd import synth
 
@@ -52,14 +53,16 @@ class PfEmu:
         return {k: int(out[i]) for k, i in CNT.items()}
 
     def encode(self, src, cap, win):
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         r = int(self.L.emu_pf_encode(_ptr(src), src.size, _ptr(dst), cap, win))
+        _check_guard(dst, cap, "emu_pf_encode")
         return r, dst[:max(r, 0)]
 
     def fx_encode(self, src, cap, piece_kib, warm_kib):
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         rounds = C.c_int(0)
         r = int(self.L.emu_pf_fx_encode(_ptr(src), src.size, _ptr(dst), cap, piece_kib << 10, warm_kib << 10, C.byref(rounds)))
+        _check_guard(dst, cap, "emu_pf_fx_encode")
         return r, dst[:max(r, 0)], rounds.value
 
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import hopcases
+from emulib import ENC_SLACK, _check_guard, _guarded
 from orclib import ROOT, _ptr, u8p
 from plz4_amd import synth
 
@@ -52,10 +53,11 @@ class PhEmu:
         return {k: int(cnt[i]) for k, i in CNT.items()}, [int(v) for v in hops]
 
     def encode(self, src, cap, win):
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         seq = np.zeros(src.size // 4 + 3, dtype=np.uint64)
         ns = C.c_int(0)
         r = int(self.L.emu_ph_encode(_ptr(src), src.size, _ptr(dst), cap, win, seq.ctypes.data, C.byref(ns)))
+        _check_guard(dst, cap, "emu_ph_encode")
         return r, dst[:max(r, 0)], seq[:ns.value]
 
 

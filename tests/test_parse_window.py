@@ -12,6 +12,7 @@ import pytest
 
 import corpus
 import pwcases
+from emulib import ENC_SLACK, _check_guard, _guarded
 from orclib import ROOT, _ptr, u8p
 from plz4_amd import synth
 
@@ -50,11 +51,12 @@ class PwEmu:
         return {k: int(out[i]) for k, i in CNT.items()}
 
     def encode(self, src, cap, win, records=False):
-        dst = np.zeros(max(cap, 1) + 64, dtype=np.uint8)
+        dst = _guarded(cap, ENC_SLACK)
         seq = np.zeros(src.size // 4 + 3, dtype=np.uint64) if records else None
         ns = C.c_int(0)
         r = int(self.L.emu_pw_encode(_ptr(src) if src.size else C.cast(None, u8p), src.size, _ptr(dst), cap, win,
                                      seq.ctypes.data if records else None, C.byref(ns)))
+        _check_guard(dst, cap, "emu_pw_encode")
         return r, dst[:max(r, 0)], (seq[:ns.value] if records else None)
 
 
