@@ -503,6 +503,13 @@ class MultiEngine:
         self._chk(self.L.plz4hip_mgpu_compress_batch(self.h, n, _ptr_array(srcs), _i32p(lens), _ptr_array(dsts), _i32p(cp), level, _i32p(res)))
         return res[:n], [d[:max(int(r), 0)] for d, r in zip(dsts, res[:n])]
 
+    def decompress_batch(self, srcs, caps):
+        n = len(srcs)
+        dsts = [np.zeros(max(int(c), 1), dtype=np.uint8) for c in caps]
+        lens = _i32([s.size for s in srcs]); cp = _i32(caps); res = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self.L.plz4hip_mgpu_decompress_batch(self.h, n, _ptr_array(srcs), _i32p(lens), _ptr_array(dsts), _i32p(cp), _i32p(res)))
+        return res[:n], [d[:max(int(r), 0)] for d, r in zip(dsts, res[:n])]
+
     def dev_encode_frame(self, shard_ptrs, shard_bytes, nblocks, bsz, block_checksum, owner, body_ptr, body_cap, level=1):
         sp = (C.c_void_p * self.g)(*shard_ptrs); sb = (C.c_int64 * self.g)(*shard_bytes)
         off = (C.c_int64 * (nblocks + 1))(); total = C.c_int64()

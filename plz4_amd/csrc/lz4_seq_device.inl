@@ -532,6 +532,11 @@ DEV int wave_parse_l1_tt(const uint8_t* __restrict__ src, const int n, void* tab
                         if (w >= 64) break;
                     }
                     eL = RL(eLane, 63 - __builtin_clzll(mm));
+                    // A match measured by an EARLIER round keeps its length and is no longer special: this round hops through it
+                    // and must still see that it ends the block (a short match never does: p + 36 <= n - 125, see above).  Without
+                    // this the batch left with a re-test pending at ip >= lastProbe, which the generic batch then executed:
+                    // one match too many inside the block's last twelve bytes, a block no decoder accepts.
+                    finished = (base + eL >= lastProbe) ? 1 : finished;
                 }
                 const unsigned long long tw2 = STAT_NOW(); (void)tw2;
                 STAT(P_CYC_HOP, tw2 - tw1);

@@ -28,6 +28,21 @@ def test_mgpu_host_buffers(orc, g):
     for s, cap, r, o in zip(srcs, caps, res, outs):
         n, want = orc.compress_fast(s, cap)
         assert int(r) == n and np.array_equal(o, want[:n])
+    # ... and back through plz4hip_mgpu_decompress_batch, one block damaged: its code is the oracle's, the others are unaffected
+    comps = [np.ascontiguousarray(o).copy() for o in outs]
+    comps[7][comps[7].size // 2] ^= 0x40
+    dcaps = [s.size for s in srcs]
+    res, outs = m.decompress_batch(comps, dcaps)
+    codes = []
+    for i, (cp, cap, r, o) in enumerate(zip(comps, dcaps, res, outs)):
+        n, want = orc.decompress_safe(cp, cap)
+        codes.append(n)
+        assert int(r) == n, (i, int(r), n)
+        if n >= 0:
+            assert np.array_equal(o, want[:n]), i
+        if i != 7:
+            assert n == srcs[i].size and np.array_equal(o, srcs[i]), i
+    assert codes[7] < 0 or not np.array_equal(outs[7], srcs[7])                  # (the damage shows)
     assert m.encode_records([], bsz, True) == []
     m.close()
 
