@@ -29,6 +29,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4hcx_device.inl"
 #include "lz4_dx_device.inl"
 #include "lz4_fx_device.inl"
+#include "ws_layout.h"
 
 namespace {
 
@@ -1889,8 +1890,6 @@ inline hipError_t copy_sync(plz4hip_ctx* c, void* dst, const void* src, size_t n
     return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 int ensure_slot(plz4hip_ctx* c, int i, size_t hostBytes, size_t devBytes)
 {
     plz4hip_ctx::HostSlot& sl = c->slot[i];
@@ -1969,41 +1968,18 @@ int reserve_h12(plz4hip_ctx* c, size_t need, bool* refused)
     return PLZ4HIP_OK;
 }
 
-// What an HC call may take for its per-block workspaces (chains, lists, search results) when PLZ4HIP_HC_BUDGET_GIB does not say:
-// a quarter of what is free, at most 64 GiB.  A library call that by default walks off with most of the card is not a drop-in
-// (round 2 took three quarters); callers that own the GPU raise the budget, and plz4hip_ctx_trim gives the memory back.  More
-// blocks per group is faster for these kernels (they live on blocks in flight), so a dedicated machine should set it.
-size_t hc_default_budget(size_t freeBytes) { const size_t q = freeBytes / 4, cap = (size_t)64 << 30; return q < cap ? q : cap; }
-
-// Level 12 on independent blocks without dictionary runs in three phases per group of blocks (lz4hc12_device.inl):
-// chain -> search results -> parser.  Per block the group workspace holds the chain (2 B per position) and F (8 B per
-// position); the group size follows from the memory set aside (PLZ4HIP_HC12_GROUP overrides, for tests).
-struct H12Plan { int64_t chainStride, fStride; size_t perBlock; int group; size_t offRank, offList, offOffsets, offF, offWs, offErr, total;
-                 int maxChunks; size_t offInfo, offChunkB, offChunkO;       // (the emit stage's small arrays: levels 3..9)
-                 int64_t recStride; size_t offRec, offBridge, offMeta, offStarts, offPieces; };   // (segments: levels 3..9)
-constexpr int kLzMaxSegs = 512;
-int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, H12Plan* pl, bool lazy, bool needF)
+// Level 12 on independent blocks without dictionary, levels 3..11 and the external-segment route: the group workspace of c->h12
+// (HcLayout, ws_layout.h).  The group size follows from the memory set aside: hc_default_budget of what is free (and whatever the
+// ctx holds already) unless PLZ4HIP_HC_BUDGET_GIB says more: the parser runs one wave per block, so the more blocks a group has (up
+// to three waves per SIMD: 3072), the better its latency is hidden -- 4096 blocks in two groups of 2048 instead of four of 1024:
+// 1418 -> 1664 MiB/s.  PLZ4HIP_HC12_GROUP overrides, for tests.  plz4hip_ctx_trim gives the memory back.
+int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, HcLayout* pl, bool lazy, bool needF)
 {
-    pl->chainStride = (int64_t)round_up((size_t)maxLen + 1, 1024);
-    pl->fStride = (int64_t)round_up((size_t)(maxLen > 11 ? maxLen - 11 : 1), 64);
-    if (!needF) pl->fStride = (int64_t)round_up((size_t)maxLen / 4 + 64, 64);        // no search results there: only the block's final records
-    pl->maxChunks = (int)((round_up((size_t)maxLen / 4 + 3, 64) + kSeqChunk - 1) / kSeqChunk);
-    pl->perBlock = (size_t)pl->chainStride * 2 + (size_t)pl->chainStride * 4 + ((size_t)pl->chainStride + 8) * 4 + (size_t)kHcHashEntries * 4 + (size_t)pl->fStride * 8
-                 + sizeof(SeqInfo) + (size_t)pl->maxChunks * 8;
-    pl->recStride = (int64_t)round_up((size_t)maxLen / 4 + (size_t)kLzMaxSegs * 80, 64);
-    if (lazy) pl->perBlock += (size_t)pl->recStride * 16 + (size_t)kLzMaxSegs * (sizeof(LzSegMeta) + kLzStarts * 8 + 2 * sizeof(LzPiece));
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-    // hc_default_budget of what is free (and whatever the ctx holds already) unless PLZ4HIP_HC_BUDGET_GIB says more: the parser runs
-    // one wave per block, so the more blocks a group has (up to three waves per SIMD: 3072), the better its latency is hidden --
-    // 4096 blocks in two groups of 2048 instead of four of 1024: 1418 -> 1664 MiB/s.  plz4hip_ctx_trim gives the memory back.
-    size_t budget = hc_default_budget(freeB + c->h12.bytes);
-    if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) { const long g = atol(v); if (g >= 1) budget = (size_t)g << 30; }
-    if (budget < c->h12.bytes) budget = c->h12.bytes;
-    int64_t grp = (int64_t)(budget / pl->perBlock);
-    if (const char* v = getenv("PLZ4HIP_HC12_GROUP")) { const int gv = atoi(v); if (gv >= 1) grp = gv; }
-    if (grp < 1) grp = 1;
-    if (grp > nBlocks) grp = nBlocks;
+    long budgetGiB = 0;  int group = 0;
+    if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) budgetGiB = atol(v);
+    if (const char* v = getenv("PLZ4HIP_HC12_GROUP")) group = atoi(v);
     if (!c->h12ParseWaves) {
         int per = 0, perSeg = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_hc12_parse, 64, 0) != hipSuccess || per < 1) per = 8;
@@ -2011,38 +1987,46 @@ int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, H12Plan* pl, bool lazy, bo
         c->h12SegWaves = c->cus * perSeg;
         c->h12ParseWaves = c->cus * (per > perSeg ? per : perSeg);           // (sizes the waves' global price-table slots: the larger of the two grids)
     }
-    for (;;) {
-        {   // groups of equal size: what is allocated is what one of them needs, whatever the budget would allow
-            const int64_t nGroups = (nBlocks + grp - 1) / grp;
-            pl->group = (int)((nBlocks + nGroups - 1) / nGroups);
-        }
-        // [0, 256): the error flag (zeroed when the workspace is allocated, sticky); the chains start behind it
-        pl->offRank = 256 + round_up((size_t)pl->group * (size_t)pl->chainStride * 2, 256);
-        pl->offList = pl->offRank + round_up((size_t)pl->group * (size_t)pl->chainStride * 4, 256);
-        pl->offOffsets = pl->offList + round_up((size_t)pl->group * ((size_t)pl->chainStride + 8) * 4, 256);
-        pl->offF = pl->offOffsets + round_up((size_t)pl->group * (size_t)kHcHashEntries * 4, 256);
-        pl->offWs = pl->offF + round_up((size_t)pl->group * (size_t)pl->fStride * 8, 256);
-        pl->offErr = 0;
-        pl->offInfo = pl->offWs + round_up((size_t)c->h12ParseWaves * kHc12WsGlobalBytes, 256);
-        pl->offChunkB = pl->offInfo + round_up((size_t)pl->group * sizeof(SeqInfo), 256);
-        pl->offChunkO = pl->offChunkB + round_up((size_t)pl->group * (size_t)pl->maxChunks * 4, 256);
-        pl->offRec = pl->offChunkO + round_up((size_t)pl->group * (size_t)pl->maxChunks * 4, 256);
-        pl->total = pl->offRec;
-        if (lazy) {
-            pl->offBridge = pl->offRec + round_up((size_t)pl->group * (size_t)pl->recStride * 8, 256);
-            pl->offMeta = pl->offBridge + round_up((size_t)pl->group * (size_t)pl->recStride * 8, 256);
-            pl->offStarts = pl->offMeta + round_up((size_t)pl->group * kLzMaxSegs * sizeof(LzSegMeta), 256);
-            pl->offPieces = pl->offStarts + round_up((size_t)pl->group * kLzMaxSegs * kLzStarts * 8, 256);
-            pl->total = pl->offPieces + round_up((size_t)pl->group * kLzMaxSegs * 2 * sizeof(LzPiece), 256);
-        }
+    const size_t perBlock = hc_layout(1, maxLen, lazy, needF, c->h12ParseWaves).perBlock;
+    int rc = PLZ4HIP_OK;
+    // groups of equal size: what is allocated is what one of them needs, whatever the budget would allow
+    const int got = fit_groups(nBlocks, hc_first_group(freeB, c->h12.bytes, budgetGiB, group, perBlock, nBlocks), true, [&](int per, bool* refused) {
+        *pl = hc_layout(per, maxLen, lazy, needF, c->h12ParseWaves);
         if (getenv("PLZ4HIP_VERBOSE"))
             fprintf(stderr, "plz4hip: level 12, %d blocks: free %zu MiB, held %zu MiB, groups of %d (%zu MiB)\n", nBlocks, freeB >> 20, c->h12.bytes >> 20, pl->group, pl->total >> 20);
-        bool refused = false;  if (int rc = reserve_h12(c, pl->total, &refused)) return rc;
-        if (!refused) break;
-        if (grp <= 1) return fail(c, PLZ4HIP_E_NOMEM, "level-12 workspace");
-        grp = (grp + 1) / 2;                                                  // refused: smaller groups
-    }
-    return PLZ4HIP_OK;
+        return reserve_h12(c, pl->total, refused);
+    }, &rc);
+    if (rc) return rc;
+    return got ? PLZ4HIP_OK : fail(c, PLZ4HIP_E_NOMEM, "level-12 workspace");
+}
+
+// The pointers of a group workspace at `base`, every per-block array moved on by k blocks (the half a group of an overlapped call uses)
+void bind_hc(CodecArgs& a, uint8_t* base, const HcLayout& L, bool segs, int64_t k)
+{
+    a.h12ChainStride = L.chainStride; a.h12FStride = L.fStride;
+    a.h12Chain = (uint16_t*)(base + L.offChain) + k * L.chainStride;
+    a.h12Rank = (uint32_t*)(base + L.offRank) + k * L.chainStride;
+    a.h12List = (uint32_t*)(base + L.offList) + k * (L.chainStride + 8);
+    a.h12Offsets = (uint32_t*)(base + L.offOffsets) + k * kHcHashEntries;
+    a.h12F = (Hc12F*)(base + L.offF) + k * L.fStride;
+    a.h12Ws = base + L.offWs; a.h12Err = (int32_t*)(base + L.offErr);
+    if (!segs) return;
+    a.l1Seq = (uint64_t*)a.h12F; a.l1SeqStride = L.fStride; a.l1MaxChunks = L.maxChunks; a.l1Bk = nullptr;
+    a.l1Info = (SeqInfo*)(base + L.offInfo) + k;
+    a.l1ChunkBytes = (uint32_t*)(base + L.offChunkB) + k * L.maxChunks; a.l1ChunkOff = (uint32_t*)(base + L.offChunkO) + k * L.maxChunks;
+    a.lzRecStride = L.recStride;
+    a.lzRec = (uint64_t*)(base + L.offRec) + k * L.recStride; a.lzBridge = (uint64_t*)(base + L.offBridge) + k * L.recStride;
+    a.lzMeta = (LzSegMeta*)(base + L.offMeta) + k * kLzMaxSegs; a.lzStarts = (uint64_t*)(base + L.offStarts) + k * kLzMaxSegs * kLzStarts;
+    a.lzPieces = (LzPiece*)(base + L.offPieces) + k * 2 * kLzMaxSegs;
+}
+
+// ... and of the chain (and lists) built up front for the one-thread parsers
+void bind_hc_pre(CodecArgs& a, uint8_t* base, const HcPreLayout& L, bool lists)
+{
+    a.h12Chain = (uint16_t*)(base + L.offChain); a.h12ChainStride = L.stride;
+    a.h12Rank = lists ? (uint32_t*)(base + L.offRank) : nullptr;
+    a.h12List = lists ? (uint32_t*)(base + L.offList) : nullptr;
+    a.h12Offsets = lists ? (uint32_t*)(base + L.offOffsets) : nullptr;
 }
 
 // (blocks of 8 MiB and more -- raw block API only -- keep the one-thread-per-block kernel: the writer packs positions into 23 bits)
@@ -2158,16 +2142,13 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
     if (lazy || use_h12(a, maxLen)) {
         // level 12 up to 4 MiB: its parser in segments as well (records; larger raw blocks keep the one-wave parser that writes bytes)
         const bool seg12 = !lazy && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC12_SEG_OFF") == nullptr;
-        H12Plan pl;
-        if (int rc = plan_h12(c, nb, maxLen + (lazyEx ? 65536 : 0), &pl, lazy || seg12, !lazy)) return rc;
+        const bool segs = lazy || seg12;
+        HcLayout pl;
+        if (int rc = plan_h12(c, nb, maxLen + (lazyEx ? 65536 : 0), &pl, segs, !lazy)) return rc;
         if (lazyEx) { if (int rc = prep_ext()) return rc; }
-        a.h12Chain = (uint16_t*)(c->h12.d + 256); a.h12ChainStride = pl.chainStride;
-        a.h12Rank = (uint32_t*)(c->h12.d + pl.offRank); a.h12List = (uint32_t*)(c->h12.d + pl.offList);
-        a.h12Offsets = (uint32_t*)(c->h12.d + pl.offOffsets);
-        a.h12F = (Hc12F*)(c->h12.d + pl.offF); a.h12FStride = pl.fStride;
-        a.h12Ws = c->h12.d + pl.offWs; a.h12Err = (int32_t*)(c->h12.d + pl.offErr); c->h12ErrOff = pl.offErr;
+        c->h12ErrOff = pl.offErr;
         a.rawMode = rawMode;
-        if (lazy || seg12) {
+        if (segs) {
             if (lazy && a.level >= 10) { if (int rc = ensure_hc(c)) return rc; a.hcWork = c->hc.d; }
             if (!c->hcLazyWaves) {
                 int per = 0;
@@ -2176,17 +2157,14 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_hc_lazy<true>, 64, 0) != hipSuccess || per < 1) per = 8;
                 c->hcLazyExWaves = c->cus * per;
             }
-            a.l1MaxLen = maxLen; a.l1Seq = (uint64_t*)a.h12F; a.l1SeqStride = pl.fStride; a.l1MaxChunks = pl.maxChunks; a.l1Bk = nullptr;
-            a.l1Info = (SeqInfo*)(c->h12.d + pl.offInfo);
-            a.l1ChunkBytes = (uint32_t*)(c->h12.d + pl.offChunkB); a.l1ChunkOff = (uint32_t*)(c->h12.d + pl.offChunkO);
-            a.lzRec = (uint64_t*)(c->h12.d + pl.offRec); a.lzBridge = (uint64_t*)(c->h12.d + pl.offBridge); a.lzRecStride = pl.recStride;
-            a.lzMeta = (LzSegMeta*)(c->h12.d + pl.offMeta); a.lzStarts = (uint64_t*)(c->h12.d + pl.offStarts); a.lzPieces = (LzPiece*)(c->h12.d + pl.offPieces);
+            a.l1MaxLen = maxLen;
             a.lzMinSeg = 8192;
             if (const char* v = getenv("PLZ4HIP_HC_MIN_SEG")) { const int m = atoi(v); if (m >= 64) a.lzMinSeg = m; }     // tests: many segments in small blocks
         }
         a.h12Gather = 12; a.h12Idle = 16;
         if (const char* v = getenv("PLZ4HIP_HC12_GATHER")) a.h12Gather = atoi(v);
         if (const char* v = getenv("PLZ4HIP_HC12_IDLE")) a.h12Idle = atoi(v);
+        bind_hc(a, c->h12.d, pl, segs, 0);
         int nGroups = (nb + pl.group - 1) / pl.group;
         int per = (nb + nGroups - 1) / nGroups;                           // groups of equal size (<= pl.group)
         HIPCHK(c, hipMemsetAsync(a.h12Err, 0, 4, s));                      // the give-up flag is per call (k_hc12_parse reports it per block)
@@ -2209,14 +2187,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
                 if (!*ev) HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
         }
         // the workspace pointers of the half a group uses: every per-block array moved on by k blocks
-        const auto half = [&](CodecArgs x, int k) {
-            x.h12Chain += (int64_t)k * x.h12ChainStride; x.h12Rank += (int64_t)k * x.h12ChainStride; x.h12List += (int64_t)k * (x.h12ChainStride + 8);
-            x.h12Offsets += (size_t)k * kHcHashEntries; x.h12F += (int64_t)k * x.h12FStride; x.l1Seq += (int64_t)k * x.l1SeqStride;
-            x.l1Info += k; x.l1ChunkBytes += (int64_t)k * x.l1MaxChunks; x.l1ChunkOff += (int64_t)k * x.l1MaxChunks;
-            x.lzRec += (int64_t)k * x.lzRecStride; x.lzBridge += (int64_t)k * x.lzRecStride;
-            x.lzMeta += (int64_t)k * kLzMaxSegs; x.lzStarts += (int64_t)k * kLzMaxSegs * kLzStarts; x.lzPieces += (int64_t)k * 2 * kLzMaxSegs;
-            return x;
-        };
+        const auto half = [&](CodecArgs x, int k) { bind_hc(x, c->h12.d, pl, segs, k); return x; };
         const auto build = [&](hipStream_t st, CodecArgs x, bool hist, bool chain) -> int {
             hipError_t e2;
             if (hist)  { x.queue = next_queue(c, st, &e2); HIPCHK(c, e2); hipLaunchKernelGGL(k_hc12_hist, dim3(grid_for(x.nBlocks, c->cus)), dim3(1024), 0, st, x); }
@@ -2319,61 +2290,36 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         a.blk0 = 0;
         int per = nb;                     // blocks per launch
         bool lists = false;
-        size_t chainBytes = 0, rankBytes = 0, listBytes = 0;
         if (a.level >= 3 && !a.hcEx && maxLen >= 4096 && getenv("PLZ4HIP_HC_PRE_OFF") == nullptr) {
             // levels 3..12, independent blocks: the chain of every block built up front (2 B per position): the parsers then run
             // without their 4 M dependent table updates per 4 MiB block.  Levels 4..12 (8 candidates and more per search)
             // also get the per-hash lists (another 8 B per position): their searches then look at up to 63 candidates per
             // round (hc_find_wider_lists).  A call whose blocks do not fit the memory set aside runs in groups of equal size.
-            const int64_t stride = (int64_t)round_up((size_t)maxLen + 1, 1024);
             size_t freeB = 0, totalB = 0;
             if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-            size_t budget = hc_default_budget(freeB + c->h12.bytes);      // the chain alone
-            // the lists are worth more memory than that: these kernels live on the number of blocks in flight (7 waves per SIMD
-            // fit), and 4096 blocks of 4 MiB with their lists (40 MiB each) are 160 GiB: a machine that is there for this sets PLZ4HIP_HC_BUDGET_GIB;
-            // plz4hip_ctx_trim gives it back.  What the ctx already holds is used in any case.
-            size_t budgetLists = hc_default_budget(freeB + c->h12.bytes);
-            if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) { const long g = atol(v); if (g >= 1) budget = budgetLists = (size_t)g << 30; }
-            if (budget < c->h12.bytes) budget = c->h12.bytes;
-            if (budgetLists < c->h12.bytes) budgetLists = c->h12.bytes;
-            const size_t slack = 256 + 4 * 256;
-            const size_t chainPer = (size_t)stride * 2;
-            const size_t listsPer = chainPer + (size_t)stride * 4 + ((size_t)stride + 8) * 4 + (size_t)kHcHashEntries * 4;
-            const auto groups_of = [&](size_t room, size_t perBlock) {          // blocks per launch, groups of equal size
-                int64_t g = room > slack ? (int64_t)((room - slack) / perBlock) : 0;
-                if (const char* v = getenv("PLZ4HIP_HC_GROUP")) { const int gv = atoi(v); if (gv >= 1 && gv < g) g = gv; }
-                if (g < 1) return 0;
-                if (g > nb) g = nb;
-                const int n = (int)((nb + g - 1) / g);
-                return (nb + n - 1) / n;
-            };
-            const int perLists = (a.level >= 4 && getenv("PLZ4HIP_HC_LISTS_OFF") == nullptr) ? groups_of(budgetLists, listsPer) : 0;
-            const int perChain = groups_of(budget, chainPer);
-            // a group has to keep the chip busy: below 2048 blocks in flight the lists lose to the chain alone over more blocks
-            // at levels 4..9; the optimal parser's levels gain an order of magnitude and take them in any case
-            lists = perLists >= 1 && (perLists == nb || perLists >= (a.level >= 10 ? 256 : 2048) || perChain < 1);
-            if (lists && perLists > c->h12.bytes / listsPer) {            // try the large request first: refused -> the chain alone
-                bool refused = false;  if (int rc = reserve_h12(c, slack + (size_t)perLists * listsPer, &refused)) return rc;
+            // The budget: hc_default_budget, for the chain alone and for the lists alike.  The lists are worth more memory than that:
+            // these kernels live on the number of blocks in flight (7 waves per SIMD fit), and 4096 blocks of 4 MiB with their lists
+            // (40 MiB each) are 160 GiB: a machine that is there for this sets PLZ4HIP_HC_BUDGET_GIB; plz4hip_ctx_trim gives it back.
+            // What the ctx already holds is used in any case.
+            long budgetGiB = 0;  int group = 0;
+            if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) budgetGiB = atol(v);
+            if (const char* v = getenv("PLZ4HIP_HC_GROUP")) group = atoi(v);
+            const HcPrePlan pp = hc_pre_plan(freeB, c->h12.bytes, budgetGiB, group, getenv("PLZ4HIP_HC_LISTS_OFF") != nullptr, a.level, nb, maxLen);
+            lists = pp.lists;
+            if (lists && pp.perLists > c->h12.bytes / hc_pre_layout(1, maxLen, true).perBlock) {   // try the large request first: refused -> the chain alone
+                bool refused = false;  if (int rc = reserve_h12(c, hc_pre_layout(pp.perLists, maxLen, true).total, &refused)) return rc;
                 if (refused) lists = false;
             }
-            const int perPre = lists ? perLists : perChain;
+            const int perPre = lists ? pp.perLists : pp.perChain;
             if (getenv("PLZ4HIP_VERBOSE"))
                 fprintf(stderr, "plz4hip: HC level %d, %d blocks: free %zu MiB, held %zu MiB, lists %d, %d blocks per group\n", a.level, nb,
                         freeB >> 20, c->h12.bytes >> 20, (int)lists, perPre);
             if (perPre >= 1) {
                 per = perPre;
-                bool refused = false;  if (int rc = reserve_h12(c, slack + (size_t)per * (lists ? listsPer : chainPer), &refused)) return rc;
+                const HcPreLayout L = hc_pre_layout(per, maxLen, lists);
+                bool refused = false;  if (int rc = reserve_h12(c, L.total, &refused)) return rc;
                 if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC chain workspace");
-                chainBytes = round_up((size_t)per * chainPer, 256);
-                rankBytes = round_up((size_t)per * (size_t)stride * 4, 256);
-                listBytes = round_up((size_t)per * ((size_t)stride + 8) * 4, 256);
-                a.h12Chain = (uint16_t*)(c->h12.d + 256); a.h12ChainStride = stride;
-                a.h12Rank = nullptr; a.h12List = nullptr; a.h12Offsets = nullptr;
-                if (lists) {
-                    a.h12Rank = (uint32_t*)(c->h12.d + 256 + chainBytes);
-                    a.h12List = (uint32_t*)(c->h12.d + 256 + chainBytes + rankBytes);
-                    a.h12Offsets = (uint32_t*)(c->h12.d + 256 + chainBytes + rankBytes + listBytes);
-                }
+                bind_hc_pre(a, c->h12.d, L, lists);
             }
         }
         for (int g0 = 0; g0 < nb; g0 += per) {
@@ -2396,6 +2342,21 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLe
         if (a.hcx) { a.hcPfx = nullptr; if (int rc = hcx_blocks(a)) return rc; }   // (the one-thread kernels passed them over)
     }
     return PLZ4HIP_OK;
+}
+
+// The pointers of a level-1 group workspace (L1Layout) and of the few-block parse's (FxLayout; returns the blocks' FxlBlk array)
+void bind_l1(CodecArgs& a, uint8_t* base, const L1Layout& L)
+{
+    a.l1SeqStride = (int64_t)L.seqStride; a.l1MaxChunks = L.maxChunks;
+    a.l1Info = (SeqInfo*)(base + L.offInfo);
+    a.l1ChunkBytes = (uint32_t*)(base + L.offChunkBytes); a.l1ChunkOff = (uint32_t*)(base + L.offChunkOff);
+    a.l1Seq = (uint64_t*)(base + L.offSeq); a.l1Bk = base + L.offBk;
+}
+FxlBlk* bind_fx(FxArgs& fx, uint8_t* base, const FxLayout& F, bool hist)
+{
+    fx.meta = (FxPiece*)(base + F.offMeta); fx.tabIn = (uint32_t*)(base + F.offIn); fx.tabOut = (uint32_t*)(base + F.offOut);
+    fx.rec = (uint64_t*)(base + F.offRec);
+    return hist ? (FxlBlk*)(base + F.offBlk) : nullptr;
 }
 
 // Enqueue one level-1 call of nb independent blocks without dictionary (a: everything but queue / workspace filled in) on s.
@@ -2468,11 +2429,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     }
     bool fused = maxLen <= 0 || maxLen > kSeqMaxBlock || getenv("PLZ4HIP_L1_FUSED") != nullptr;
     if (hist && l1x && !l1x_on() && !fxl_wanted(nb, maxLen)) fused = true;              // (the one-kernel encoder: no workspace)
-    const size_t seqStride = round_up((size_t)(maxLen > 0 ? maxLen : 0) / 4 + 3, 64);     // + the dump entry (lz4_seq_device.inl)
-    const int    maxChunks = (int)((seqStride + kSeqChunk - 1) / kSeqChunk);
-    const size_t perBlock  = sizeof(SeqInfo) + (size_t)maxChunks * 8 + seqStride * 9 + (l1x ? sizeof(FxlBlk) : 0);
-    const auto need_for = [&](int per) { return round_up((size_t)per * sizeof(SeqInfo), 256) + 2 * round_up((size_t)per * maxChunks * 4, 256) + round_up((size_t)per * seqStride * 9, 8)
-                                                + (l1x ? (size_t)per * sizeof(FxlBlk) : 0); };
+    const auto need_for = [&](int per) { return l1_layout(per, maxLen, l1x).total; };
     int per = nb;
     if (shared && !fused && wsi != 0 && !ws->d && c->l1Refused > 0) { c->l1Refused--; wsi = 0; ws = &c->l1[0]; }   // (refused a moment ago)
     if (shared && !fused && wsi != 0 && !ws->d) {
@@ -2488,20 +2445,18 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     if (!fused && need_for(nb) > ws->bytes) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-        size_t budget = (freeB + ws->bytes) / 2;
-        if (const char* v = getenv("PLZ4HIP_L1_BUDGET_GIB")) { const long g = atol(v); if (g >= 1) budget = (size_t)g << 30; }
-        if (const char* v = getenv("PLZ4HIP_L1_BUDGET_MIB")) { const long g = atol(v); if (g >= 1) budget = (size_t)g << 20; }   // tests: force groups
-        if (budget < ws->bytes) budget = ws->bytes;
-        int64_t grp = (int64_t)(budget / (perBlock + 64));
-        if (grp > nb) grp = nb;
-        while (grp >= 1) {
-            const int nGroups = (int)((nb + grp - 1) / grp);
-            per = (nb + nGroups - 1) / nGroups;
-            bool refused = false;  HIPCHK(c, order ? ws->reserve(need_for(per), *order, &refused) : ws->reserve(need_for(per), s, &refused));
-            if (!refused) break;
-            grp = grp / 2;                                                              // refused: smaller groups
-        }
-        if (grp < 1) fused = true;                                                      // not even one block: the fused kernels need no workspace
+        long budgetGiB = 0, budgetMiB = 0;
+        if (const char* v = getenv("PLZ4HIP_L1_BUDGET_GIB")) budgetGiB = atol(v);
+        if (const char* v = getenv("PLZ4HIP_L1_BUDGET_MIB")) budgetMiB = atol(v);                                               // tests: force groups
+        int rc = PLZ4HIP_OK;
+        const int64_t grp = l1_first_group(freeB, ws->bytes, budgetGiB, budgetMiB, l1_layout(1, maxLen, l1x).perBlock, nb);
+        const int got = fit_groups(nb, grp, false, [&](int p, bool* refused) {
+            per = p;
+            HIPCHK(c, order ? ws->reserve(need_for(per), *order, refused) : ws->reserve(need_for(per), s, refused));
+            return (int)PLZ4HIP_OK;
+        }, &rc);
+        if (rc) return rc;
+        if (!got) fused = true;                                                         // not even one block: the fused kernels need no workspace
         if (getenv("PLZ4HIP_VERBOSE"))
             fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, fused ? " (fused)" : "");
     }
@@ -2518,12 +2473,10 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     // from here on the job is marked behind whatever was enqueued, whichever way the call ends
     MarkOnExit job, fxJob;
     if (order) { HIPCHK(c, order->wait(s)); job.arm(*order, s); }
-    a.l1MaxLen = maxLen; a.l1SeqStride = (int64_t)seqStride; a.l1MaxChunks = maxChunks;
-    a.l1Info = (SeqInfo*)ws->d;
-    a.l1ChunkBytes = (uint32_t*)(ws->d + round_up((size_t)per * sizeof(SeqInfo), 256));
-    a.l1ChunkOff   = (uint32_t*)((uint8_t*)a.l1ChunkBytes + round_up((size_t)per * maxChunks * 4, 256));
-    a.l1Seq        = (uint64_t*)((uint8_t*)a.l1ChunkOff + round_up((size_t)per * maxChunks * 4, 256));
-    a.l1Bk         = (uint8_t*)(a.l1Seq + (size_t)per * seqStride);
+    const L1Layout L = l1_layout(per, maxLen, l1x);
+    a.l1MaxLen = maxLen;
+    bind_l1(a, ws->d, L);
+    const int maxChunks = L.maxChunks;
     // A call of at most PLZ4HIP_FX_MAX_BLOCKS blocks (0: off) whose blocks may take liblz4's byU32 tables has its parse cut across the
     // chip (lz4_fx_device.inl) in pieces of PLZ4HIP_FX_PIECE_KIB, guessed starts PLZ4HIP_FX_WARMUP_KIB early.  Its workspace is sized
     // per call (a group of `per` blocks); when it cannot be had, the call parses as below.
@@ -2539,23 +2492,18 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             if (const char* v = getenv("PLZ4HIP_FX_WARMUP_KIB")) { const int x = atoi(v); if (x >= 0 && x <= 4096) wk = x; }
             fx.pb = pk << 10; fx.warm = wk << 10;
             fx.P = (maxLen + fx.pb - 1) / fx.pb; fx.recStride = fx_rec_stride_host(fx.pb); fx.cnt = c->d_counters;
-            const size_t nP = (size_t)per * fx.P;
-            const size_t offIn = round_up(nP * sizeof(FxPiece), 256), offOut = offIn + nP * kFxTab * 4, offRec = offOut + 2 * nP * kFxTab * 4;
-            const size_t offBlk = offRec + nP * (size_t)fx.recStride * 8;
-            const size_t need = offBlk + (hist ? round_up((size_t)per * sizeof(FxlBlk), 256) : 0);
+            const FxLayout F = fx_layout(per, fx.P, fx.recStride, hist);
             HIPCHK(c, c->fxOrder.wait(s));
-            bool refused = false;  HIPCHK(c, c->fx.reserve(need, c->fxOrder, &refused));
+            bool refused = false;  HIPCHK(c, c->fx.reserve(F.total, c->fxOrder, &refused));
             if (!refused) {
-                fx.meta = (FxPiece*)c->fx.d; fx.tabIn = (uint32_t*)(c->fx.d + offIn); fx.tabOut = (uint32_t*)(c->fx.d + offOut);
-                fx.rec = (uint64_t*)(c->fx.d + offRec);
-                if (hist) xb = (FxlBlk*)(c->fx.d + offBlk);
+                xb = bind_fx(fx, c->fx.d, F, hist);
                 useFx = true;
                 fxJob.arm(c->fxOrder, s);
             }
         }
     }
     if (hist && !useFx && !(l1x && l1x_on())) return dict_kernels();
-    if (hist && !useFx) xb = (FxlBlk*)(a.l1Bk + round_up((size_t)per * seqStride, 8));       // (the bulk route: behind the group's records)
+    if (hist && !useFx) xb = (FxlBlk*)(ws->d + L.offBlk);                                     // (the bulk route: behind the group's records)
     for (int g0 = 0; g0 < nb; g0 += per) {
         const int ng = nb - g0 < per ? nb - g0 : per;
         a.blk0 = g0; a.nBlocks = ng;
@@ -2670,6 +2618,33 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
 // per chain.  PLZ4HIP_DXL_GROUP_BLOCKS: blocks per group (0: no groups, one wave per chain beyond PLZ4HIP_DX_MAX_BLOCKS; set, it
 // also cuts calls that would fit one pass).  The constants and the default: profiles/dxl_group_rate.json.
 enum { kHistNone = 0, kHistDict = 1, kHistLinked = 2 };
+// The tables both flavours of the few-block decoder start with, at `base`; then DxLayout's record arrays (hashed: and the checksum
+// verdicts), link arrays (hist) and the grouped call's word per chain (else null), and DxbLayout's stages for raw blocks above 4 MiB
+template <class Layout> void bind_dx_tables(CodecArgs& a, uint8_t* base, const Layout& L)
+{
+    a.dxT = (uint64_t*)(base + L.offT); a.dxTStride = (int64_t)L.tStride;
+    a.dxPtr = (uint32_t*)(base + L.offPtr); a.dxPtrStride = (int64_t)L.pStride;
+    a.dxUnits = (DxUnit*)(base + L.offUnits); a.dxMaxSeg = L.maxSeg;
+    a.dxInfo = (DxInfo*)(base + L.offInfo);
+}
+void bind_dx(CodecArgs& a, uint8_t* base, const DxLayout& L, bool records, bool hashed, bool hist)
+{
+    bind_dx_tables(a, base, L);
+    if (records) { a.dxSrcOff = (int64_t*)(base + L.offSrcOff); a.dxLen = (int32_t*)(base + L.offLen); }
+    if (hashed) a.dxHashBad = (int32_t*)(base + L.offHashBad);
+    if (!hist) return;
+    a.dxlFirst = (int32_t*)(base + L.offFirst); a.dxlChain = (int32_t*)(base + L.offChain); a.dxlGood = (int32_t*)(base + L.offGood);
+    a.dxlMoved = (uint32_t*)(base + L.offMoved);
+}
+int32_t* dx_dead(uint8_t* base, const DxLayout& L, bool grouped) { return grouped ? (int32_t*)(base + L.offDead) : nullptr; }
+void bind_dxb(CodecArgs& a, uint8_t* base, const DxbLayout& L)
+{
+    bind_dx_tables(a, base, L);
+    a.dxbTG = (uint64_t*)(base + L.offTG); a.dxbTGStride = (int64_t)L.tgStride;
+    a.dxbEnt = (DxbEntry*)(base + L.offEnt); a.dxbGroups = L.groups;
+    a.dxbRuns = (DxRun*)(base + L.offRuns); a.dxbRunRoom = L.room;
+    a.dxbInfo = (DxbInfo*)(base + L.offBi);
+}
 constexpr int    kDxlGroupBlocks = 128;                                     // the fastest of 16 / 32 / 64 / 128 on a 256-block chain
 constexpr double kDxlMsPerBlock = 0.33, kWalkMsPerBlock = 59.0;             // t_dx, t_wave: 4 MiB blocks; both scale with the block alike
 constexpr int    kDxlGroupChains = 1024;                                    // chains a group's pointer space has room for
@@ -2691,7 +2666,7 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
     }
     const int nCh = hist == kHistLinked ? a.nChains : 0;
     const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
-    const size_t tStride = dx_t_stride(maxIn), pStride = dx_ptr_stride(maxOut);
+    const size_t pStride = dx_ptr_stride(maxOut);
     // groups: [g0, g1) blocks and [ch0, ch1) chains each
     std::vector<DxlGroup> groups;
     int gMax = nb;
@@ -2740,25 +2715,15 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
             int G = dxb_group_for(maxSeg), thr = kDxbThr;
             if (const char* v = getenv("PLZ4HIP_DX_BIG_GROUP")) { const int g = atoi(v); if (g >= 2 && g <= kDxbMaxGroup) G = g; }
             if (const char* v = getenv("PLZ4HIP_DX_BIG_RUN_KIB")) { const int k = atoi(v); if (k >= 1 && k <= (1 << 20)) thr = k << 10; }
-            const int groups = dxb_groups(maxSeg, G), room = dxb_run_room(maxIn, maxOut, thr), rounds = dxb_rounds(maxOut);
-            const size_t tStrideB = dx_t_stride(maxIn), pStrideB = dxb_ptr_stride(maxOut), tgStride = (size_t)groups * kDxSeg, wb = (size_t)nb;
-            const size_t offPtr = round_up(wb * tStrideB * 8, 256), offUnits = offPtr + round_up(wb * pStrideB * 4, 256);
-            const size_t offInfo = offUnits + round_up(wb * maxSeg * sizeof(DxUnit), 256), offTG = offInfo + round_up(wb * sizeof(DxInfo), 256);
-            const size_t offEnt = offTG + round_up(wb * tgStride * 8, 256), offRuns = offEnt + round_up(wb * groups * sizeof(DxbEntry), 256);
-            const size_t offBi = offRuns + round_up(wb * (size_t)room * sizeof(DxRun), 256), need = offBi + round_up(wb * sizeof(DxbInfo), 256);
+            const DxbLayout L = dxb_layout(nb, maxIn, maxOut, G, thr);
+            const int groups = L.groups, rounds = dxb_rounds(maxOut);
             HIPCHK(c, c->dxOrder.wait(s));
-            bool refused = false;  HIPCHK(c, c->dx.reserve(need, c->dxOrder, &refused));
+            bool refused = false;  HIPCHK(c, c->dx.reserve(L.total, c->dxOrder, &refused));
             dx = false;                                                         // (no room: one wave per block)
             if (!refused) {
                 job.arm(c->dxOrder, s);
-                a.dxT = (uint64_t*)c->dx.d; a.dxTStride = (int64_t)tStrideB;
-                a.dxPtr = (uint32_t*)(c->dx.d + offPtr); a.dxPtrStride = (int64_t)pStrideB;
-                a.dxUnits = (DxUnit*)(c->dx.d + offUnits); a.dxMaxSeg = maxSeg;
-                a.dxInfo = (DxInfo*)(c->dx.d + offInfo);
-                a.dxbTG = (uint64_t*)(c->dx.d + offTG); a.dxbTGStride = (int64_t)tgStride;
-                a.dxbEnt = (DxbEntry*)(c->dx.d + offEnt); a.dxbGroups = groups; a.dxbG = G;
-                a.dxbRuns = (DxRun*)(c->dx.d + offRuns); a.dxbRunRoom = room; a.dxbThr = thr;
-                a.dxbInfo = (DxbInfo*)(c->dx.d + offBi); a.dxbRounds = rounds;
+                bind_dxb(a, c->dx.d, L);
+                a.dxbG = G; a.dxbThr = thr; a.dxbRounds = rounds;
                 const int chunks = (int)((maxOut + 1023) / 1024);
                 hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
                 hipLaunchKernelGGL(k_dxb_compose, dim3(groups * 32, nb), dim3(256), 0, s, a);
@@ -2773,20 +2738,17 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
         }
     }
     if (dx) {
-        const int maxSeg = dx_max_seg(maxIn);
-        const size_t wb = (size_t)gMax;                                         // blocks the workspace is laid out for: the call, or one group
-        const size_t offPtr = round_up(wb * tStride * 8, 256), offUnits = offPtr + round_up(wb * pStride * 4, 256);
-        const size_t offInfo = offUnits + round_up(wb * maxSeg * sizeof(DxUnit), 256), offRec = offInfo + round_up(wb * sizeof(DxInfo), 256);
-        const size_t offLink = offRec + round_up(wb * 16, 256);
-        const size_t offDead = offLink + (hist ? round_up(wb * (12 + 4 * (kDxlMaxRounds + 1)), 256) : 0);
-        const size_t need = offDead + (groups.empty() ? 0 : round_up((size_t)nCh * 4, 256));
+        // gMax: the blocks the workspace is laid out for (the call, or one group); a group's record and link arrays are packed by its own count
+        const auto layout_for = [&](int n) { return dx_layout(gMax, n, maxIn, maxOut, hist != kHistNone, records, groups.empty() ? 0 : nCh); };
+        const DxLayout whole = layout_for(gMax);
+        const int maxSeg = whole.maxSeg;
         HIPCHK(c, c->dxOrder.wait(s));
-        bool refused = false;  HIPCHK(c, c->dx.reserve(need, c->dxOrder, &refused));
+        bool refused = false;  HIPCHK(c, c->dx.reserve(whole.total, c->dxOrder, &refused));
         if (refused) dx = false;                                                // no room: one wave per block
         if (dx) {
             job.arm(c->dxOrder, s);
             const CodecArgs call = a;
-            int32_t* const dead = groups.empty() ? nullptr : (int32_t*)(c->dx.d + offDead);
+            int32_t* const dead = dx_dead(c->dx.d, whole, !groups.empty());
             if (dead) HIPCHK(c, hipMemsetAsync(dead, 0, (size_t)nCh * 4, s));
             const int nGroups = groups.empty() ? 1 : (int)groups.size();
             for (int gi = 0; gi < nGroups; ++gi) {
@@ -2801,17 +2763,11 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
                     a.dxlDead = dead + g.ch0; a.dxlBlk0 = g.g0; a.dxlGroup = gi; a.dxlGroups = nGroups;
                 }
                 const int nChG = hist == kHistLinked ? a.nChains : 0;
-                a.dxT = (uint64_t*)c->dx.d; a.dxTStride = (int64_t)tStride;
-                a.dxPtr = (uint32_t*)(c->dx.d + offPtr); a.dxPtrStride = (int64_t)pStride;
-                a.dxUnits = (DxUnit*)(c->dx.d + offUnits); a.dxMaxSeg = maxSeg;
-                a.dxInfo = (DxInfo*)(c->dx.d + offInfo);
                 const bool hashed = records && a.blockChecksum;
+                bind_dx(a, c->dx.d, layout_for(nb), records, hashed, hist != kHistNone);
                 if (records) {
-                    int64_t* so = (int64_t*)(c->dx.d + offRec); int32_t* ln = (int32_t*)(so + nb);
-                    hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, so, ln);
-                    a.dxSrcOff = so; a.dxLen = ln;
+                    hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, (int64_t*)a.dxSrcOff, (int32_t*)a.dxLen);     // (fills them)
                     if (hashed) {
-                        a.dxHashBad = ln + nb;
                         // (the ctx's own stream, idle otherwise: one stream more would push the staging slots' streams onto shared
                         // hardware queues -- the runtime has four -- and cost the large host calls their overlap: 412 -> 610 ms per
                         // 2304 blocks, measured)
@@ -2833,8 +2789,6 @@ int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t ma
                     if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
                     hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
                 } else {
-                    a.dxlFirst = (int32_t*)(c->dx.d + offLink); a.dxlChain = a.dxlFirst + nb; a.dxlGood = a.dxlChain + nb;
-                    a.dxlMoved = (uint32_t*)(a.dxlGood + nb);
                     // the copy chain of a call (of a group) can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
                     int rounds = 1;
                     while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
@@ -3391,31 +3345,7 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes
 }
 
 // ---------------------------------------------------------------------------------------- host-buffer API
-// Staging layout on both sides: [int32 lenA[n]] [int32 lenB[n]] [int32 res[n]] [int32 st[n]] [in blocks @inStride] [out blocks @outStride]
-namespace {
-// Layout of one chunk in a slot (same offsets in the pinned host buffer and in the device buffer):
-//   [srcLen n][dstCap n][result n][status n][outLen n][outOff n+1 (int64)] | inputs at inStride | outputs at outStride
-// and, device only, the outputs once more back to back (compacted) -- that is what travels back over PCIe.
-struct Staging { size_t offA, offB, offRes, offSt, offLen, offOff, offIn, offOut, offPack, total; int64_t inStride, outStride; size_t gap; };
-
-// gap: bytes of scratch in front of every input block (HC with a dictionary / linked blocks: the external segment goes there)
-Staging plan(int n, int maxIn, int maxOut, size_t gap = 0)
-{
-    Staging s{};
-    s.gap = gap;
-    const size_t arr = round_up((size_t)n * 4, 256);
-    s.offA = 0; s.offB = arr; s.offRes = 2 * arr; s.offSt = 3 * arr; s.offLen = 4 * arr;
-    s.offOff = 5 * arr;
-    s.offIn = s.offOff + round_up((size_t)(n + 1) * 8, 256);
-    s.inStride = (int64_t)round_up((size_t)maxIn + gap + 16, 16);
-    s.outStride = (int64_t)round_up((size_t)maxOut + 16, 16);
-    s.offOut = s.offIn + (size_t)n * s.inStride;
-    s.offPack = s.offOut + (size_t)n * s.outStride;
-    s.total = s.offPack + (size_t)n * s.outStride;
-    return s;
-}
-}  // namespace
-
+// The layout of one chunk in a slot, the same in the pinned host buffer and in the device buffer: Staging (ws_layout.h)
 struct DictJob {                       // optional dictionary / linked parameters of a host call
     const plz4hip_dict* dict = nullptr;
     int   linked = 0;
@@ -3463,21 +3393,16 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
     const size_t gap = (dictMode && (mode == 0 || mode == 2)) ? 65536 : 0;     // encoders with a dictionary / linked blocks: room for the external segment
     int cb = nBlocks;
     {
-        const Staging one = plan(1, maxIn, maxOut, gap);
+        const Staging one = staging_layout(1, maxIn, maxOut, gap, false, 1);
         const size_t per = (size_t)one.inStride + 2 * (size_t)one.outStride;
         if (!chained && per * (size_t)nBlocks > kChunkBytes) { cb = (int)(kChunkBytes / per); if (cb < 1) cb = 1; }
     }
     const int nChunks = (nBlocks + cb - 1) / cb;
     // HC kernels index one shared workspace by workgroup: never two of them at once
     const int nSlots = hcMode ? 1 : (nChunks < plz4hip_ctx::kSlots ? nChunks : plz4hip_ctx::kSlots);
-    const Staging st = plan(cb, maxIn, maxOut, gap);
-    // [prevTail 64 KiB][per chain: window 2 x 64 KiB][windowLen per chain][chainFirst]
     const int    nCh = (dictMode && dj->window) ? dj->nChains : 1;
-    const size_t offExtra = st.total;
-    const size_t offWin = offExtra + 65536, offWinLen = offWin + (size_t)nCh * 131072, offFirst = offWinLen + round_up((size_t)nCh * 4, 256);
-    const size_t winBytes = (offFirst + round_up((size_t)(nCh + 1) * 4, 256)) - offWin;
-    const size_t slotBytes = st.total + (dictMode ? 65536 + winBytes : 0);
-    for (int i = 0; i < nSlots; ++i) if (int rc = ensure_slot(c, i, slotBytes, slotBytes)) return rc;
+    const Staging st = staging_layout(cb, maxIn, maxOut, gap, dictMode, nCh);
+    for (int i = 0; i < nSlots; ++i) if (int rc = ensure_slot(c, i, st.total, st.total)) return rc;
 
     auto submit = [&](int k) -> int {
         plz4hip_ctx::HostSlot& sl = c->slot[k % nSlots];
@@ -3521,17 +3446,17 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
                 pt = (const uint8_t*)src[b0 - 1] + (pl - ptLen);
             }
             if (ptLen >= 0) {
-                if (ptLen) memcpy(sl.h + offExtra, pt, (size_t)ptLen);
-                HIPCHK(c, hipMemcpyAsync(sl.d + offExtra, sl.h + offExtra, (size_t)ptLen + 16, hipMemcpyHostToDevice, s));
-                a.prevTail = sl.d + offExtra; a.prevTailLen = ptLen;
+                if (ptLen) memcpy(sl.h + st.offExtra, pt, (size_t)ptLen);
+                HIPCHK(c, hipMemcpyAsync(sl.d + st.offExtra, sl.h + st.offExtra, (size_t)ptLen + 16, hipMemcpyHostToDevice, s));
+                a.prevTail = sl.d + st.offExtra; a.prevTailLen = ptLen;
             }
             if (dj->window) {
-                for (int ch = 0; ch < nCh; ++ch) memcpy(sl.h + offWin + (size_t)ch * 131072, dj->window + (size_t)ch * 65536, 65536);
-                memcpy(sl.h + offWinLen, dj->windowLen, (size_t)nCh * sizeof(int));
-                if (dj->chainFirst) memcpy(sl.h + offFirst, dj->chainFirst, (size_t)(nCh + 1) * sizeof(int32_t));
-                HIPCHK(c, hipMemcpyAsync(sl.d + offWin, sl.h + offWin, winBytes, hipMemcpyHostToDevice, s));
-                a.window = sl.d + offWin; a.windowLen = (int*)(sl.d + offWinLen);
-                a.nChains = nCh; a.chainFirst = dj->chainFirst ? (const int32_t*)(sl.d + offFirst) : nullptr;
+                for (int ch = 0; ch < nCh; ++ch) memcpy(sl.h + st.offWin + (size_t)ch * 131072, dj->window + (size_t)ch * 65536, 65536);
+                memcpy(sl.h + st.offWinLen, dj->windowLen, (size_t)nCh * sizeof(int));
+                if (dj->chainFirst) memcpy(sl.h + st.offFirst, dj->chainFirst, (size_t)(nCh + 1) * sizeof(int32_t));
+                HIPCHK(c, hipMemcpyAsync(sl.d + st.offWin, sl.h + st.offWin, st.winBytes, hipMemcpyHostToDevice, s));
+                a.window = sl.d + st.offWin; a.windowLen = (int*)(sl.d + st.offWinLen);
+                a.nChains = nCh; a.chainFirst = dj->chainFirst ? (const int32_t*)(sl.d + st.offFirst) : nullptr;
             }
         }
         switch (mode) {
@@ -3581,7 +3506,7 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
         // results, status, sizes and offsets now; the packed bytes once their total is known (retire)
         HIPCHK(c, hipMemcpyAsync(sl.h + st.offRes, sl.d + st.offRes, st.offIn - st.offRes, hipMemcpyDeviceToHost, s));
         if (dictMode && dj->window)
-            HIPCHK(c, hipMemcpyAsync(sl.h + offWin, sl.d + offWin, offFirst - offWin, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(sl.h + st.offWin, sl.d + st.offWin, st.offFirst - st.offWin, hipMemcpyDeviceToHost, s));
         return PLZ4HIP_OK;
     };
     auto retire = [&](int k) -> int {
@@ -3598,8 +3523,8 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
             HIPCHK(c, hipStreamSynchronize(sl.s));
         }
         if (dictMode && dj->window) {
-            for (int ch = 0; ch < nCh; ++ch) memcpy(dj->window + (size_t)ch * 65536, sl.h + offWin + (size_t)ch * 131072, 65536);
-            memcpy(dj->windowLen, sl.h + offWinLen, (size_t)nCh * sizeof(int));
+            for (int ch = 0; ch < nCh; ++ch) memcpy(dj->window + (size_t)ch * 65536, sl.h + st.offWin + (size_t)ch * 131072, 65536);
+            memcpy(dj->windowLen, sl.h + st.offWinLen, (size_t)nCh * sizeof(int));
         }
         for (int i = 0; i < nb; ++i) { result[b0 + i] = hRes[i]; if (status) status[b0 + i] = hSt[i]; }
         if (mode != 4)
