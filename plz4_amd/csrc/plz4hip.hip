@@ -30,6 +30,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_dx_device.inl"
 #include "lz4_fx_device.inl"
 #include "ws_layout.h"
+#include "route.h"
 
 namespace {
 
@@ -1829,7 +1830,6 @@ struct plz4hip_dict {
 namespace {
 
 constexpr int kQueueSlots = 4096;
-constexpr int kFxMaxBlocks = 128;         // PLZ4HIP_FX_MAX_BLOCKS: the few-block level-1 parse up to this many blocks (launch_l1; profiles/fx_rate.json)
 
 // LZ4_loadDict_internal(_ld_slow) on the host (lz4.c:1587-1646): the table a dictionary context carries.
 void build_dict_table_slow(const uint8_t* p, int n, uint32_t* tab)
@@ -1939,6 +1939,14 @@ int grid_for(int nBlocks, int resident) { return nBlocks < resident ? nBlocks : 
 
 bool is_hc_level(int level) { return level >= 2 && level <= 12; }        // every row of the level table (lz4hc.c:92-106): mid, hash chain, optimal
 
+// The one place that names the instantiations of these kernels: the occupancy queries and the launches ask here.
+using Kernel1 = void (*)(CodecArgs);
+using HcxKernel = void (*)(CodecArgs, unsigned long long*);
+Kernel1 hc_mid_kernel(bool kD) { return !kD ? k_hc_mid<false> : k_hc_mid<true>; }
+HcxKernel hcx_kernel(bool raw, bool mid) { return !mid ? (!raw ? k_hcx<false, false> : k_hcx<true, false>) : (!raw ? k_hcx<false, true> : k_hcx<true, true>); }
+Kernel1 hc_lazy_kernel(bool kD) { return !kD ? k_hc_lazy<false> : k_hc_lazy<true>; }
+Kernel1 hc_stitch_kernel(bool kD) { return kD ? k_hc_stitch<true> : k_hc_stitch<false>; }
+
 int ensure_hc(plz4hip_ctx* c)
 {
     if (c->hc.d) return PLZ4HIP_OK;
@@ -1949,7 +1957,7 @@ int ensure_hc(plz4hip_ctx* c)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_encode_rec_hc, 64, 0) != hipSuccess || per < 1) per = 8;
     {   // (level 2's batch walk keeps its tables in these slots as well and holds more waves per CU than the one-thread parsers)
         int perMid = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perMid, k_hc_mid<false>, 64, 0) == hipSuccess && perMid > per) per = perMid;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perMid, hc_mid_kernel(false), 64, 0) == hipSuccess && perMid > per) per = perMid;
     }
     if (const char* v = getenv("PLZ4HIP_HC_WAVES_PER_CU")) { const int w = atoi(v); if (w >= 1 && w <= per) per = w; }
     const int waves = c->cus * per;
@@ -1973,13 +1981,10 @@ int reserve_h12(plz4hip_ctx* c, size_t need, bool* refused)
 // ctx holds already) unless PLZ4HIP_HC_BUDGET_GIB says more: the parser runs one wave per block, so the more blocks a group has (up
 // to three waves per SIMD: 3072), the better its latency is hidden -- 4096 blocks in two groups of 2048 instead of four of 1024:
 // 1418 -> 1664 MiB/s.  PLZ4HIP_HC12_GROUP overrides, for tests.  plz4hip_ctx_trim gives the memory back.
-int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, HcLayout* pl, bool lazy, bool needF)
+int plan_h12(plz4hip_ctx* c, const HcSwitches& sw, int nBlocks, int maxLen, HcLayout* pl, bool lazy, bool needF)
 {
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-    long budgetGiB = 0;  int group = 0;
-    if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) budgetGiB = atol(v);
-    if (const char* v = getenv("PLZ4HIP_HC12_GROUP")) group = atoi(v);
     if (!c->h12ParseWaves) {
         int per = 0, perSeg = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_hc12_parse, 64, 0) != hipSuccess || per < 1) per = 8;
@@ -1990,7 +1995,7 @@ int plan_h12(plz4hip_ctx* c, int nBlocks, int maxLen, HcLayout* pl, bool lazy, b
     const size_t perBlock = hc_layout(1, maxLen, lazy, needF, c->h12ParseWaves).perBlock;
     int rc = PLZ4HIP_OK;
     // groups of equal size: what is allocated is what one of them needs, whatever the budget would allow
-    const int got = fit_groups(nBlocks, hc_first_group(freeB, c->h12.bytes, budgetGiB, group, perBlock, nBlocks), true, [&](int per, bool* refused) {
+    const int got = fit_groups(nBlocks, hc_first_group(freeB, c->h12.bytes, sw.budgetGiB, sw.h12Group, perBlock, nBlocks), true, [&](int per, bool* refused) {
         *pl = hc_layout(per, maxLen, lazy, needF, c->h12ParseWaves);
         if (getenv("PLZ4HIP_VERBOSE"))
             fprintf(stderr, "plz4hip: level 12, %d blocks: free %zu MiB, held %zu MiB, groups of %d (%zu MiB)\n", nBlocks, freeB >> 20, c->h12.bytes >> 20, pl->group, pl->total >> 20);
@@ -2029,12 +2034,34 @@ void bind_hc_pre(CodecArgs& a, uint8_t* base, const HcPreLayout& L, bool lists)
     a.h12Offsets = lists ? (uint32_t*)(base + L.offOffsets) : nullptr;
 }
 
-// (blocks of 8 MiB and more -- raw block API only -- keep the one-thread-per-block kernel: the writer packs positions into 23 bits)
-bool use_h12(const CodecArgs& a, int maxLen) { return a.level >= 12 && !a.hcEx && maxLen < (1 << 23) && getenv("PLZ4HIP_HC12_OFF") == nullptr; }
-// levels 3..11, independent blocks up to 4 MiB: segments walked at once, stitched, record emit (lz4hc_lazy_device.inl)
-// (PLZ4HIP_HC12_LAZY=1, an experiment switch: level 12 on the same walk -- its searches made where the optimal parser asks for them,
-// wave-wide, instead of every position's search up front, lz4hc12_device.inl)
-bool use_lazy(const CodecArgs& a, int maxLen) { return a.level >= 3 && (a.level <= 11 || getenv("PLZ4HIP_HC12_LAZY") != nullptr) && !a.hcEx && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_LAZY_OFF") == nullptr; }
+// The launchers' switches (route.h), read once at the top of launch_l1 / launch_hc / launch_decode: every call sees the environment
+// as it is when the call is made.
+L1Switches read_l1_switches() { return parse_l1_switches([](const char* n) { return (const char*)getenv(n); }); }
+HcSwitches read_hc_switches() { return parse_hc_switches([](const char* n) { return (const char*)getenv(n); }); }
+DxSwitches read_dx_switches() { return parse_dx_switches([](const char* n) { return (const char*)getenv(n); }); }
+
+// The emit stage of the ng blocks from g0 on: sizes, scan, write, checksums.  Back: level-1 records with catch-up; Mid: records
+// without (level 2, the segmented HC walk); Seg: history outside the block (xb: the blocks' segments).  Waves per block so that a
+// small call still spreads over the chip.  ctxSmall: the blocks <= 4 KiB under a dictionary context are k_fxl_small's -- their
+// lengths before the records are placed in a body, else behind the stage.
+enum class Emit { Back, Mid, Seg };
+void launch_emit(hipStream_t s, const CodecArgs& a, int ng, int g0, int maxChunks, Emit kind, const FxlBlk* xb = nullptr, bool ctxSmall = false)
+{
+    int wg = (16384 / ng) / 4;
+    if (wg > (maxChunks + 3) / 4) wg = (maxChunks + 3) / 4;
+    if (wg < 1) wg = 1;
+    if (kind == Emit::Seg) hipLaunchKernelGGL(k_fxl_sizes, dim3(wg, ng), dim3(256), 0, s, a, xb);
+    else if (kind == Emit::Mid) hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_l1_sizes<true>, dim3(wg, ng), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
+    if (ctxSmall && a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);
+    if (a.bodyOff) hipLaunchKernelGGL(k_scan_from, dim3(1), dim3(64), 0, s, (const int32_t*)(a.result + g0), a.bodyOff + g0, ng, g0 == 0 ? 1 : 0);
+    if (kind == Emit::Seg) hipLaunchKernelGGL(k_fxl_write, dim3(wg, ng), dim3(256), 0, s, a, xb);
+    else if (kind == Emit::Mid) hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_l1_write<true>, dim3(wg, ng), dim3(256), 0, s, a);
+    if (!a.rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 15) / 16), dim3(64), 0, s, a);
+    if (ctxSmall && !a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);
+}
 
 // The block checksums of a record decode on the bulk path, in front of its launch (k_rec_verify16): every launch of k_decode_rec and
 // of k_l1_duplex's decode side goes through here first.
@@ -2043,12 +2070,13 @@ void launch_rec_verify(hipStream_t s, const CodecArgs& d)
     if (d.blockChecksum && d.nBlocks > 0) hipLaunchKernelGGL(k_rec_verify16, dim3((d.nBlocks + 15) / 16), dim3(64), 0, s, d);
 }
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined = nullptr,
-              const CodecArgs* rider = nullptr, bool hist = false, bool l1x = false);
+              const CodecArgs* rider = nullptr, bool hist = false, bool l1x = false, const L1Switches* read = nullptr);
 
 // Enqueue one HC call of nb blocks (a: everything but queue / workspace filled in) on s.  rawMode: LZ4 blocks, else records.
-int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked);
+int launch_hc_body(plz4hip_ctx* c, hipStream_t s, const HcSwitches& sw, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked);
 int launch_hc(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode)
 {
+    const HcSwitches sw = read_hc_switches();
     HIPCHK(c, c->hcOrder.wait(s));
     // Whatever was enqueued uses the ctx's workspaces, also when the body left early: the call's stream joins the builder's
     // stream (a completed body has done so group by group) and the job is marked in any case, so that a following trim /
@@ -2056,292 +2084,257 @@ int launch_hc(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     MarkOnExit job;
     job.arm(c->hcOrder, s);
     bool forked = false;
-    const int rc = launch_hc_body(c, s, a, nb, maxLen, rawMode, &forked);
+    const int rc = launch_hc_body(c, s, sw, a, nb, maxLen, rawMode, &forked);
     if (rc != PLZ4HIP_OK && forked && c->hcBuildStream && c->evHcFork
         && hipEventRecord(c->evHcFork, c->hcBuildStream) == hipSuccess) (void)hipStreamWaitEvent(s, c->evHcFork, 0);
     if (rc != PLZ4HIP_OK) return rc;
     HIPCHK(c, job.leave());
     return PLZ4HIP_OK;
 }
-int launch_hc_body(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked)
+struct HcCall { plz4hip_ctx* c; hipStream_t s; int nb, maxLen, rawMode; };    // what the routes' functions share
+
+// the blocks' segments laid out, their lengths noted (k_hc_ext_prep)
+int hc_prep_ext(const HcCall& k, CodecArgs& a)
+{
+    plz4hip_ctx* const c = k.c;  hipError_t e;
+    if ((size_t)k.nb * 4 > c->hcPfx.bytes) {                                 // (grown with room for 256 blocks more)
+        bool refused = false;  HIPCHK(c, c->hcPfx.reserve((size_t)k.nb * 4 + 1024, c->hcOrder, &refused));
+        if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC segment lengths");
+    }
+    a.hcPfx = (int32_t*)c->hcPfx.d; a.rawMode = k.rawMode; a.nBlocks = k.nb; a.blk0 = 0;
+    a.queue = next_queue(c, k.s, &e); HIPCHK(c, e);
+    hipLaunchKernelGGL(k_hc_ext_prep, dim3(grid_for(k.nb, c->cus * 8)), dim3(64), 0, k.s, a);
+    return PLZ4HIP_OK;
+}
+// every block of the call that is k_hcx's, one launch
+int hc_hcx_blocks(const HcCall& k, CodecArgs x)
+{
+    plz4hip_ctx* const c = k.c;  hipError_t e;
+    const bool mid = x.level == 2;
+    const HcxKernel kern = hcx_kernel(k.rawMode != 0, mid);
+    const int which = (k.rawMode ? 1 : 0) + (mid ? 2 : 0);
+    if (!c->hcxWaves[which]) {                                               // (of the instantiation that is launched)
+        int per = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)kern, 64, 0) != hipSuccess || per < 1) per = 7;
+        c->hcxWaves[which] = c->cus * per;
+    }
+    int waves = c->hcxWaves[which];
+    if (mid || x.level >= 10) {                                              // (a price table / the records per wave: the HC workspace's)
+        if (int rc = ensure_hc(c)) return rc;
+        x.hcWork = c->hc.d;
+        if (c->hcWaves < waves) waves = c->hcWaves;
+    }
+    x.blk0 = 0; x.nBlocks = k.nb;
+    x.queue = next_queue(c, k.s, &e); HIPCHK(c, e);
+    hipLaunchKernelGGL(kern, dim3(grid_for(k.nb, waves)), dim3(64), 0, k.s, x, c->d_counters);
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
+}
+// the blocks <= 4 KiB under a dictionary context (hcPfx < 0; the emit stage has laid them down as stored records in the meantime):
+// k_hcx, or the one-thread parser over the context's two sets of tables, writes them now
+int hc_ctx_blocks(const HcCall& k, const CodecArgs& a0)
+{
+    plz4hip_ctx* const c = k.c;  hipError_t e;
+    if (a0.hcx) return hc_hcx_blocks(k, a0);
+    if (int rc = ensure_hc(c)) return rc;
+    CodecArgs x = a0; x.hcWork = c->hc.d; x.blk0 = 0; x.nBlocks = k.nb; x.h12Chain = nullptr; x.h12Rank = nullptr; x.h12List = nullptr;
+    x.queue = next_queue(c, k.s, &e); HIPCHK(c, e);
+    if (k.rawMode) hipLaunchKernelGGL(k_encode_raw_hc, dim3(grid_for(k.nb, c->hcWaves)), dim3(64), 0, k.s, x);
+    else           hipLaunchKernelGGL(k_encode_rec_hc, dim3(grid_for(k.nb, c->hcWaves)), dim3(64), 0, k.s, x);
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
+}
+// the histogram and / or the chain and lists of x's blocks on st
+int hc_build(plz4hip_ctx* c, hipStream_t st, CodecArgs x, bool hist, bool chain)
 {
     hipError_t e;
-    const auto prep_ext = [&]() -> int {                                    // the blocks' segments laid out, their lengths noted (k_hc_ext_prep)
-        if ((size_t)nb * 4 > c->hcPfx.bytes) {                               // (grown with room for 256 blocks more)
-            bool refused = false;  HIPCHK(c, c->hcPfx.reserve((size_t)nb * 4 + 1024, c->hcOrder, &refused));
-            if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC segment lengths");
-        }
-        a.hcPfx = (int32_t*)c->hcPfx.d; a.rawMode = rawMode; a.nBlocks = nb; a.blk0 = 0;
-        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-        hipLaunchKernelGGL(k_hc_ext_prep, dim3(grid_for(nb, c->cus * 8)), dim3(64), 0, s, a);
-        return PLZ4HIP_OK;
-    };
-    // levels 2..12: the blocks <= 4 KiB under a dictionary context go to the wave-wide parser (k_hcx) unless PLZ4HIP_HCX=0 (read per call)
-    {   const char* v = getenv("PLZ4HIP_HCX");
-        a.hcx = a.hcEx && (a.dict != nullptr || a.dictLen >= 0) && a.hcxStart && a.level >= kHcxMinLevel && a.level <= kHcxMaxLevel && !(v && atoi(v) == 0); }
-    const auto hcx_blocks = [&](CodecArgs x) -> int {                       // every block of the call that is k_hcx's, one launch
-        const bool mid = x.level == 2;
-        const void* const kernels[4] = {(const void*)k_hcx<false, false>, (const void*)k_hcx<true, false>, (const void*)k_hcx<false, true>, (const void*)k_hcx<true, true>};
-        const int which = (rawMode ? 1 : 0) + (mid ? 2 : 0);
-        if (!c->hcxWaves[which]) {                                           // (of the instantiation that is launched)
+    if (hist)  { x.queue = next_queue(c, st, &e); HIPCHK(c, e); hipLaunchKernelGGL(k_hc12_hist, dim3(grid_for(x.nBlocks, c->cus)), dim3(1024), 0, st, x); }
+    if (chain) { x.queue = next_queue(c, st, &e); HIPCHK(c, e); hipLaunchKernelGGL(k_hc12_chain, dim3(grid_for(x.nBlocks, c->cus)), dim3(64), 0, st, x); }
+    return PLZ4HIP_OK;
+}
+
+// Segmented (route.h).  Levels 3..12 with a dictionary and/or linked blocks take the same route as the lazy levels -- chain and lists
+// over segment + block, the walk in segments, stitched, records through the emit stage -- with the segment rules of the reference
+// kept in the finders (lz4hc_lazy_device.inl, kD); only the blocks <= 4 KiB under a dictionary context are launched behind.
+// Levels 3..11: the list builder is one wave per CU around 128 KiB of LDS (0.3 s per 2048 blocks with the chip all but idle), the
+// walk needs no LDS.  A call of enough blocks therefore runs in at least four groups over the two halves of the workspace, the
+// builder of group g+1 on a second stream beside the walk of group g (which leaves it a wave slot per CU); the histogram of group
+// g+1 (1024-thread workgroups that would not find room beside the walk) runs between two walks.
+int hc_segmented(const HcCall& k, const HcSwitches& sw, const HcPlan& p, CodecArgs a, bool* forked)
+{
+    plz4hip_ctx* const c = k.c;  const hipStream_t s = k.s;  hipError_t e;
+    const int nb = k.nb;
+    HcLayout pl;
+    if (int rc = plan_h12(c, sw, nb, k.maxLen + (p.lazyEx ? 65536 : 0), &pl, p.segs, !p.lazy)) return rc;
+    if (p.prepExt) { if (int rc = hc_prep_ext(k, a)) return rc; }
+    c->h12ErrOff = pl.offErr;
+    a.rawMode = k.rawMode;
+    if (p.segs) {
+        if (p.lazy && a.level >= 10) { if (int rc = ensure_hc(c)) return rc; a.hcWork = c->hc.d; }
+        if (!c->hcLazyWaves) {
             int per = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernels[which], 64, 0) != hipSuccess || per < 1) per = 7;
-            c->hcxWaves[which] = c->cus * per;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, hc_lazy_kernel(false), 64, 0) != hipSuccess || per < 1) per = 8;
+            c->hcLazyWaves = c->cus * per;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, hc_lazy_kernel(true), 64, 0) != hipSuccess || per < 1) per = 8;
+            c->hcLazyExWaves = c->cus * per;
         }
-        int waves = c->hcxWaves[which];
-        if (mid || x.level >= 10) {                                          // (a price table / the records per wave: the HC workspace's)
-            if (int rc = ensure_hc(c)) return rc;
-            x.hcWork = c->hc.d;
-            if (c->hcWaves < waves) waves = c->hcWaves;
+        a.l1MaxLen = k.maxLen;
+        a.lzMinSeg = p.lzMinSeg;
+    }
+    a.h12Gather = p.gather; a.h12Idle = p.idle;
+    bind_hc(a, c->h12.d, pl, p.segs, 0);
+    HIPCHK(c, hipMemsetAsync(a.h12Err, 0, 4, s));                          // the give-up flag is per call (k_hc12_parse reports it per block)
+    const HcGroups g = hc_groups(nb, pl.group, p.lazy, sw);
+    const bool overlap = g.overlap;
+    const int per = g.per, nGroups = g.nGroups;
+    if (overlap) {
+        if (!c->hcBuildStream) HIPCHK(c, hipStreamCreateWithFlags(&c->hcBuildStream, hipStreamNonBlocking));
+        for (hipEvent_t* ev : {&c->evHcFork, &c->evHcHist, &c->evHcChain[0], &c->evHcChain[1], &c->evHcFree[0], &c->evHcFree[1]})
+            if (!*ev) HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    }
+    const CodecArgs a0 = a;
+    // the workspace pointers of the half group gi uses (every per-block array moved on by at blocks), and the group's blocks
+    const auto group = [&](int at, int gi) { CodecArgs x = a0; bind_hc(x, c->h12.d, pl, p.segs, at); x.blk0 = g.gStart[gi]; x.nBlocks = g.gSize[gi]; return x; };
+    const hipStream_t sb = c->hcBuildStream;
+    if (overlap) {
+        HIPCHK(c, hipEventRecord(c->evHcFork, s));
+        HIPCHK(c, hipStreamWaitEvent(sb, c->evHcFork, 0));
+        *forked = true;
+        if (int rc = hc_build(c, sb, group(0, 0), true, true)) return rc;
+        HIPCHK(c, hipEventRecord(c->evHcChain[0], sb));
+        if (nGroups > 1) {
+            if (int rc = hc_build(c, sb, group(per, 1), true, false)) return rc;
+            HIPCHK(c, hipEventRecord(c->evHcHist, sb));
         }
-        x.blk0 = 0; x.nBlocks = nb;
-        x.queue = next_queue(c, s, &e); HIPCHK(c, e);
-        if (mid) {
-            if (rawMode) hipLaunchKernelGGL((k_hcx<true, true>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
-            else         hipLaunchKernelGGL((k_hcx<false, true>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
+    }
+    for (int gi = 0; gi < nGroups; ++gi) {
+        const int ng = g.gSize[gi];
+        if (overlap) a = group((gi & 1) * per, gi);
+        a.blk0 = g.gStart[gi]; a.nBlocks = ng;
+        if (overlap) {
+            HIPCHK(c, hipStreamWaitEvent(s, c->evHcChain[gi & 1], 0));
+            if (gi + 1 < nGroups) {
+                HIPCHK(c, hipStreamWaitEvent(s, c->evHcHist, 0));               // the next group's histogram is done: its builder starts now
+                if (int rc = hc_build(c, sb, group(((gi + 1) & 1) * per, gi + 1), false, true)) return rc;
+                HIPCHK(c, hipEventRecord(c->evHcChain[(gi + 1) & 1], sb));
+            }
         } else {
-            if (rawMode) hipLaunchKernelGGL((k_hcx<true, false>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
-            else         hipLaunchKernelGGL((k_hcx<false, false>), dim3(grid_for(nb, waves)), dim3(64), 0, s, x, c->d_counters);
+            if (int rc = hc_build(c, s, a, true, true)) return rc;
+        }
+        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (!p.lazy) hipLaunchKernelGGL(k_hc12_search, dim3(grid_for(ng, c->cus)), dim3(1024), 0, s, a);
+        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (!p.segs) hipLaunchKernelGGL(k_hc12_parse, dim3(grid_for(ng, c->h12ParseWaves)), dim3(64), 0, s, a);
+        else {
+            // segments per block: as many as there are 8 KiB pieces, at most 512.  Measured at 4096 blocks of 4 MiB, level 3 /
+            // level 9: 16 segments 7522 / 4870, 32: 7734 / 4986, 64: 7908 / 5090, 128: 8071 / 5691, 256: 8279 / 5958, 512: 8602 /
+            // 6139, 1024: 8642 / 6159 MiB/s.  Far more walks than the chip holds waves: the queue hands neighbouring segments of
+            // one block to neighbouring waves, which then share the block's source and lists in L2, and short items even out.
+            a.lzSegs = p.lzSegs;
+            if (p.seg12) {
+                hipLaunchKernelGGL(k_hc12_seg, dim3(grid_for(ng * a.lzSegs, c->h12SegWaves)), dim3(64), 0, s, a);
+                a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+                hipLaunchKernelGGL(k_hc12_stitch, dim3(grid_for(ng, c->h12SegWaves)), dim3(64), 0, s, a);
+            } else {
+                const int resident = p.lazyEx ? c->hcLazyExWaves : c->hcLazyWaves;
+                int lzWaves = a.level >= 10 && c->hcWaves < resident ? c->hcWaves : resident;   // (a price table per wave)
+                if (overlap && lzWaves > 2 * c->cus) lzWaves -= c->cus;                    // a wave slot (and its registers) per CU for the builder
+                hipLaunchKernelGGL(hc_lazy_kernel(p.lazyEx), dim3(grid_for(ng * a.lzSegs, lzWaves)), dim3(64), 0, s, a);
+                a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+                hipLaunchKernelGGL(hc_stitch_kernel(p.lazyEx), dim3(grid_for(ng, lzWaves)), dim3(64), 0, s, a);
+            }
+            hipLaunchKernelGGL(k_hc_gather, dim3(ng >= 1024 ? 4 : 16, ng), dim3(256), 0, s, a);
+            launch_emit(s, a, ng, 0, pl.maxChunks, Emit::Mid);
         }
         HIPCHK(c, hipGetLastError());
-        return PLZ4HIP_OK;
-    };
-    // a call of nothing but such blocks (many small records under one dictionary) is that one launch: no segments to lay out, no
-    // lists in device memory, no workspace
-    if (a.hcx && maxLen <= kHcxMaxBlock && (rawMode || !a.linked)) { a.hcPfx = nullptr; return hcx_blocks(a); }
-    const auto ctx_blocks = [&](const CodecArgs& a0) -> int {
-        // the blocks <= 4 KiB under a dictionary context (hcPfx < 0; the emit stage has laid them down as stored records in the
-        // meantime): k_hcx, or the one-thread parser over the context's two sets of tables, writes them now
-        if (a0.dict == nullptr && a0.dictLen < 0) return PLZ4HIP_OK;
-        if (a0.hcx) return hcx_blocks(a0);
-        if (int rc = ensure_hc(c)) return rc;
-        CodecArgs x = a0; x.hcWork = c->hc.d; x.blk0 = 0; x.nBlocks = nb; x.h12Chain = nullptr; x.h12Rank = nullptr; x.h12List = nullptr;
-        x.queue = next_queue(c, s, &e); HIPCHK(c, e);
-        if (rawMode) hipLaunchKernelGGL(k_encode_raw_hc, dim3(grid_for(nb, c->hcWaves)), dim3(64), 0, s, x);
-        else         hipLaunchKernelGGL(k_encode_rec_hc, dim3(grid_for(nb, c->hcWaves)), dim3(64), 0, s, x);
+        if (overlap && gi + 2 < nGroups) {
+            // this half is free again: the histogram of the group after next may overwrite it
+            HIPCHK(c, hipEventRecord(c->evHcFree[gi & 1], s));
+            HIPCHK(c, hipStreamWaitEvent(sb, c->evHcFree[gi & 1], 0));
+            if (int rc = hc_build(c, sb, group((gi & 1) * per, gi + 2), true, false)) return rc;
+            HIPCHK(c, hipEventRecord(c->evHcHist, sb));
+        }
+    }
+    return p.ctxBlocks ? hc_ctx_blocks(k, a0) : PLZ4HIP_OK;
+}
+
+// OneThread (route.h).  pre -- levels 3..12, independent blocks: the chain of every block built up front (2 B per position): the
+// parsers then run without their 4 M dependent table updates per 4 MiB block.  Levels 4..12 (8 candidates and more per search) also
+// get the per-hash lists (another 8 B per position): their searches then look at up to 63 candidates per round
+// (hc_find_wider_lists).  A call whose blocks do not fit the memory set aside runs in groups of equal size.
+int hc_one_thread(const HcCall& k, const HcSwitches& sw, const HcPlan& p, CodecArgs a)
+{
+    plz4hip_ctx* const c = k.c;  const hipStream_t s = k.s;  hipError_t e;
+    const int nb = k.nb, maxLen = k.maxLen;
+    if (int rc = ensure_hc(c)) return rc;
+    a.hcWork = c->hc.d; a.nBlocks = nb;
+    a.h12Chain = nullptr;
+    a.blk0 = 0;
+    int per = nb;                     // blocks per launch
+    bool lists = false;
+    if (p.pre) {
+        size_t freeB = 0, totalB = 0;
+        if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
+        // The budget: hc_default_budget, for the chain alone and for the lists alike.  The lists are worth more memory than that:
+        // these kernels live on the number of blocks in flight (7 waves per SIMD fit), and 4096 blocks of 4 MiB with their lists
+        // (40 MiB each) are 160 GiB: a machine that is there for this sets PLZ4HIP_HC_BUDGET_GIB; plz4hip_ctx_trim gives it back.
+        // What the ctx already holds is used in any case.
+        const HcPrePlan pp = hc_pre_plan(freeB, c->h12.bytes, sw.budgetGiB, sw.group, sw.listsOff, a.level, nb, maxLen);
+        lists = pp.lists;
+        if (lists && pp.perLists > c->h12.bytes / hc_pre_layout(1, maxLen, true).perBlock) {   // try the large request first: refused -> the chain alone
+            bool refused = false;  if (int rc = reserve_h12(c, hc_pre_layout(pp.perLists, maxLen, true).total, &refused)) return rc;
+            if (refused) lists = false;
+        }
+        const int perPre = lists ? pp.perLists : pp.perChain;
+        if (getenv("PLZ4HIP_VERBOSE"))
+            fprintf(stderr, "plz4hip: HC level %d, %d blocks: free %zu MiB, held %zu MiB, lists %d, %d blocks per group\n", a.level, nb,
+                    freeB >> 20, c->h12.bytes >> 20, (int)lists, perPre);
+        if (perPre >= 1) {
+            per = perPre;
+            const HcPreLayout L = hc_pre_layout(per, maxLen, lists);
+            bool refused = false;  if (int rc = reserve_h12(c, L.total, &refused)) return rc;
+            if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC chain workspace");
+            bind_hc_pre(a, c->h12.d, L, lists);
+        }
+    }
+    for (int g0 = 0; g0 < nb; g0 += per) {
+        const int ng = nb - g0 < per ? nb - g0 : per;
+        a.blk0 = g0; a.nBlocks = ng;
+        if (a.h12Chain && lists) {
+            if (int rc = hc_build(c, s, a, true, true)) return rc;
+        } else if (a.h12Chain) {
+            a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+            hipLaunchKernelGGL(k_hc_chain, dim3(grid_for(ng, c->cus)), dim3(64), 0, s, a);
+        }
+        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (k.rawMode) hipLaunchKernelGGL(k_encode_raw_hc, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
+        else           hipLaunchKernelGGL(k_encode_rec_hc, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
         HIPCHK(c, hipGetLastError());
-        return PLZ4HIP_OK;
-    };
-    const bool extOk = a.hcEx && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_EXT_OFF") == nullptr;
-    if (a.level == 2 && (!a.hcEx || extOk) && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC_MID_OFF") == nullptr) {
+    }
+    if (p.hcxBehind) { a.hcPfx = nullptr; return hc_hcx_blocks(k, a); }        // (the one-thread kernels passed them over)
+    return PLZ4HIP_OK;
+}
+
+int launch_hc_body(plz4hip_ctx* c, hipStream_t s, const HcSwitches& sw, CodecArgs a, int nb, int maxLen, int rawMode, bool* forked)
+{
+    const HcCall k{c, s, nb, maxLen, rawMode};
+    const HcShape shape{a.level, nb, maxLen, rawMode != 0, a.hcEx != 0, a.dict != nullptr, a.dictLen >= 0, a.linked != 0, a.hcxStart != nullptr};
+    HcPlan p = hc_route(shape, sw);
+    a.hcx = p.hcx;
+    // many small records under one dictionary: no segments to lay out, no lists in device memory, no workspace
+    if (p.route == HcRoute::HcxOnly) { a.hcPfx = nullptr; return hc_hcx_blocks(k, a); }
+    if (p.route == HcRoute::MidStaged) {
         // level 2, blocks up to 4 MiB: the staged call of level 1 with the level-2 walk as its parser (behind external segments too)
         if (int rc = ensure_hc(c)) return rc;
         a.hcWork = c->hc.d;
-        if (a.hcEx) { if (int rc = prep_ext()) return rc; }
+        if (p.prepExt) { if (int rc = hc_prep_ext(k, a)) return rc; }
         bool declined = false;
         if (int rc = launch_l1(c, s, a, nb, maxLen, rawMode, nullptr, &declined)) return rc;
-        if (!declined) return a.hcEx ? ctx_blocks(a) : PLZ4HIP_OK;
+        if (!declined) return p.ctxBlocks ? hc_ctx_blocks(k, a) : PLZ4HIP_OK;
         a.hcPfx = nullptr;                                                   // (no workspace: every block on the one-thread parser)
+        p = hc_route(shape, sw, true);
     }
-    // levels 3..12 with a dictionary and/or linked blocks, blocks up to 4 MiB (round 4): the same route as the lazy levels -- chain and
-    // lists over segment + block, the walk in segments, stitched, records through the emit stage -- with the segment rules of the
-    // reference kept in the finders (lz4hc_lazy_device.inl, kD); level 12 walks its optimal parser there as well.  Only the blocks
-    // <= 4 KiB under a dictionary context (usingDictCtxHc: two sets of tables) keep the one-thread parser, launched behind.
-    const bool lazyEx = extOk && a.level >= 3;
-    const bool lazy = use_lazy(a, maxLen) || lazyEx;
-    if (lazy || use_h12(a, maxLen)) {
-        // level 12 up to 4 MiB: its parser in segments as well (records; larger raw blocks keep the one-wave parser that writes bytes)
-        const bool seg12 = !lazy && maxLen > 0 && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_HC12_SEG_OFF") == nullptr;
-        const bool segs = lazy || seg12;
-        HcLayout pl;
-        if (int rc = plan_h12(c, nb, maxLen + (lazyEx ? 65536 : 0), &pl, segs, !lazy)) return rc;
-        if (lazyEx) { if (int rc = prep_ext()) return rc; }
-        c->h12ErrOff = pl.offErr;
-        a.rawMode = rawMode;
-        if (segs) {
-            if (lazy && a.level >= 10) { if (int rc = ensure_hc(c)) return rc; a.hcWork = c->hc.d; }
-            if (!c->hcLazyWaves) {
-                int per = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_hc_lazy<false>, 64, 0) != hipSuccess || per < 1) per = 8;
-                c->hcLazyWaves = c->cus * per;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_hc_lazy<true>, 64, 0) != hipSuccess || per < 1) per = 8;
-                c->hcLazyExWaves = c->cus * per;
-            }
-            a.l1MaxLen = maxLen;
-            a.lzMinSeg = 8192;
-            if (const char* v = getenv("PLZ4HIP_HC_MIN_SEG")) { const int m = atoi(v); if (m >= 64) a.lzMinSeg = m; }     // tests: many segments in small blocks
-        }
-        a.h12Gather = 12; a.h12Idle = 16;
-        if (const char* v = getenv("PLZ4HIP_HC12_GATHER")) a.h12Gather = atoi(v);
-        if (const char* v = getenv("PLZ4HIP_HC12_IDLE")) a.h12Idle = atoi(v);
-        bind_hc(a, c->h12.d, pl, segs, 0);
-        int nGroups = (nb + pl.group - 1) / pl.group;
-        int per = (nb + nGroups - 1) / nGroups;                           // groups of equal size (<= pl.group)
-        HIPCHK(c, hipMemsetAsync(a.h12Err, 0, 4, s));                      // the give-up flag is per call (k_hc12_parse reports it per block)
-        // Levels 3..11: the list builder is one wave per CU around 128 KiB of LDS (0.3 s per 2048 blocks with the chip all but idle),
-        // the walk needs no LDS.  A call of enough blocks therefore runs in at least four groups over the two halves of the
-        // workspace, the builder of group g+1 on a second stream beside the walk of group g (which leaves it a wave slot per CU);
-        // the histogram of group g+1 (1024-thread workgroups that would not find room beside the walk) runs between two walks.
-        int overlapMin = 2048;
-        if (const char* v = getenv("PLZ4HIP_HC_OVERLAP_MIN")) overlapMin = atoi(v);           // tests: the pipeline on a handful of blocks
-        const bool overlap = lazy && nb >= overlapMin && nb >= 2 && pl.group >= 2 && getenv("PLZ4HIP_HC_OVERLAP_OFF") == nullptr;   // (two groups' worth of workspace)
-        if (overlap) {
-            int want = 4;
-            if (const char* v = getenv("PLZ4HIP_HC_OVERLAP_GROUPS")) { want = atoi(v); if (want < 2) want = 2; }
-            int tgt = pl.group / 2 < (nb + want - 1) / want ? pl.group / 2 : (nb + want - 1) / want;
-            if (tgt < 1) tgt = 1;
-            nGroups = (nb + tgt - 1) / tgt;
-            per = (nb + nGroups - 1) / nGroups;
-            if (!c->hcBuildStream) HIPCHK(c, hipStreamCreateWithFlags(&c->hcBuildStream, hipStreamNonBlocking));
-            for (hipEvent_t* ev : {&c->evHcFork, &c->evHcHist, &c->evHcChain[0], &c->evHcChain[1], &c->evHcFree[0], &c->evHcFree[1]})
-                if (!*ev) HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
-        }
-        // the workspace pointers of the half a group uses: every per-block array moved on by k blocks
-        const auto half = [&](CodecArgs x, int k) { bind_hc(x, c->h12.d, pl, segs, k); return x; };
-        const auto build = [&](hipStream_t st, CodecArgs x, bool hist, bool chain) -> int {
-            hipError_t e2;
-            if (hist)  { x.queue = next_queue(c, st, &e2); HIPCHK(c, e2); hipLaunchKernelGGL(k_hc12_hist, dim3(grid_for(x.nBlocks, c->cus)), dim3(1024), 0, st, x); }
-            if (chain) { x.queue = next_queue(c, st, &e2); HIPCHK(c, e2); hipLaunchKernelGGL(k_hc12_chain, dim3(grid_for(x.nBlocks, c->cus)), dim3(64), 0, st, x); }
-            return PLZ4HIP_OK;
-        };
-        const CodecArgs a0 = a;
-        // The groups.  With the builder beside the walk only the first group's builder is exposed, so the groups start small and
-        // double (a builder takes about half the time of the walk over the same blocks: the next group's is done when this
-        // group's walk is) until they have the full size.
-        std::vector<int> gStart, gSize;
-        for (int at = 0, sz = overlap ? (per / 8 > 0 ? per / 8 : 1) : per; at < nb; ) {
-            const int n_ = nb - at < sz ? nb - at : sz;
-            gStart.push_back(at); gSize.push_back(n_);
-            at += n_;
-            sz = sz * 2 < per ? sz * 2 : per;
-        }
-        nGroups = (int)gStart.size();
-        if (overlap) {
-            hipStream_t sb = c->hcBuildStream;
-            HIPCHK(c, hipEventRecord(c->evHcFork, s));
-            HIPCHK(c, hipStreamWaitEvent(sb, c->evHcFork, 0));
-            *forked = true;
-            CodecArgs x = half(a0, 0); x.blk0 = gStart[0]; x.nBlocks = gSize[0];
-            if (int rc = build(sb, x, true, true)) return rc;
-            HIPCHK(c, hipEventRecord(c->evHcChain[0], sb));
-            if (nGroups > 1) {
-                x = half(a0, per); x.blk0 = gStart[1]; x.nBlocks = gSize[1];
-                if (int rc = build(sb, x, true, false)) return rc;
-                HIPCHK(c, hipEventRecord(c->evHcHist, sb));
-            }
-        }
-        for (int gi = 0; gi < nGroups; ++gi) {
-            const int g0 = gStart[gi], ng = gSize[gi];
-            if (overlap) a = half(a0, (gi & 1) * per);
-            a.blk0 = g0; a.nBlocks = ng;
-            if (overlap) {
-                hipStream_t sb = c->hcBuildStream;
-                HIPCHK(c, hipStreamWaitEvent(s, c->evHcChain[gi & 1], 0));
-                if (gi + 1 < nGroups) {
-                    HIPCHK(c, hipStreamWaitEvent(s, c->evHcHist, 0));           // the next group's histogram is done: its builder starts now
-                    CodecArgs x = half(a0, ((gi + 1) & 1) * per); x.blk0 = gStart[gi + 1]; x.nBlocks = gSize[gi + 1];
-                    if (int rc = build(sb, x, false, true)) return rc;
-                    HIPCHK(c, hipEventRecord(c->evHcChain[(gi + 1) & 1], sb));
-                }
-            } else {
-                if (int rc = build(s, a, true, true)) return rc;
-            }
-            a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-            if (!lazy) hipLaunchKernelGGL(k_hc12_search, dim3(grid_for(ng, c->cus)), dim3(1024), 0, s, a);
-            a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-            if (!lazy && !seg12) hipLaunchKernelGGL(k_hc12_parse, dim3(grid_for(ng, c->h12ParseWaves)), dim3(64), 0, s, a);
-            else {
-                // segments per block: as many as there are 8 KiB pieces, at most 512.  Measured at 4096 blocks of 4 MiB, level 3 /
-                // level 9: 16 segments 7522 / 4870, 32: 7734 / 4986, 64: 7908 / 5090, 128: 8071 / 5691, 256: 8279 / 5958, 512: 8602 /
-                // 6139, 1024: 8642 / 6159 MiB/s.  Far more walks than the chip holds waves: the queue hands neighbouring segments of
-                // one block to neighbouring waves, which then share the block's source and lists in L2, and short items even out.
-                a.lzSegs = kLzMaxSegs;
-                if (const char* v = getenv("PLZ4HIP_HC_SEGS")) a.lzSegs = atoi(v);
-                a.lzSegs = a.lzSegs < 1 ? 1 : (a.lzSegs > kLzMaxSegs ? kLzMaxSegs : a.lzSegs);
-                if (seg12) {
-                    hipLaunchKernelGGL(k_hc12_seg, dim3(grid_for(ng * a.lzSegs, c->h12SegWaves)), dim3(64), 0, s, a);
-                    a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-                    hipLaunchKernelGGL(k_hc12_stitch, dim3(grid_for(ng, c->h12SegWaves)), dim3(64), 0, s, a);
-                } else {
-                const int resident = lazyEx ? c->hcLazyExWaves : c->hcLazyWaves;
-                int lzWaves = a.level >= 10 && c->hcWaves < resident ? c->hcWaves : resident;   // (a price table per wave)
-                if (overlap && lzWaves > 2 * c->cus) lzWaves -= c->cus;                    // a wave slot (and its registers) per CU for the builder
-                if (lazyEx) hipLaunchKernelGGL(k_hc_lazy<true>, dim3(grid_for(ng * a.lzSegs, lzWaves)), dim3(64), 0, s, a);
-                else        hipLaunchKernelGGL(k_hc_lazy<false>, dim3(grid_for(ng * a.lzSegs, lzWaves)), dim3(64), 0, s, a);
-                a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-                if (lazyEx) hipLaunchKernelGGL(k_hc_stitch<true>, dim3(grid_for(ng, lzWaves)), dim3(64), 0, s, a);
-                else        hipLaunchKernelGGL(k_hc_stitch<false>, dim3(grid_for(ng, lzWaves)), dim3(64), 0, s, a);
-                }
-                hipLaunchKernelGGL(k_hc_gather, dim3(ng >= 1024 ? 4 : 16, ng), dim3(256), 0, s, a);
-                int wg = (16384 / ng) / 4;                                  // emit: waves per block so that a small call still spreads over the chip
-                if (wg > (pl.maxChunks + 3) / 4) wg = (pl.maxChunks + 3) / 4;
-                if (wg < 1) wg = 1;
-                hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
-                hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
-                hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
-                if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 15) / 16), dim3(64), 0, s, a);
-            }
-            HIPCHK(c, hipGetLastError());
-            if (overlap && gi + 2 < nGroups) {
-                // this half is free again: the histogram of the group after next may overwrite it
-                hipStream_t sb = c->hcBuildStream;
-                HIPCHK(c, hipEventRecord(c->evHcFree[gi & 1], s));
-                HIPCHK(c, hipStreamWaitEvent(sb, c->evHcFree[gi & 1], 0));
-                CodecArgs x = half(a0, (gi & 1) * per); x.blk0 = gStart[gi + 2]; x.nBlocks = gSize[gi + 2];
-                if (int rc = build(sb, x, true, false)) return rc;
-                HIPCHK(c, hipEventRecord(c->evHcHist, sb));
-            }
-        }
-        if (lazyEx) { if (int rc = ctx_blocks(a0)) return rc; }
-    } else {
-        if (int rc = ensure_hc(c)) return rc;
-        a.hcWork = c->hc.d; a.nBlocks = nb;
-        a.h12Chain = nullptr;
-        a.blk0 = 0;
-        int per = nb;                     // blocks per launch
-        bool lists = false;
-        if (a.level >= 3 && !a.hcEx && maxLen >= 4096 && getenv("PLZ4HIP_HC_PRE_OFF") == nullptr) {
-            // levels 3..12, independent blocks: the chain of every block built up front (2 B per position): the parsers then run
-            // without their 4 M dependent table updates per 4 MiB block.  Levels 4..12 (8 candidates and more per search)
-            // also get the per-hash lists (another 8 B per position): their searches then look at up to 63 candidates per
-            // round (hc_find_wider_lists).  A call whose blocks do not fit the memory set aside runs in groups of equal size.
-            size_t freeB = 0, totalB = 0;
-            if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-            // The budget: hc_default_budget, for the chain alone and for the lists alike.  The lists are worth more memory than that:
-            // these kernels live on the number of blocks in flight (7 waves per SIMD fit), and 4096 blocks of 4 MiB with their lists
-            // (40 MiB each) are 160 GiB: a machine that is there for this sets PLZ4HIP_HC_BUDGET_GIB; plz4hip_ctx_trim gives it back.
-            // What the ctx already holds is used in any case.
-            long budgetGiB = 0;  int group = 0;
-            if (const char* v = getenv("PLZ4HIP_HC_BUDGET_GIB")) budgetGiB = atol(v);
-            if (const char* v = getenv("PLZ4HIP_HC_GROUP")) group = atoi(v);
-            const HcPrePlan pp = hc_pre_plan(freeB, c->h12.bytes, budgetGiB, group, getenv("PLZ4HIP_HC_LISTS_OFF") != nullptr, a.level, nb, maxLen);
-            lists = pp.lists;
-            if (lists && pp.perLists > c->h12.bytes / hc_pre_layout(1, maxLen, true).perBlock) {   // try the large request first: refused -> the chain alone
-                bool refused = false;  if (int rc = reserve_h12(c, hc_pre_layout(pp.perLists, maxLen, true).total, &refused)) return rc;
-                if (refused) lists = false;
-            }
-            const int perPre = lists ? pp.perLists : pp.perChain;
-            if (getenv("PLZ4HIP_VERBOSE"))
-                fprintf(stderr, "plz4hip: HC level %d, %d blocks: free %zu MiB, held %zu MiB, lists %d, %d blocks per group\n", a.level, nb,
-                        freeB >> 20, c->h12.bytes >> 20, (int)lists, perPre);
-            if (perPre >= 1) {
-                per = perPre;
-                const HcPreLayout L = hc_pre_layout(per, maxLen, lists);
-                bool refused = false;  if (int rc = reserve_h12(c, L.total, &refused)) return rc;
-                if (refused) return fail(c, PLZ4HIP_E_NOMEM, "HC chain workspace");
-                bind_hc_pre(a, c->h12.d, L, lists);
-            }
-        }
-        for (int g0 = 0; g0 < nb; g0 += per) {
-            const int ng = nb - g0 < per ? nb - g0 : per;
-            a.blk0 = g0; a.nBlocks = ng;
-            if (a.h12Chain && lists) {
-                a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-                hipLaunchKernelGGL(k_hc12_hist, dim3(grid_for(ng, c->cus)), dim3(1024), 0, s, a);
-                a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-                hipLaunchKernelGGL(k_hc12_chain, dim3(grid_for(ng, c->cus)), dim3(64), 0, s, a);
-            } else if (a.h12Chain) {
-                a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-                hipLaunchKernelGGL(k_hc_chain, dim3(grid_for(ng, c->cus)), dim3(64), 0, s, a);
-            }
-            a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-            if (rawMode) hipLaunchKernelGGL(k_encode_raw_hc, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
-            else         hipLaunchKernelGGL(k_encode_rec_hc, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
-            HIPCHK(c, hipGetLastError());
-        }
-        if (a.hcx) { a.hcPfx = nullptr; if (int rc = hcx_blocks(a)) return rc; }   // (the one-thread kernels passed them over)
-    }
-    return PLZ4HIP_OK;
+    return p.route == HcRoute::Segmented ? hc_segmented(k, sw, p, a, forked) : hc_one_thread(k, sw, p, a);
 }
 
 // The pointers of a level-1 group workspace (L1Layout) and of the few-block parse's (FxLayout; returns the blocks' FxlBlk array)
@@ -2359,80 +2352,82 @@ FxlBlk* bind_fx(FxArgs& fx, uint8_t* base, const FxLayout& F, bool hist)
     return hist ? (FxlBlk*)(base + F.offBlk) : nullptr;
 }
 
-// Enqueue one level-1 call of nb independent blocks without dictionary (a: everything but queue / workspace filled in) on s.
-// Whether a level-1 call of nb blocks with history outside the block (a dictionary, linked blocks) takes the few-block path:
-// at most PLZ4HIP_FX_MAX_BLOCKS blocks, the largest of kFxMinLen .. 4 MiB, and PLZ4HIP_FX_LINKED not 0 (read per call).
-bool fxl_wanted(int nb, int maxLen)
+// Which of the ctx's level-1 workspaces a call on s takes: the one this stream used last; else one whose last job is over (no second
+// allocation for streams that merely take turns); else one that does not exist yet; else the first one (and the wait for it).
+int pick_l1_workspace(plz4hip_ctx* c, hipStream_t s, const L1Switches& sw)
 {
-    if (const char* v = getenv("PLZ4HIP_FX_LINKED")) { if (atoi(v) == 0) return false; }
-    int fxMax = kFxMaxBlocks;
-    if (const char* v = getenv("PLZ4HIP_FX_MAX_BLOCKS")) fxMax = atoi(v);
-    return nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock && getenv("PLZ4HIP_L1_FUSED") == nullptr;
+    const int nws = sw.oneWorkspace ? 1 : plz4hip_ctx::kL1Shared;
+    int mine = -1, idle = -1, fresh = -1;
+    for (int i = 0; i < nws; ++i) {
+        if (c->l1[i].d && c->l1Order[i].stream == s && mine < 0) mine = i;
+        if (c->l1[i].d && idle < 0 && c->l1Order[i].idle()) idle = i;
+        if (!c->l1[i].d && fresh < 0) fresh = i;
+    }
+    return mine >= 0 ? mine : (idle >= 0 ? idle : (fresh >= 0 ? fresh : 0));
 }
 
-// Whether a level-1 call of MANY blocks with history outside the block, from device-resident plaintext, takes the staged design
-// (k_l1x_parse + the kSeg emit stage) or the one-kernel encoder k_encode_rec_dict: PLZ4HIP_L1X (read per call; 0: the one-kernel
-// encoder, anything else: staged).  The default is a measurement: profiles/l1x_rate.json, DESIGN 3.3.
-constexpr bool kL1xDefault = true;
-bool l1x_on()
+// The parse launch of a group of the staged call that fills the device (Parse, Duplex): ordered behind the other stream's by the gate
+int l1_gate(plz4hip_ctx* c, hipStream_t s, CodecArgs& a, int ng)
 {
-    if (getenv("PLZ4HIP_L1_FUSED") != nullptr) return false;
-    if (const char* v = getenv("PLZ4HIP_L1X")) return atoi(v) != 0;
-    return kL1xDefault;
+    // (only behind a launch that fills the device: the parse launches of the host-buffer calls' chunks -- a third of the
+    // wave slots each -- are meant to share it, and behind the gate they would run one after the other: 2560 blocks through
+    // host memory 470 -> 680 ms)
+    if (c->gatePending && c->gateStream != s && c->gateBlocks >= 8 * c->cus)
+        hipLaunchKernelGGL(k_parse_gate, dim3(1), dim3(64), 0, s, (const uint32_t*)c->d_gate, c->gateSeq);
+    if (c->gateSeq >= 0x7FFF0000u) {                                    // (once in two billion launches: start over)
+        HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, zero_sync(c, c->d_gate, sizeof(uint32_t))); c->gateSeq = 0;
+    }
+    a.gate = c->d_gate; a.gateSeq = ++c->gateSeq;
+    c->gatePending = true; c->gateStream = s; c->gateBlocks = ng;
+    return PLZ4HIP_OK;
 }
 
-// rawMode: LZ4 blocks (result = bytes or 0), else records.  Blocks up to 4 MiB run in stages (lz4_seq_device.inl): the
-// workspace holds 8 bytes per possible sequence -- 2 bytes per input byte -- of one group of blocks; a call that does not fit
-// the memory set aside (half of what is free; PLZ4HIP_L1_BUDGET_GIB) runs in groups of equal size.  ws: the workspace to use
-// (a staging slot's own, always used from that slot's stream) or null for the ctx's, which is ordered across streams.
-// Larger blocks (raw block API only) and calls that do not say how long their blocks are keep the fused kernels.
-// midDeclined: the call is a level-2 call (k_hc_mid instead of k_l1_parse, records without catch-up); set when no workspace could
-// be had, the caller then runs its one-kernel path.
-// rider: the record decode of another call (queue filled in) that shares the parse kernel's launch (k_l1_duplex); a call that
-// runs in groups carries it in its first group, one that takes the fused kernels launches it by itself.
+// One parse launch shared with the record decode of another call: workgroups of P + D waves, what the device holds at once unless
+// neither role has that much to do
+int launch_duplex(plz4hip_ctx* c, hipStream_t s, const L1Switches& sw, const CodecArgs& a, const CodecArgs& rider, int ng)
+{
+    const int P = sw.duplexP, D = sw.duplexD;
+#define DUPLEX_CASE(PP, DD) \
+    if (P == PP && D == DD) { \
+        int wgs = ((ng + PP - 1) / PP > (rider.nBlocks + DD - 1) / DD) ? (ng + PP - 1) / PP : (rider.nBlocks + DD - 1) / DD; \
+        const int hold = c->cus * duplex_wgs_per_cu(PP, DD); \
+        if (wgs > hold) wgs = hold; \
+        if (sw.duplexPrio) hipLaunchKernelGGL((k_l1_duplex<PP, DD, 3>), dim3(wgs), dim3(64 * (PP + DD)), 0, s, a, rider); \
+        else               hipLaunchKernelGGL((k_l1_duplex<PP, DD, 0>), dim3(wgs), dim3(64 * (PP + DD)), 0, s, a, rider); \
+        return PLZ4HIP_OK; \
+    }
+    DUPLEX_CASE(1, 1) DUPLEX_CASE(1, 2) DUPLEX_CASE(3, 4) DUPLEX_CASE(9, 7)      // (9+5, 9+3, 3+2 measured as well: DESIGN 3.1b)
+#undef DUPLEX_CASE
+    return fail(c, PLZ4HIP_E_ARG, "PLZ4HIP_DUPLEX: not a built combination");
+}
+
+// Enqueue one level-1 call of nb blocks (a: everything but queue / workspace filled in) on s; the routes and their fallbacks: route.h,
+// DESIGN 2.  rawMode: LZ4 blocks (result = bytes or 0), else records.  The staged routes' workspace holds 8 bytes per possible
+// sequence -- 2 bytes per input byte -- of one group of blocks; a call that does not fit the memory set aside (half of what is free;
+// PLZ4HIP_L1_BUDGET_GIB) runs in groups of equal size.  ws: the workspace to use (a staging slot's own, always used from that slot's
+// stream) or null for the ctx's, which is ordered across streams.
+// midDeclined: the call is a level-2 call; set when no workspace could be had, the caller then runs its one-kernel path.
+// rider: the record decode of another call (queue filled in) that shares the parse kernel's launch; a call that runs in groups
+// carries it in its first group, one that takes the fused kernels launches it by itself.
 // hist: the blocks have history outside the block (a: dictionary / linked fields filled in, 64 KiB of room in front of every input
-// block).  Such a call is here for the few-block path's external-segment flavour (fxl_wanted has said yes); whenever that path
-// cannot be had -- no workspace, the fused kernels -- it runs k_encode_rec_dict / k_encode_raw_dict, one wave per block, as ever.
-// l1x (with hist; the device-resident entry points plz4hip_dev_encode_records_ex / _body_ex): fxl_wanted is asked here, and a call
-// that is not the few-block path's takes the staged design with one wave per block (k_l1x_parse, then the kSeg emit stage); the
-// workspace then carries one FxlBlk per block of a group behind the records.  Records straight into a frame body (a.bodyOff) have
-// no one-kernel form: PLZ4HIP_E_NOMEM when the workspace cannot be had.
+// block); l1x: from the device-resident entry points, whose workspace carries one FxlBlk per block of a group behind the records.
 int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, int rawMode, DeviceBuffer* ws, bool* midDeclined,
-              const CodecArgs* rider, bool hist, bool l1x)
+              const CodecArgs* rider, bool hist, bool l1x, const L1Switches* read)
 {
     hipError_t e;
-    const auto dict_kernels = [&]() -> int {
-        if (a.bodyOff) return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
-        a.blk0 = 0; a.nBlocks = nb;
-        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-        if (rawMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a); else ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
-        HIPCHK(c, hipGetLastError());
-        return PLZ4HIP_OK;
-    };
+    const L1Switches sw = read ? *read : read_l1_switches();                    // (read: the caller had to ask l1_want itself)
     const bool mid = midDeclined != nullptr;
+    const L1Shape shape{nb, maxLen, rawMode != 0, mid, rider != nullptr, hist, l1x, a.bodyOff != nullptr, hist && a.dictLen >= 8};
+    const L1Want want = l1_want(shape, sw);
     a.rawMode = rawMode; a.blk0 = 0; a.nBlocks = nb;
     const bool shared = (ws == nullptr);
     int wsi = 0;
-    if (shared) {
-        // the workspace this stream used last; else one whose last job is over (no second allocation for streams that merely take
-        // turns); else one that does not exist yet; else the first one (and the wait below)
-        int nws = plz4hip_ctx::kL1Shared;
-        if (const char* v = getenv("PLZ4HIP_L1_WORKSPACES")) { if (atoi(v) == 1) nws = 1; }
-        int mine = -1, idle = -1, fresh = -1;
-        for (int i = 0; i < nws; ++i) {
-            if (c->l1[i].d && c->l1Order[i].stream == s && mine < 0) mine = i;
-            if (c->l1[i].d && idle < 0 && c->l1Order[i].idle()) idle = i;
-            if (!c->l1[i].d && fresh < 0) fresh = i;
-        }
-        wsi = mine >= 0 ? mine : (idle >= 0 ? idle : (fresh >= 0 ? fresh : 0));
-        ws = &c->l1[wsi];
-    }
-    bool fused = maxLen <= 0 || maxLen > kSeqMaxBlock || getenv("PLZ4HIP_L1_FUSED") != nullptr;
-    if (hist && l1x && !l1x_on() && !fxl_wanted(nb, maxLen)) fused = true;              // (the one-kernel encoder: no workspace)
+    if (shared) { wsi = pick_l1_workspace(c, s, sw); ws = &c->l1[wsi]; }
+    bool granted = want.staged;
     const auto need_for = [&](int per) { return l1_layout(per, maxLen, l1x).total; };
     int per = nb;
-    if (shared && !fused && wsi != 0 && !ws->d && c->l1Refused > 0) { c->l1Refused--; wsi = 0; ws = &c->l1[0]; }   // (refused a moment ago)
-    if (shared && !fused && wsi != 0 && !ws->d) {
+    if (shared && granted && wsi != 0 && !ws->d && c->l1Refused > 0) { c->l1Refused--; wsi = 0; ws = &c->l1[0]; }   // (refused a moment ago)
+    if (shared && granted && wsi != 0 && !ws->d) {
         // a SECOND workspace is there for overlap: it is taken whole or not at all (a smaller one would cut this call into groups,
         // which costs more than waiting for the first workspace does)
         bool refused = false;  HIPCHK(c, ws->reserve(need_for(nb), c->l1Order[wsi], &refused));
@@ -2442,129 +2437,94 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         }
     }
     StreamOrder* const order = shared ? &c->l1Order[wsi] : nullptr;                      // (a slot's own workspace: the slot's stream)
-    if (!fused && need_for(nb) > ws->bytes) {
+    if (granted && need_for(nb) > ws->bytes) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return fail(c, PLZ4HIP_E_DEVICE, "hipMemGetInfo");
-        long budgetGiB = 0, budgetMiB = 0;
-        if (const char* v = getenv("PLZ4HIP_L1_BUDGET_GIB")) budgetGiB = atol(v);
-        if (const char* v = getenv("PLZ4HIP_L1_BUDGET_MIB")) budgetMiB = atol(v);                                               // tests: force groups
         int rc = PLZ4HIP_OK;
-        const int64_t grp = l1_first_group(freeB, ws->bytes, budgetGiB, budgetMiB, l1_layout(1, maxLen, l1x).perBlock, nb);
+        const int64_t grp = l1_first_group(freeB, ws->bytes, sw.budgetGiB, sw.budgetMiB, l1_layout(1, maxLen, l1x).perBlock, nb);
         const int got = fit_groups(nb, grp, false, [&](int p, bool* refused) {
             per = p;
             HIPCHK(c, order ? ws->reserve(need_for(per), *order, refused) : ws->reserve(need_for(per), s, refused));
             return (int)PLZ4HIP_OK;
         }, &rc);
         if (rc) return rc;
-        if (!got) fused = true;                                                         // not even one block: the fused kernels need no workspace
+        if (!got) granted = false;                                                      // not even one block: the kernels that need no workspace
         if (getenv("PLZ4HIP_VERBOSE"))
-            fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, fused ? " (fused)" : "");
+            fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, granted ? "" : " (fused)");
     }
-    if (fused && hist) return dict_kernels();
-    if (fused && a.bodyOff) return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
-    if (fused && mid) { *midDeclined = true; return PLZ4HIP_OK; }            // (behind the refusal above: the one-thread parsers write staged records too)
-    if (fused) {
-        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-        if (rawMode) ENC_LAUNCH(k_encode_raw, nb, c, s, a); else ENC_LAUNCH(k_encode_rec, nb, c, s, a);
-        if (rider) { launch_rec_verify(s, *rider); hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(rider->nBlocks, c->decWaves)), dim3(64), 0, s, *rider); }
-        HIPCHK(c, hipGetLastError());
-        return PLZ4HIP_OK;
-    }
-    // from here on the job is marked behind whatever was enqueued, whichever way the call ends
+    // from here on the jobs are marked behind whatever was enqueued, whichever way the call ends
     MarkOnExit job, fxJob;
-    if (order) { HIPCHK(c, order->wait(s)); job.arm(*order, s); }
-    const L1Layout L = l1_layout(per, maxLen, l1x);
-    a.l1MaxLen = maxLen;
-    bind_l1(a, ws->d, L);
-    const int maxChunks = L.maxChunks;
-    // A call of at most PLZ4HIP_FX_MAX_BLOCKS blocks (0: off) whose blocks may take liblz4's byU32 tables has its parse cut across the
-    // chip (lz4_fx_device.inl) in pieces of PLZ4HIP_FX_PIECE_KIB, guessed starts PLZ4HIP_FX_WARMUP_KIB early.  Its workspace is sized
-    // per call (a group of `per` blocks); when it cannot be had, the call parses as below.
     FxArgs fx{};
     FxlBlk* xb = nullptr;                                                       // hist: per block of a group, its segment (k_fxl_prep)
-    bool useFx = false;
-    {
-        int fxMax = kFxMaxBlocks;
-        if (const char* v = getenv("PLZ4HIP_FX_MAX_BLOCKS")) fxMax = atoi(v);
-        if (!mid && !rider && nb <= fxMax && maxLen >= kFxMinLen && maxLen <= kSeqMaxBlock && (!l1x || fxl_wanted(nb, maxLen))) {
-            int pk = 64, wk = 64;
-            if (const char* v = getenv("PLZ4HIP_FX_PIECE_KIB")) { const int x = atoi(v); if (x >= 1 && x <= 4096) pk = x; }
-            if (const char* v = getenv("PLZ4HIP_FX_WARMUP_KIB")) { const int x = atoi(v); if (x >= 0 && x <= 4096) wk = x; }
-            fx.pb = pk << 10; fx.warm = wk << 10;
-            fx.P = (maxLen + fx.pb - 1) / fx.pb; fx.recStride = fx_rec_stride_host(fx.pb); fx.cnt = c->d_counters;
+    L1Layout L{};
+    bool fxGranted = false;
+    if (granted) {
+        if (order) { HIPCHK(c, order->wait(s)); job.arm(*order, s); }
+        L = l1_layout(per, maxLen, l1x);
+        a.l1MaxLen = maxLen;
+        bind_l1(a, ws->d, L);
+        if (want.fx) {
+            // the few-block parse's workspace is sized per call (a group of `per` blocks); when it cannot be had, the call parses as the others
+            fx.pb = want.piece; fx.warm = want.warm; fx.P = want.P; fx.recStride = fx_rec_stride_host(fx.pb); fx.cnt = c->d_counters;
             const FxLayout F = fx_layout(per, fx.P, fx.recStride, hist);
             HIPCHK(c, c->fxOrder.wait(s));
             bool refused = false;  HIPCHK(c, c->fx.reserve(F.total, c->fxOrder, &refused));
-            if (!refused) {
-                xb = bind_fx(fx, c->fx.d, F, hist);
-                useFx = true;
-                fxJob.arm(c->fxOrder, s);
-            }
+            if (!refused) { xb = bind_fx(fx, c->fx.d, F, hist); fxGranted = true; fxJob.arm(c->fxOrder, s); }
         }
     }
-    if (hist && !useFx && !(l1x && l1x_on())) return dict_kernels();
-    if (hist && !useFx) xb = (FxlBlk*)(ws->d + L.offBlk);                                     // (the bulk route: behind the group's records)
+    const L1Route route = l1_route(shape, sw, want, granted, fxGranted);
+    switch (route) {
+    case L1Route::NoMemBody:
+        return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
+    case L1Route::MidDeclined:                                                  // (the one-thread parsers write staged records too)
+        *midDeclined = true; return PLZ4HIP_OK;
+    case L1Route::DictKernels: case L1Route::Fused:
+        a.blk0 = 0; a.nBlocks = nb;
+        a.queue = next_queue(c, s, &e); HIPCHK(c, e);
+        if (route == L1Route::DictKernels) { if (rawMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a); else ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a); }
+        else                               { if (rawMode) ENC_LAUNCH(k_encode_raw, nb, c, s, a); else ENC_LAUNCH(k_encode_rec, nb, c, s, a); }
+        if (route == L1Route::Fused && rider) { launch_rec_verify(s, *rider); hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(rider->nBlocks, c->decWaves)), dim3(64), 0, s, *rider); }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, job.leave());
+        HIPCHK(c, fxJob.leave());
+        return PLZ4HIP_OK;
+    default: break;
+    }
+    if (route == L1Route::L1x) xb = (FxlBlk*)(ws->d + L.offBlk);                 // (the bulk route: behind the group's records)
     for (int g0 = 0; g0 < nb; g0 += per) {
         const int ng = nb - g0 < per ? nb - g0 : per;
         a.blk0 = g0; a.nBlocks = ng;
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         if (rider && g0 == 0) launch_rec_verify(s, *rider);                     // (in front of the gate: beside the other stream's launch)
-        const bool signals = !mid && !getenv("PLZ4HIP_EXP_NO_GATE");            // (the level-1 parse and the duplex launch)
-        if (useFx || hist) a.gate = nullptr;                                    // (neither waits for nor signals the gate)
-        else if (signals) {
-            // (only behind a launch that fills the device: the parse launches of the host-buffer calls' chunks -- a third of the
-            // wave slots each -- are meant to share it, and behind the gate they would run one after the other: 2560 blocks through
-            // host memory 470 -> 680 ms)
-            if (c->gatePending && c->gateStream != s && c->gateBlocks >= 8 * c->cus)
-                hipLaunchKernelGGL(k_parse_gate, dim3(1), dim3(64), 0, s, (const uint32_t*)c->d_gate, c->gateSeq);
-            if (c->gateSeq >= 0x7FFF0000u) {                                    // (once in two billion launches: start over)
-                HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, zero_sync(c, c->d_gate, sizeof(uint32_t))); c->gateSeq = 0;
-            }
-            a.gate = c->d_gate; a.gateSeq = ++c->gateSeq;
-            c->gatePending = true; c->gateStream = s; c->gateBlocks = ng;
-        } else {
-            a.gate = nullptr; c->gatePending = false;
-        }
-        if (mid && a.hcPfx) hipLaunchKernelGGL(k_hc_mid<true>, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
-        else if (mid) hipLaunchKernelGGL(k_hc_mid<false>, dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
-        else if (useFx && hist) {
+        a.gate = nullptr;                                                       // (only Parse and Duplex wait for and signal the gate)
+        if (route == L1Route::Parse || route == L1Route::Duplex) {
+            if (sw.noGate) c->gatePending = false;
+            else if (int rc = l1_gate(c, s, a, ng)) return rc;
+        } else if (route == L1Route::Mid) c->gatePending = false;
+        switch (route) {
+        case L1Route::Mid:
+            hipLaunchKernelGGL(hc_mid_kernel(a.hcPfx != nullptr), dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
+            break;
+        case L1Route::Fxl:
             // (every block reads block gi - 1's plaintext tail out of the call's input, whichever group that block is in)
             if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
             hipLaunchKernelGGL(k_fxl_prep, dim3(ng), dim3(64), 0, s, a, fx, xb);
             for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fxl_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, (const FxlBlk*)xb, r);
             hipLaunchKernelGGL(k_fxl_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx, (const FxlBlk*)xb);
-        }
-        else if (useFx) {
+            break;
+        case L1Route::Fx:
             // P rounds are always enough (lz4_fx_device.inl); the rounds after the last change find nothing to do
             if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
             for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fx_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, r);
             hipLaunchKernelGGL(k_fx_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx);
-        }
-        else if (hist) {
-            // one wave per block, every block one exact run
+            break;
+        case L1Route::L1x:                                                       // one wave per block, every block one exact run
             ENC_LAUNCH(k_l1x_parse, ng, c, s, a, xb, c->d_counters);
-        }
-        else if (rider && g0 == 0) {
-            // workgroups: what the device holds at once, unless neither role has that much to do
-            int P = 1, D = 1, prio = 3;
-            if (const char* ev = getenv("PLZ4HIP_DUPLEX")) { if (sscanf(ev, "%d,%d", &P, &D) != 2) { P = 1; D = 1; } }
-            if (const char* ev = getenv("PLZ4HIP_DUPLEX_PRIO")) prio = atoi(ev);
-#define DUPLEX_CASE(PP, DD) \
-            if (P == PP && D == DD) { \
-                int wgs = ((ng + PP - 1) / PP > (rider->nBlocks + DD - 1) / DD) ? (ng + PP - 1) / PP : (rider->nBlocks + DD - 1) / DD; \
-                const int hold = c->cus * duplex_wgs_per_cu(PP, DD); \
-                if (wgs > hold) wgs = hold; \
-                if (prio) hipLaunchKernelGGL((k_l1_duplex<PP, DD, 3>), dim3(wgs), dim3(64 * (PP + DD)), 0, s, a, *rider); \
-                else      hipLaunchKernelGGL((k_l1_duplex<PP, DD, 0>), dim3(wgs), dim3(64 * (PP + DD)), 0, s, a, *rider); \
-                launched = true; \
-            }
-            bool launched = false;
-            DUPLEX_CASE(1, 1) DUPLEX_CASE(1, 2) DUPLEX_CASE(3, 4) DUPLEX_CASE(9, 7)      // (9+5, 9+3, 3+2 measured as well: DESIGN 3.1b)
-#undef DUPLEX_CASE
-            if (!launched) return fail(c, PLZ4HIP_E_ARG, "PLZ4HIP_DUPLEX: not a built combination");
-        }
+            break;
+        default:
+            if (route == L1Route::Duplex && g0 == 0) { if (int rc = launch_duplex(c, s, sw, a, *rider, ng)) return rc; break; }
 #if defined(PLZ4_EXP_TABBITS)
-        else {   // EXPERIMENT: W waves per workgroup, as many workgroups as the device holds
+            {   // EXPERIMENT: W waves per workgroup, as many workgroups as the device holds
             int W = 10; if (const char* ev = getenv("PLZ4HIP_EXP_W")) W = atoi(ev);
 #define EXP_CASE(WW) if (W == WW) { int per = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_l1_parse<WW>, 64 * WW, 0); \
                 if (getenv("PLZ4HIP_VERBOSE")) fprintf(stderr, "exp: W=%d workgroups per CU %d\n", WW, per); \
@@ -2572,26 +2532,12 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
                 hipLaunchKernelGGL(k_l1_parse<WW>, dim3(wgs), dim3(64 * WW), 0, s, a); }
             EXP_CASE(4) EXP_CASE(5) EXP_CASE(6) EXP_CASE(8) EXP_CASE(9) EXP_CASE(10) EXP_CASE(12) EXP_CASE(13) EXP_CASE(14) EXP_CASE(16)
 #undef EXP_CASE
-        }
+            }
 #else
-        else ENC_LAUNCH(k_l1_parse, ng, c, s, a);
+            ENC_LAUNCH(k_l1_parse, ng, c, s, a);
 #endif
-        // emit: waves per block so that a small call still spreads over the chip
-        int wg = (16384 / ng) / 4;
-        if (wg > (maxChunks + 3) / 4) wg = (maxChunks + 3) / 4;
-        if (wg < 1) wg = 1;
-        if (hist) hipLaunchKernelGGL(k_fxl_sizes, dim3(wg, ng), dim3(256), 0, s, a, (const FxlBlk*)xb);
-        else if (mid) hipLaunchKernelGGL(k_l1_sizes<false>, dim3(wg, ng), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_l1_sizes<true>, dim3(wg, ng), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_l1_scan, dim3((ng + 3) / 4), dim3(256), 0, s, a);
-        const bool ctxSmall = hist && a.dictLen >= 8;                           // (the blocks <= 4 KiB under the context: k_fxl_small)
-        if (ctxSmall && a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);   // (their lengths, before the records are placed)
-        if (a.bodyOff) hipLaunchKernelGGL(k_scan_from, dim3(1), dim3(64), 0, s, (const int32_t*)(a.result + g0), a.bodyOff + g0, ng, g0 == 0 ? 1 : 0);
-        if (hist) hipLaunchKernelGGL(k_fxl_write, dim3(wg, ng), dim3(256), 0, s, a, (const FxlBlk*)xb);
-        else if (mid) hipLaunchKernelGGL(k_l1_write<false>, dim3(wg, ng), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_l1_write<true>, dim3(wg, ng), dim3(256), 0, s, a);
-        if (!rawMode && a.blockChecksum) hipLaunchKernelGGL(k_l1_finish, dim3((ng + 15) / 16), dim3(64), 0, s, a);
-        if (ctxSmall && !a.bodyOff) hipLaunchKernelGGL(k_fxl_small, dim3(ng < 1024 ? ng : 1024), dim3(64), 0, s, a);
+        }
+        launch_emit(s, a, ng, g0, L.maxChunks, hist ? Emit::Seg : mid ? Emit::Mid : Emit::Back, xb, shape.ctx);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, job.leave());
@@ -2599,25 +2545,6 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     return PLZ4HIP_OK;
 }
 
-// Enqueue the decode of nb blocks on s (a: everything but the queue filled in) -- raw blocks (LZ4_decompress_safe per block) or, with
-// `records`, frame records (FrameReader._read + BlkT.Decompress, blk/frame.go:54-127, blk.go:50-61).  maxIn / maxOut: upper bounds of
-// the blocks' compressed and decoded sizes known to the host (the lengths themselves may live on the device).
-// A call of few blocks is cut across the chip (lz4_dx_device.inl: 1 x 4 MiB in about a millisecond of kernels instead of the
-// 66 ms one wavefront needs; the records' block checksums are verified beside it on a stream of their own); blocks that path will
-// not answer for -- anything but a plainly valid compressed block -- and calls of many blocks, where one wave per block is the
-// better use of the chip, run the one-wave kernels.  PLZ4HIP_DX_MAX_BLOCKS (default 128; 0: off).
-// hist: the blocks have history outside the block -- kHistDict: independent blocks under a.dict; kHistLinked: the chains of a.window /
-// a.chainFirst.  Few blocks of that kind take the same path with one pointer space for the whole call (dxl_*, lz4_dx_device.inl;
-// PLZ4HIP_DX_LINKED=0: they do not); a chain is answered up to its first block that is not plainly good, and the one-wave walk goes
-// on from there inside k_dxl_finish.
-// A linked call that does not fit one pass of that path is cut into groups of consecutive blocks, each group the same stage train on
-// s: a block needs only the 64 KiB in front of it, which the finish stage of the group before has laid down in a.window; that, the
-// window's length and one word per chain -- the chain has had a bad block -- are what goes from group to group, in device memory.
-// hostFirst: the call's chainFirst on the host (nChains + 1 entries; null: one chain).
-// Groups are taken iff blocks x kDxlMsPerBlock <= longest chain x kWalkMsPerBlock: many short chains are better served by one wave
-// per chain.  PLZ4HIP_DXL_GROUP_BLOCKS: blocks per group (0: no groups, one wave per chain beyond PLZ4HIP_DX_MAX_BLOCKS; set, it
-// also cuts calls that would fit one pass).  The constants and the default: profiles/dxl_group_rate.json.
-enum { kHistNone = 0, kHistDict = 1, kHistLinked = 2 };
 // The tables both flavours of the few-block decoder start with, at `base`; then DxLayout's record arrays (hashed: and the checksum
 // verdicts), link arrays (hist) and the grouped call's word per chain (else null), and DxbLayout's stages for raw blocks above 4 MiB
 template <class Layout> void bind_dx_tables(CodecArgs& a, uint8_t* base, const Layout& L)
@@ -2645,178 +2572,186 @@ void bind_dxb(CodecArgs& a, uint8_t* base, const DxbLayout& L)
     a.dxbRuns = (DxRun*)(base + L.offRuns); a.dxbRunRoom = L.room;
     a.dxbInfo = (DxbInfo*)(base + L.offBi);
 }
-constexpr int    kDxlGroupBlocks = 128;                                     // the fastest of 16 / 32 / 64 / 128 on a 256-block chain
-constexpr double kDxlMsPerBlock = 0.33, kWalkMsPerBlock = 59.0;             // t_dx, t_wave: 4 MiB blocks; both scale with the block alike
-constexpr int    kDxlGroupChains = 1024;                                    // chains a group's pointer space has room for
+// DxBig: every block of the call through the dxb stages, the small ones beside the large
+void launch_dxb(plz4hip_ctx* c, hipStream_t s, CodecArgs& a, int nb, int64_t maxOut, const DxWant& w, const DxbLayout& L)
+{
+    bind_dxb(a, c->dx.d, L);
+    a.dxbG = w.bigG; a.dxbThr = w.thr; a.dxbRounds = w.rounds;
+    const int chunks = (int)((maxOut + 1023) / 1024);
+    hipLaunchKernelGGL(k_dx_tables, dim3(L.maxSeg, nb), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_dxb_compose, dim3(L.groups * 32, nb), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_dxb_hop, dim3(nb), dim3(64), 0, s, a, c->d_counters);
+    hipLaunchKernelGGL(k_dxb_units, dim3(L.groups, nb), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_dxb_fill, dim3(L.maxSeg, nb), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_dxb_runs, dim3(1024, nb), dim3(256), 0, s, a);
+    for (int r = 0; r < w.rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxb_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+    hipLaunchKernelGGL(k_dxb_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+}
+
+// Dx, and one group of DxGrouped: the stage train over a's nb blocks (the call, or the group's view of it), L: their layout.  hist:
+// the dxl flavour, one pointer space for the blocks; a chain is answered up to its first block that is not plainly good, and the
+// one-wave walk goes on from there inside k_dxl_finish.
+int launch_dx_train(plz4hip_ctx* c, hipStream_t s, CodecArgs& a, int nb, const DxLayout& L, int64_t maxOut, bool records, int hist)
+{
+    const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
+    const int maxSeg = L.maxSeg, chunks = (int)((outB + 1023) / 1024);
+    const int nChG = hist == kHistLinked ? a.nChains : 0;
+    const bool hashed = records && a.blockChecksum;
+    bind_dx(a, c->dx.d, L, records, hashed, hist != kHistNone);
+    if (records) {
+        hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, (int64_t*)a.dxSrcOff, (int32_t*)a.dxLen);     // (fills them)
+        if (hashed) {
+            // the block checksums beside the decode, on the ctx's own stream, idle otherwise: one stream more would push the staging
+            // slots' streams onto shared hardware queues -- the runtime has four -- and cost the large host calls their overlap:
+            // 412 -> 610 ms per 2304 blocks, measured
+            c->dxHashStream = c->stream;
+            if (!c->evDxFork) HIPCHK(c, hipEventCreateWithFlags(&c->evDxFork, hipEventDisableTiming));
+            if (!c->evDxHash) HIPCHK(c, hipEventCreateWithFlags(&c->evDxHash, hipEventDisableTiming));
+            HIPCHK(c, hipEventRecord(c->evDxFork, s));
+            HIPCHK(c, hipStreamWaitEvent(c->dxHashStream, c->evDxFork, 0));
+            hipLaunchKernelGGL(k_dx_rec_hash, dim3(nb), dim3(64), 0, c->dxHashStream, a);
+            HIPCHK(c, hipEventRecord(c->evDxHash, c->dxHashStream));
+        }
+    }
+    hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_dx_stitch, dim3(nb), dim3(64), 0, s, a);
+    if (!hist) {
+        hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+        for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+        if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
+        hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+    } else {
+        // the copy chain of a call (of a group) can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
+        int rounds = 1;
+        while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
+        a.dxlRounds = rounds;
+        hipLaunchKernelGGL(k_dxl_link, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
+        hipLaunchKernelGGL(k_dxl_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_dxl_resolve, dim3((int)(L.pStride / 1024), nb), dim3(256), 0, s, a);
+        for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxl_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+        hipLaunchKernelGGL(k_dxl_gather, dim3(chunks, nb), dim3(256), 0, s, a);
+        if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
+        if (hist == kHistLinked) hipLaunchKernelGGL(k_dxl_finish, dim3(nChG), dim3(64), 0, s, a, c->d_counters);
+        else                     hipLaunchKernelGGL(k_dxl_verdict, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
+}
+
+// Enqueue the decode of nb blocks on s (a: everything but the queue filled in) -- raw blocks (LZ4_decompress_safe per block) or, with
+// `records`, frame records (FrameReader._read + BlkT.Decompress, blk/frame.go:54-127, blk.go:50-61); the routes: route.h, DESIGN 2.
+// maxIn / maxOut: upper bounds of the blocks' compressed and decoded sizes known to the host (the lengths themselves may live on the
+// device).  hist -- kHistDict: independent blocks under a.dict; kHistLinked: the chains of a.window / a.chainFirst.  hostFirst: the
+// call's chainFirst on the host (nChains + 1 entries; null: one chain).  The stage trains answer plainly valid blocks (1 x 4 MiB in
+// about a millisecond of kernels instead of the 66 ms one wavefront needs); the one-wave kernels behind them answer the rest.  The
+// grouping constants and their default: profiles/dxl_group_rate.json.
 int launch_decode(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int64_t maxIn, int64_t maxOut, bool records, int hist = kHistNone,
                   const int32_t* hostFirst = nullptr)
 {
     hipError_t e;
     MarkOnExit job;
-    int dxMax = 128;
-    if (const char* v = getenv("PLZ4HIP_DX_MAX_BLOCKS")) dxMax = atoi(v);
-    const bool dxShape = maxIn >= 16384 && maxIn <= (int64_t)(6 << 20) && maxOut >= 1;
-    bool dx = nb <= dxMax && dxShape;
-    bool dxl = true;
-    if (hist) {
-        const char* v = getenv("PLZ4HIP_DX_LINKED");
-        if (v && atoi(v) == 0) dxl = false;
-        if (hist == kHistLinked && (!records || !a.window || a.nChains < 1)) dxl = false;
-        if (!dxl) dx = false;
-    }
+    const DxSwitches sw = read_dx_switches();
     const int nCh = hist == kHistLinked ? a.nChains : 0;
-    const int64_t outB = maxOut < kDxMaxOut ? maxOut : kDxMaxOut;
-    const size_t pStride = dx_ptr_stride(maxOut);
+    DxShape shape{nb, maxIn, maxOut, records, hist, a.window != nullptr, a.nChains, 0, hostFirst != nullptr || nCh == 1};
+    if (shape.hostFirst) for (int ch = 0; ch < nCh; ++ch) {
+        const int n = hostFirst ? hostFirst[ch + 1] - hostFirst[ch] : nb;
+        if (n > shape.longest) shape.longest = n;
+    }
+    const DxWant w = dx_want(shape, sw);
     // groups: [g0, g1) blocks and [ch0, ch1) chains each
     std::vector<DxlGroup> groups;
-    int gMax = nb;
-    if (hist == kHistLinked && dxl && dxShape && dxMax > 0 && (hostFirst || nCh == 1)) {
-        int G = kDxlGroupBlocks; bool forced = false;
-        if (const char* v = getenv("PLZ4HIP_DXL_GROUP_BLOCKS")) { G = atoi(v); forced = true; }
-        // the pointer space: blocks x stride + chains x 64 Ki stays below 2^31 (bit 31 tags a distance)
-        const int64_t room = ((int64_t)1 << 31) - (int64_t)kDxlGroupChains * kDxlHist - 1;
-        if (G > 0 && (int64_t)G * (int64_t)pStride > room) G = (int)(room / (int64_t)pStride);
-        if (G > 0 && (forced ? nb > G : !dx)) {
-            int longest = 0;
-            for (int ch = 0; ch < nCh; ++ch) {
-                const int n = hostFirst ? hostFirst[ch + 1] - hostFirst[ch] : nb;
-                if (n > longest) longest = n;
-            }
-            bool take = (double)nb * kDxlMsPerBlock <= (double)longest * kWalkMsPerBlock;
-            int cursor = 0;
-            for (int g0 = 0; take && g0 < nb; g0 += G) {
-                DxlGroup g;
-                dxl_group(hostFirst, nCh, nb, G, g0, &cursor, &g);
-                if (g.ch1 - g.ch0 > kDxlGroupChains) take = false;             // (chains without a block in between, by the thousand)
-                groups.push_back(g);
-            }
-            if (!take || groups.size() < 2) groups.clear();
-            else { dx = true; gMax = G; }
-        }
+    int cursor = 0;
+    for (int g0 = 0; w.G > 0 && g0 < nb; g0 += w.G) {
+        DxlGroup g;
+        dxl_group(hostFirst, nCh, nb, w.G, g0, &cursor, &g);
+        groups.push_back(g);
+        if (g.ch1 - g.ch0 > kDxlGroupChains) { groups.clear(); break; }            // (chains without a block in between, by the thousand)
     }
+    const bool grouped = !groups.empty();
     a.dxInfo = nullptr; a.dxSrcOff = nullptr; a.dxLen = nullptr; a.dxHashBad = nullptr; a.dxlGood = nullptr;
     a.dxlDead = nullptr; a.dxlBlk0 = 0; a.dxlGroup = 0; a.dxlGroups = 0;
-    // Raw blocks above 4 MiB + 8 (the raw block API only: a frame's block stops at 4 MiB): a call of few blocks whose largest
-    // capacity is above kDxMaxOut takes the same path with the stages that were one wave per block cut once more (dxb_*,
-    // lz4_dx_device.inl) -- every block of the call, the small ones beside the large.  PLZ4HIP_DX_BIG=0: no such call does (blocks up
-    // to kDxMaxOut of it keep the path above, the others one wave each); PLZ4HIP_DX_BIG_MAX_MIB (default 1024): the largest capacity
-    // bound, + 8, the path is taken for.  PLZ4HIP_DX_BIG_GROUP / PLZ4HIP_DX_BIG_RUN_KIB: segments per group of the stitch (default:
-    // about the square root of the segments) and the length from which a run goes to the grid-wide stage (default 64), for tests
-    // and A/B runs.  The workspace -- 8 B per input byte and 4 B per output byte of the call's strides, 8 B x 8192 per group, 16 B per
-    // segment and per listed run -- is the ctx's dx buffer: kept until plz4hip_ctx_trim.
-    if (!hist && !records && nb <= dxMax && maxOut > (int64_t)kDxMaxOut && maxIn >= 16384) {
-        int64_t bigMax = 1024; bool on = true;
-        if (const char* v = getenv("PLZ4HIP_DX_BIG")) on = atoi(v) != 0;
-        if (const char* v = getenv("PLZ4HIP_DX_BIG_MAX_MIB")) bigMax = atoll(v);
-        if (bigMax > 1024) bigMax = 1024;                                   // (positions are 31-bit)
-        const int64_t capMax = (bigMax << 20) + 8;
-        if (on && maxOut <= capMax && maxIn <= capMax + capMax / 255 + 64) {
-            const int maxSeg = dx_max_seg(maxIn);
-            int G = dxb_group_for(maxSeg), thr = kDxbThr;
-            if (const char* v = getenv("PLZ4HIP_DX_BIG_GROUP")) { const int g = atoi(v); if (g >= 2 && g <= kDxbMaxGroup) G = g; }
-            if (const char* v = getenv("PLZ4HIP_DX_BIG_RUN_KIB")) { const int k = atoi(v); if (k >= 1 && k <= (1 << 20)) thr = k << 10; }
-            const DxbLayout L = dxb_layout(nb, maxIn, maxOut, G, thr);
-            const int groups = L.groups, rounds = dxb_rounds(maxOut);
-            HIPCHK(c, c->dxOrder.wait(s));
-            bool refused = false;  HIPCHK(c, c->dx.reserve(L.total, c->dxOrder, &refused));
-            dx = false;                                                         // (no room: one wave per block)
-            if (!refused) {
-                job.arm(c->dxOrder, s);
-                bind_dxb(a, c->dx.d, L);
-                a.dxbG = G; a.dxbThr = thr; a.dxbRounds = rounds;
-                const int chunks = (int)((maxOut + 1023) / 1024);
-                hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                hipLaunchKernelGGL(k_dxb_compose, dim3(groups * 32, nb), dim3(256), 0, s, a);
-                hipLaunchKernelGGL(k_dxb_hop, dim3(nb), dim3(64), 0, s, a, c->d_counters);
-                hipLaunchKernelGGL(k_dxb_units, dim3(groups, nb), dim3(64), 0, s, a);
-                hipLaunchKernelGGL(k_dxb_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                hipLaunchKernelGGL(k_dxb_runs, dim3(1024, nb), dim3(256), 0, s, a);
-                for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxb_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-                hipLaunchKernelGGL(k_dxb_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
-                HIPCHK(c, hipGetLastError());
-            }
-        }
-    }
-    if (dx) {
-        // gMax: the blocks the workspace is laid out for (the call, or one group); a group's record and link arrays are packed by its own count
-        const auto layout_for = [&](int n) { return dx_layout(gMax, n, maxIn, maxOut, hist != kHistNone, records, groups.empty() ? 0 : nCh); };
-        const DxLayout whole = layout_for(gMax);
-        const int maxSeg = whole.maxSeg;
+    // The workspace of either flavour is the ctx's dx buffer, kept until plz4hip_ctx_trim -- DxBig: 8 B per input byte and 4 B per
+    // output byte of the call's strides, 8 B x 8192 per group, 16 B per segment and per listed run.  No room: one wave per block.
+    // gMax: the blocks a DxLayout is laid out for (the call, or one group); a group's record and link arrays are packed by its own count
+    const int gMax = grouped ? w.G : nb;
+    const auto layout_for = [&](int n) { return dx_layout(gMax, n, maxIn, maxOut, hist != kHistNone, records, grouped ? nCh : 0); };
+    DxbLayout big{};  DxLayout whole{};
+    bool granted = false;
+    if (w.big || w.dx || grouped) {
+        if (w.big) big = dxb_layout(nb, maxIn, maxOut, w.bigG, w.thr); else whole = layout_for(gMax);
         HIPCHK(c, c->dxOrder.wait(s));
-        bool refused = false;  HIPCHK(c, c->dx.reserve(whole.total, c->dxOrder, &refused));
-        if (refused) dx = false;                                                // no room: one wave per block
-        if (dx) {
-            job.arm(c->dxOrder, s);
-            const CodecArgs call = a;
-            int32_t* const dead = dx_dead(c->dx.d, whole, !groups.empty());
-            if (dead) HIPCHK(c, hipMemsetAsync(dead, 0, (size_t)nCh * 4, s));
-            const int nGroups = groups.empty() ? 1 : (int)groups.size();
-            for (int gi = 0; gi < nGroups; ++gi) {
-                if (!groups.empty()) {
-                    // the group's view of the call
-                    const DxlGroup& g = groups[gi];
-                    a = call; nb = g.g1 - g.g0;
-                    if (a.recOff) a.recOff += g.g0; else { a.src += (int64_t)g.g0 * a.srcStride; a.srcLen += g.g0; }
-                    a.dst += (int64_t)g.g0 * a.dstStride; a.result += g.g0; a.status += g.g0; a.nBlocks = nb;
-                    a.window += (size_t)g.ch0 * 131072; a.windowLen += g.ch0; a.nChains = g.ch1 - g.ch0;
-                    if (a.chainFirst) a.chainFirst += g.ch0;
-                    a.dxlDead = dead + g.ch0; a.dxlBlk0 = g.g0; a.dxlGroup = gi; a.dxlGroups = nGroups;
-                }
-                const int nChG = hist == kHistLinked ? a.nChains : 0;
-                const bool hashed = records && a.blockChecksum;
-                bind_dx(a, c->dx.d, layout_for(nb), records, hashed, hist != kHistNone);
-                if (records) {
-                    hipLaunchKernelGGL(k_dx_rec_prep, dim3((nb + 255) / 256), dim3(256), 0, s, a, (int64_t*)a.dxSrcOff, (int32_t*)a.dxLen);     // (fills them)
-                    if (hashed) {
-                        // (the ctx's own stream, idle otherwise: one stream more would push the staging slots' streams onto shared
-                        // hardware queues -- the runtime has four -- and cost the large host calls their overlap: 412 -> 610 ms per
-                        // 2304 blocks, measured)
-                        c->dxHashStream = c->stream;
-                        if (!c->evDxFork) HIPCHK(c, hipEventCreateWithFlags(&c->evDxFork, hipEventDisableTiming));
-                        if (!c->evDxHash) HIPCHK(c, hipEventCreateWithFlags(&c->evDxHash, hipEventDisableTiming));
-                        HIPCHK(c, hipEventRecord(c->evDxFork, s));
-                        HIPCHK(c, hipStreamWaitEvent(c->dxHashStream, c->evDxFork, 0));
-                        hipLaunchKernelGGL(k_dx_rec_hash, dim3(nb), dim3(64), 0, c->dxHashStream, a);
-                        HIPCHK(c, hipEventRecord(c->evDxHash, c->dxHashStream));
-                    }
-                }
-                const int chunks = (int)((outB + 1023) / 1024);
-                hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                hipLaunchKernelGGL(k_dx_stitch, dim3(nb), dim3(64), 0, s, a);
-                if (!hist) {
-                    hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                    for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-                    if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-                    hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
-                } else {
-                    // the copy chain of a call (of a group) can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
-                    int rounds = 1;
-                    while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
-                    a.dxlRounds = rounds;
-                    hipLaunchKernelGGL(k_dxl_link, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
-                    hipLaunchKernelGGL(k_dxl_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-                    hipLaunchKernelGGL(k_dxl_resolve, dim3((int)(pStride / 1024), nb), dim3(256), 0, s, a);
-                    for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxl_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-                    hipLaunchKernelGGL(k_dxl_gather, dim3(chunks, nb), dim3(256), 0, s, a);
-                    if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-                    if (hist == kHistLinked) hipLaunchKernelGGL(k_dxl_finish, dim3(nChG), dim3(64), 0, s, a, c->d_counters);
-                    else                     hipLaunchKernelGGL(k_dxl_verdict, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
-                }
-                HIPCHK(c, hipGetLastError());
-            }
-            if (!groups.empty()) { a = call; nb = call.nBlocks; }
+        bool refused = false;  HIPCHK(c, c->dx.reserve(w.big ? big.total : whole.total, c->dxOrder, &refused));
+        granted = !refused;
+        if (granted) job.arm(c->dxOrder, s);
+    }
+    const DxPlan p = dx_route(shape, w, grouped, granted);
+    if (p.route == DxRoute::DxBig) { launch_dxb(c, s, a, nb, maxOut, w, big); HIPCHK(c, hipGetLastError()); }
+    else if (p.route == DxRoute::Dx) { if (int rc = launch_dx_train(c, s, a, nb, whole, maxOut, records, hist)) return rc; }
+    else if (p.route == DxRoute::DxGrouped) {
+        // Each group is the same stage train on s: a block needs only the 64 KiB in front of it, which the finish stage of the group
+        // before has laid down in a.window; that, the window's length and one word per chain -- the chain has had a bad block -- are
+        // what goes from group to group, in device memory.
+        int32_t* const dead = dx_dead(c->dx.d, whole, true);
+        HIPCHK(c, hipMemsetAsync(dead, 0, (size_t)nCh * 4, s));
+        const int nGroups = (int)groups.size();
+        for (int gi = 0; gi < nGroups; ++gi) {
+            const DxlGroup& g = groups[gi];
+            CodecArgs x = a;                                                        // the group's view of the call
+            const int ng = g.g1 - g.g0;
+            if (x.recOff) x.recOff += g.g0; else { x.src += (int64_t)g.g0 * x.srcStride; x.srcLen += g.g0; }
+            x.dst += (int64_t)g.g0 * x.dstStride; x.result += g.g0; x.status += g.g0; x.nBlocks = ng;
+            x.window += (size_t)g.ch0 * 131072; x.windowLen += g.ch0; x.nChains = g.ch1 - g.ch0;
+            if (x.chainFirst) x.chainFirst += g.ch0;
+            x.dxlDead = dead + g.ch0; x.dxlBlk0 = g.g0; x.dxlGroup = gi; x.dxlGroups = nGroups;
+            if (int rc = launch_dx_train(c, s, x, ng, layout_for(ng), maxOut, records, hist)) return rc;
         }
     }
+    // the tail: the one-wave kernels answer every block the stages above have not
     a.queue = next_queue(c, s, &e); HIPCHK(c, e);
-    if (hist == kHistLinked) { if (!dx) hipLaunchKernelGGL(k_decode_rec_linked, dim3(grid_for(a.nChains, c->decWaves)), dim3(64), 0, s, a); }
-    else if (hist && records) hipLaunchKernelGGL(k_decode_rec_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
-    else if (hist)            hipLaunchKernelGGL(k_decode_raw_dict, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
-    else if (records && dx) hipLaunchKernelGGL(k_decode_rec_dx, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
-    else if (records)  { launch_rec_verify(s, a); hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a); }
-    else               hipLaunchKernelGGL(k_decode_raw, dim3(grid_for(nb, c->decWaves)), dim3(64), 0, s, a);
+    const dim3 grid(grid_for(p.tail == DxTail::RecLinked ? a.nChains : nb, c->decWaves));
+    switch (p.tail) {
+    case DxTail::RecLinked: hipLaunchKernelGGL(k_decode_rec_linked, grid, dim3(64), 0, s, a); break;
+    case DxTail::RecDict:   hipLaunchKernelGGL(k_decode_rec_dict, grid, dim3(64), 0, s, a); break;
+    case DxTail::RawDict:   hipLaunchKernelGGL(k_decode_raw_dict, grid, dim3(64), 0, s, a); break;
+    case DxTail::RecDx:     hipLaunchKernelGGL(k_decode_rec_dx, grid, dim3(64), 0, s, a); break;
+    case DxTail::Rec:       launch_rec_verify(s, a); hipLaunchKernelGGL(k_decode_rec, grid, dim3(64), 0, s, a); break;
+    case DxTail::Raw:       hipLaunchKernelGGL(k_decode_raw, grid, dim3(64), 0, s, a); break;
+    case DxTail::None:      break;
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, job.leave());
     return PLZ4HIP_OK;
+}
+
+// What the entry points hand to the launchers.  The record decode of nBlocks records of a frame body ...
+CodecArgs rec_decode_args(const void* body, const int64_t* recOff, int nBlocks, int bsz, int blockChecksum, void* dst, int64_t dstStride,
+                          int dstCap, int32_t* result, int32_t* status)
+{
+    CodecArgs a{};
+    a.src = (const uint8_t*)body; a.recOff = recOff; a.bsz = bsz;
+    a.dst = (uint8_t*)dst; a.dstStride = dstStride; a.dstCapAll = dstCap;
+    a.result = result; a.status = status; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
+    a.dictLen = -1; a.prevTailLen = -1;
+    return a;
+}
+// ... the record encode of srcBytes of plaintext in blocks of bsz, srcStride apart, into a staging area or straight into a frame body
+CodecArgs rec_encode_args(const void* src, int64_t srcBytes, int64_t srcStride, int bsz, int blockChecksum, int32_t* recLen, int nBlocks)
+{
+    CodecArgs a{};
+    a.src = (const uint8_t*)src; a.srcStride = srcStride; a.srcBytes = srcBytes; a.bsz = bsz;
+    a.result = recLen; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
+    a.dictLen = -1; a.prevTailLen = -1;
+    return a;
+}
+void into_stage(CodecArgs& a, void* stage, int64_t stride) { a.dst = (uint8_t*)stage; a.dstStride = stride; a.bodyOff = nullptr; a.bodyCap = 0; }
+void into_body(CodecArgs& a, void* body, int64_t bodyCap, int64_t* recOff) { a.dst = (uint8_t*)body; a.dstStride = 0; a.bodyOff = recOff; a.bodyCap = bodyCap; }
+// ... and a dictionary's level-1 table and, for the HC levels, its context's tables and k_hcx's lists
+void dict_args(CodecArgs& a, const plz4hip_dict* dict) { a.dict = dict->d_bytes; a.dictLen = dict->len; a.dictTable = dict->d_table; }
+void dict_hc_args(CodecArgs& a, const plz4hip_dict* dict, int level)
+{
+    const uint8_t* t = dict->d_hc + (level <= 2 ? 0 : (size_t)kHcWorkBytes);
+    a.hcDictHash = (const uint32_t*)t; a.hcDictChain = (const uint16_t*)(t + kHcHashEntries * 4);
+    a.hcxStart = (const uint32_t*)dict->d_hcx; a.hcxList = (const uint16_t*)(dict->d_hcx + kHcxDictStartBytes);
 }
 
 }  // namespace
@@ -3030,11 +2965,8 @@ int plz4hip_dev_encode_records(plz4hip_ctx* c, const void* src, int64_t srcBytes
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    CodecArgs a{};
-    a.src = (const uint8_t*)src; a.srcStride = bsz; a.srcBytes = srcBytes; a.bsz = bsz;
-    a.dst = (uint8_t*)stage; a.dstStride = plz4hip_dev_stage_stride(bsz);
-    a.result = recLen; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
-    a.dictLen = -1; a.prevTailLen = -1;
+    CodecArgs a = rec_encode_args(src, srcBytes, bsz, bsz, blockChecksum, recLen, nBlocks);
+    into_stage(a, stage, plz4hip_dev_stage_stride(bsz));
     if (is_hc_level(level)) {
         a.level = level;
         return launch_hc(c, s, a, nBlocks, bsz, 0);
@@ -3086,11 +3018,7 @@ int plz4hip_dev_decode_records(plz4hip_ctx* c, const void* body, const int64_t* 
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    CodecArgs a{};
-    a.src = (const uint8_t*)body; a.recOff = recOff; a.bsz = bsz;
-    a.dst = (uint8_t*)dst; a.dstStride = dstStride; a.dstCapAll = dstCap;
-    a.result = result; a.status = status; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
-    a.dictLen = -1; a.prevTailLen = -1;
+    CodecArgs a = rec_decode_args(body, recOff, nBlocks, bsz, blockChecksum, dst, dstStride, dstCap, result, status);
     return launch_decode(c, s, a, nBlocks, bsz, dstCap, true);
 }
 
@@ -3121,13 +3049,9 @@ int plz4hip_dev_decode_records_ex(plz4hip_ctx* c, const void* body, const int64_
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    CodecArgs a{};
-    a.src = (const uint8_t*)body; a.recOff = recOff; a.bsz = bsz;
-    a.dst = (uint8_t*)dst; a.dstStride = dstStride; a.dstCapAll = dstCap;
-    a.result = result; a.status = status; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
-    a.dictLen = -1; a.prevTailLen = -1;
+    CodecArgs a = rec_decode_args(body, recOff, nBlocks, bsz, blockChecksum, dst, dstStride, dstCap, result, status);
     if (!linked) {
-        a.dict = dict->d_bytes; a.dictLen = dict->len; a.dictTable = dict->d_table;
+        dict_args(a, dict);
         return launch_decode(c, s, a, nBlocks, bsz, dstCap, true, kHistDict);
     }
     a.linked = 1; a.window = (uint8_t*)windows; a.windowLen = windowLen; a.nChains = nChains;
@@ -3166,11 +3090,7 @@ int plz4hip_dev_duplex_records(plz4hip_ctx* c, const void* src, int64_t srcBytes
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    CodecArgs d{};
-    d.src = (const uint8_t*)body; d.recOff = recOff; d.bsz = decBsz;
-    d.dst = (uint8_t*)dst; d.dstStride = dstStride; d.dstCapAll = dstCap;
-    d.result = result; d.status = status; d.nBlocks = nDecBlocks; d.blockChecksum = decBlockChecksum;
-    d.dictLen = -1; d.prevTailLen = -1;
+    CodecArgs d = rec_decode_args(body, recOff, nDecBlocks, decBsz, decBlockChecksum, dst, dstStride, dstCap, result, status);
     if (nDecBlocks > 0) { hipError_t e; d.queue = next_queue(c, s, &e); HIPCHK(c, e); }
     if (nBlocks == 0) {
         launch_rec_verify(s, d);
@@ -3178,11 +3098,8 @@ int plz4hip_dev_duplex_records(plz4hip_ctx* c, const void* src, int64_t srcBytes
         HIPCHK(c, hipGetLastError());
         return PLZ4HIP_OK;
     }
-    CodecArgs a{};
-    a.src = (const uint8_t*)src; a.srcStride = bsz; a.srcBytes = srcBytes; a.bsz = bsz;
-    a.dst = (uint8_t*)stage; a.dstStride = plz4hip_dev_stage_stride(bsz);
-    a.result = recLen; a.nBlocks = nBlocks; a.blockChecksum = blockChecksum;
-    a.dictLen = -1; a.prevTailLen = -1;
+    CodecArgs a = rec_encode_args(src, srcBytes, bsz, bsz, blockChecksum, recLen, nBlocks);
+    into_stage(a, stage, plz4hip_dev_stage_stride(bsz));
     return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nDecBlocks > 0 ? &d : nullptr);
 }
 
@@ -3197,10 +3114,8 @@ static int encode_body_args(plz4hip_ctx* c, CodecArgs& a, const void* src, int64
     const int64_t nb64 = (srcBytes + bsz - 1) / bsz;
     if (nb64 > 0x7FFFFFFF) return fail(c, PLZ4HIP_E_ARG, "too many blocks");
     *nBlocksOut = (int)nb64;
-    a.src = (const uint8_t*)src; a.srcStride = bsz; a.srcBytes = srcBytes; a.bsz = bsz;
-    a.dst = (uint8_t*)body; a.dstStride = 0; a.bodyOff = recOff; a.bodyCap = bodyCap;
-    a.result = recLen; a.nBlocks = *nBlocksOut; a.blockChecksum = blockChecksum;
-    a.dictLen = -1; a.prevTailLen = -1;
+    a = rec_encode_args(src, srcBytes, bsz, bsz, blockChecksum, recLen, *nBlocksOut);
+    into_body(a, body, bodyCap, recOff);
     return PLZ4HIP_OK;
 }
 int plz4hip_dev_encode_body(plz4hip_ctx* c, const void* src, int64_t srcBytes, int bsz, int level, int blockChecksum,
@@ -3229,11 +3144,7 @@ int plz4hip_dev_duplex_body(plz4hip_ctx* c, const void* src, int64_t srcBytes, i
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    CodecArgs d{};
-    d.src = (const uint8_t*)decBody; d.recOff = decRecOff; d.bsz = decBsz;
-    d.dst = (uint8_t*)dst; d.dstStride = dstStride; d.dstCapAll = dstCap;
-    d.result = result; d.status = status; d.nBlocks = nDecBlocks; d.blockChecksum = decBlockChecksum;
-    d.dictLen = -1; d.prevTailLen = -1;
+    CodecArgs d = rec_decode_args(decBody, decRecOff, nDecBlocks, decBsz, decBlockChecksum, dst, dstStride, dstCap, result, status);
     if (nDecBlocks > 0) { hipError_t e; d.queue = next_queue(c, s, &e); HIPCHK(c, e); }
     if (nBlocks == 0) {
         HIPCHK(c, hipMemsetAsync(recOff, 0, sizeof(int64_t), s));
@@ -3268,19 +3179,13 @@ static int encode_ex_args(plz4hip_ctx* c, CodecArgs& a, const void* src, int64_t
     const int64_t nb64 = (srcBytes + bsz - 1) / bsz;
     if (nb64 > 0x7FFFFFFF) return fail(c, PLZ4HIP_E_ARG, "too many blocks");
     *nBlocksOut = (int)nb64;
-    a.src = (const uint8_t*)src; a.srcStride = srcStride; a.srcBytes = srcBytes; a.bsz = bsz;
-    a.result = recLen; a.nBlocks = *nBlocksOut; a.blockChecksum = blockChecksum;
-    a.dictLen = -1; a.prevTailLen = -1;
+    a = rec_encode_args(src, srcBytes, srcStride, bsz, blockChecksum, recLen, *nBlocksOut);
     a.linked = linked ? 1 : 0;
-    if (dict) { a.dict = dict->d_bytes; a.dictLen = dict->len; a.dictTable = dict->d_table; }
+    if (dict) dict_args(a, dict);
     if (linked && prevTailLen >= 0) { a.prevTail = (const uint8_t*)prevTail; a.prevTailLen = prevTailLen; }
     if (is_hc_level(level)) {
         a.level = level; a.hcEx = 1;
-        if (dict) {
-            const uint8_t* t = dict->d_hc + (level <= 2 ? 0 : (size_t)kHcWorkBytes);
-            a.hcDictHash = (const uint32_t*)t; a.hcDictChain = (const uint16_t*)(t + kHcHashEntries * 4);
-            a.hcxStart = (const uint32_t*)dict->d_hcx; a.hcxList = (const uint16_t*)(dict->d_hcx + kHcxDictStartBytes);
-        }
+        if (dict) dict_hc_args(a, dict, level);
     }
     return PLZ4HIP_OK;
 }
@@ -3298,7 +3203,7 @@ int plz4hip_dev_encode_records_ex(plz4hip_ctx* c, const void* src, int64_t srcBy
     std::lock_guard<std::mutex> g(c->mu);
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    a.dst = (uint8_t*)stage; a.dstStride = plz4hip_dev_stage_stride(bsz);
+    into_stage(a, stage, plz4hip_dev_stage_stride(bsz));
     if (is_hc_level(level)) return launch_hc(c, s, a, nBlocks, bsz, 0);
     return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true);
 }
@@ -3316,7 +3221,7 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes
     ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     if (nBlocks == 0) { HIPCHK(c, hipMemsetAsync(recOff, 0, sizeof(int64_t), s)); return PLZ4HIP_OK; }
-    a.dst = (uint8_t*)body; a.dstStride = 0; a.bodyOff = recOff; a.bodyCap = bodyCap;
+    into_body(a, body, bodyCap, recOff);
     if (level == 2) {
         // (a block <= 4 KiB under a dictionary context is written by the one-thread parser behind the emit stage, into a staged record)
         const int lastLen = (int)(srcBytes - (int64_t)(nBlocks - 1) * bsz);
@@ -3325,15 +3230,17 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes
         if (ctxSmall) return fail(c, PLZ4HIP_E_UNSUPPORTED, "plz4hip_dev_encode_body_ex: level 2 with a block <= 4 KiB under a dictionary context (plz4hip_dev_encode_records_ex + plz4hip_dev_compact_records)");
         return launch_hc(c, s, a, nBlocks, bsz, 0);
     }
-    if (!fxl_wanted(nBlocks, bsz) && !l1x_on()) {
+    const L1Shape shape{nBlocks, bsz, false, false, false, true, true, true, a.dictLen >= 8};
+    const L1Switches sw = read_l1_switches();                                   // (once per call: launch_l1 is handed these)
+    if (!l1_want(shape, sw).staged) {
         // the one-kernel encoder writes staged records: a staging area of the ctx's, then the compaction of plz4hip_dev_compact_records
         const int64_t stride = plz4hip_dev_stage_stride(bsz);
         HIPCHK(c, c->xstageOrder.wait(s));
         bool refused = false;  HIPCHK(c, c->xstage.reserve((size_t)nBlocks * (size_t)stride, c->xstageOrder, &refused));
         if (refused) return fail(c, PLZ4HIP_E_NOMEM, "plz4hip_dev_encode_body_ex: the one-kernel encoder's staging area");
         MarkOnExit job;  job.arm(c->xstageOrder, s);
-        a.dst = c->xstage.d; a.dstStride = stride; a.bodyOff = nullptr; a.bodyCap = 0;
-        if (int rc = launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true)) return rc;
+        into_stage(a, c->xstage.d, stride);
+        if (int rc = launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true, &sw)) return rc;
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(64), 0, s, (const int32_t*)recLen, recOff, nBlocks);
         hipLaunchKernelGGL(k_move_records, dim3(nBlocks, move_slices((int)stride)), dim3(256), 0, s,
                            (const uint8_t*)c->xstage.d, (const int64_t*)nullptr, stride, (const int32_t*)recLen, (const int64_t*)recOff, (uint8_t*)body, bodyCap);
@@ -3341,7 +3248,7 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes
         HIPCHK(c, job.leave());
         return PLZ4HIP_OK;
     }
-    return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true);
+    return launch_l1(c, s, a, nBlocks, bsz, 0, nullptr, nullptr, nullptr, true, true, &sw);
 }
 
 // ---------------------------------------------------------------------------------------- host-buffer API
@@ -3430,15 +3337,8 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
         a.dictLen = -1; a.prevTailLen = -1;
         if (hcMode) a.level = dj->level;
         if (dictMode) {
-            if (dj->dict) { a.dict = dj->dict->d_bytes; a.dictLen = dj->dict->len; a.dictTable = dj->dict->d_table; }
-            if (hcMode) {
-                a.hcEx = 1;
-                if (dj->dict) {
-                    const uint8_t* t = dj->dict->d_hc + (dj->level <= 2 ? 0 : (size_t)kHcWorkBytes);
-                    a.hcDictHash = (const uint32_t*)t; a.hcDictChain = (const uint16_t*)(t + kHcHashEntries * 4);
-                    a.hcxStart = (const uint32_t*)dj->dict->d_hcx; a.hcxList = (const uint16_t*)(dj->dict->d_hcx + kHcxDictStartBytes);
-                }
-            }
+            if (dj->dict) dict_args(a, dj->dict);
+            if (hcMode) { a.hcEx = 1; if (dj->dict) dict_hc_args(a, dj->dict, dj->level); }
             a.linked = dj->linked;
             const void* pt = dj->prevTail; int ptLen = (dj->prevTail && dj->prevTailLen >= 0) ? dj->prevTailLen : -1;
             if (dj->linked && b0 > 0) {                                   // a later chunk of a linked encode
@@ -3461,16 +3361,12 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
         }
         switch (mode) {
         case 0: if (hcMode) { if (int rc = launch_hc(c, s, a, nb, maxIn, 1)) return rc; }
-                else if (dictMode && fxl_wanted(nb, maxIn)) { if (int rc = launch_l1(c, s, a, nb, maxIn, 1, &sl.l1, nullptr, nullptr, true)) return rc; }
-                else if (dictMode) ENC_LAUNCH(k_encode_raw_dict, nb, c, s, a);
-                else { if (int rc = launch_l1(c, s, a, nb, maxIn, 1, &sl.l1)) return rc; } break;
+                else { if (int rc = launch_l1(c, s, a, nb, maxIn, 1, &sl.l1, nullptr, nullptr, dictMode)) return rc; } break;
         case 1: if (int rc = launch_decode(c, s, a, nb, maxIn, maxOut, false, dictMode ? kHistDict : kHistNone)) return rc;
                 break;
         case 2: a.dstCap = nullptr;
                 if (hcMode) { if (int rc = launch_hc(c, s, a, nb, maxIn, 0)) return rc; }
-                else if (dictMode && fxl_wanted(nb, maxIn)) { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1, nullptr, nullptr, true)) return rc; }
-                else if (dictMode) ENC_LAUNCH(k_encode_rec_dict, nb, c, s, a);
-                else { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1)) return rc; } break;
+                else { if (int rc = launch_l1(c, s, a, nb, maxIn, 0, &sl.l1, nullptr, nullptr, dictMode)) return rc; } break;
         case 3: a.dstCap = nullptr;
                 if (int rc = launch_decode(c, s, a, nb, bsz, bsz + 8, true, !dictMode ? kHistNone : (dj->linked ? kHistLinked : kHistDict),
                                            dictMode ? dj->chainFirst : nullptr)) return rc;    // (a linked decode is one chunk: the call's chains)
