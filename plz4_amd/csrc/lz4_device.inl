@@ -1350,23 +1350,25 @@ DEV int64_t read_more_len(const uint8_t* src, int* ip, int ilimit, bool initialC
 // others ("near": the source holds bytes of this very batch) follow in rounds of mutually independent copies, long and
 // overlapping ones as one cooperative copy each.  Everything else -- long literal runs, very long matches, bad offsets,
 // the ends of the block -- is left to the exact sequential step of
-// wave_decode_block, which also owns liblz4's accept/reject rules.  Returns the number of sequences decoded.
+// wave_decode_block, which also owns liblz4's accept/reject rules.
 // Caller guarantees ip0 + 160 <= iend and op0 + 1088 <= oend (the reference is in its fast loop there).
-// kLds: the batch's output is assembled in `lb`, kDecLdsBytes of LDS owned by this wave (the last kDecTail bytes already
-// written, then up to 1024 new ones), and stored to memory in one coalesced sweep.  Near matches then read LDS instead of
-// waiting a memory round trip per dependency round; `tailAt` is the output position the LDS tail is valid for.
+// Two routines over one window parse: wave_decode_plain_batch copies through memory; wave_decode_lds_batch assembles the batch's
+// output in `lb`, kDecLdsBytes of LDS owned by this wave (the last kDecTail bytes already written, then up to 1024 new ones),
+// and stores it to memory in one coalesced sweep -- near matches then read LDS instead of waiting a memory round trip per
+// dependency round.
 enum : int { kDecTail = 32, kDecDump = kDecTail + 1024 + 64, kDecLdsBytes = kDecDump + 16 };    // (kDecDump: 16 bytes nobody reads)
-template <bool kLds>
-DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int* ipp, int64_t* opp,
-                                LVREF(v16u_t, win), int* winIp, uint8_t* lb = nullptr, int64_t* tailAt = nullptr,
-                                unsigned long long* st_ = nullptr)           // (diagnostics build: the caller's counters)
+#if defined(PLZ4_EMU)
+unsigned long long plz4_emu_dec[8];               // test diagnostics of the LDS-staged batch: [0] batches, [1] walks of kDecHops plain tokens, [2] near rounds, [3] cooperative copies,
+                                                  // [4] of those, the ones read from memory, [5] batches without members, [6] primes of the window and
+                                                  // the staged tail, [7] members
+#define EMU_DEC(i, v) (plz4_emu_dec[(i)] += (unsigned long long)(v))
+#else
+#define EMU_DEC(i, v) do {} while (0)
+#endif
+// The 64 hypothetical sequences of a window, one per lane, parsed from the lane's 16 bytes; returns the mask of the plain ones.
+DEV uint64_t wave_decode_parse_window(LVREF(v16u_t, win), LVREF(uint32_t, b0), LVREF(int, ll), LVREF(int, ml), LVREF(int, off),
+                                      LVREF(int, nxt), LVREF(int, outLen), LVREF(int, plain), LVREF(int, coop))
 {
-    const int ip0 = *ipp; const int64_t op0 = *opp;
-    (void)st_;
-    const unsigned long long td0 = STAT_NOW(); (void)td0;
-    // every lane holds the 16 input bytes from its window position on; normally requested by the previous batch
-    if (*winIp != ip0) { LANES({ win[I_] = *(const v16u_t*)(src + ip0 + LANE); }) }
-    LV(uint32_t, b0); LV(int, ll); LV(int, ml); LV(int, off); LV(int, nxt); LV(int, outLen); LV(int, plain); LV(int, coop);
     LV(int, longLit);
     LANES({
         const uint64_t w0 = (uint64_t)win[I_].w[0] | ((uint64_t)win[I_].w[1] << 32);
@@ -1424,9 +1426,17 @@ DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __rest
             }
         })
     }
-    const uint64_t plainMask = BALLOT(plain[I_]);
-    const unsigned long long td1 = STAT_NOW(); (void)td1;
-    STAT(0, td1 - td0);
+    return BALLOT(plain[I_]);
+}
+// The batch assembled in memory (the raw, dictionary, linked and few-block kernels).  Returns the number of sequences decoded.
+DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int* ipp, int64_t* opp,
+                                LVREF(v16u_t, win), int* winIp)
+{
+    const int ip0 = *ipp; const int64_t op0 = *opp;
+    // every lane holds the 16 input bytes from its window position on; normally requested by the previous batch
+    if (*winIp != ip0) { LANES({ win[I_] = *(const v16u_t*)(src + ip0 + LANE); }) }
+    LV(uint32_t, b0); LV(int, ll); LV(int, ml); LV(int, off); LV(int, nxt); LV(int, outLen); LV(int, plain); LV(int, coop);
+    const uint64_t plainMask = wave_decode_parse_window(win, b0, ll, ml, off, nxt, outLen, plain, coop);
     if (!(plainMask & 1)) return 0;
     // Follow the token chain through the whole window, four hops to a branch (mark the lane, fetch its successor; a
     // finished walk only re-marks lane 0, where it started), then cut the chain at the first sequence that is not plain.
@@ -1460,13 +1470,9 @@ DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __rest
         })
         // a source before the start of the output is the sequential step's business (error, or a dictionary);
         // and the batch's output stays inside the room the caller checked
-        // (LDS staging: a long match whose source starts before the staged tail and runs into this batch's output as well)
-        const uint64_t stop = BALLOT(LANE_IN(mL) && (sp[I_] < 0 || acc[I_] > 1024 ||
-                                     (kLds && coop[I_] && sp[I_] < op0 - kDecTail && (int64_t)sp[I_] + ml[I_] > op0)));
+        const uint64_t stop = BALLOT(LANE_IN(mL) && (sp[I_] < 0 || acc[I_] > 1024));
         if (stop) members &= (1ull << ctz64(stop)) - 1;
     }
-    const unsigned long long td2 = STAT_NOW(); (void)td2;
-    STAT(1, td2 - td1);
     if (!members) return 0;
     const uint64_t mL = members;
     const int last = 63 - __builtin_clzll(members);
@@ -1478,101 +1484,6 @@ DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __rest
     // A "near" source may contain bytes this batch produces; those go in dependency order below.
     const uint64_t coopM = mL & BALLOT(coop[I_]);
     const uint64_t far = mL & ~coopM & BALLOT((int64_t)sp[I_] + ml[I_] <= op0);
-    if (kLds) {
-        const int total = RL(acc, last);                       // bytes this batch produces
-        // A match of 4..18 bytes travels as four overlapping pieces: [0,4) and [len-4,len) always, [len-8,len-4) from 8 bytes on,
-        // [4,12) from 12 on -- together they cover every length, and where two overlap they carry the same bytes.  Every piece
-        // has a fixed place per lane and batch, so a round is four loads and four stores; a lane that is not part of the round
-        // (or a piece its length does not have) stores to the dump bytes behind the buffer: a divergent `if` costs this machine
-        // ~45 cycles whether any lane takes it or not, a redirected store costs a select.
-        LV(int, mdst); LV(int, qoff);
-        LANES({
-            mdst[I_] = kDecTail + (outStart[I_] - (int)op0) + (ll[I_] & 0xFFFF);       // where the match goes, as an offset into lb
-            qoff[I_] = mdst[I_] - off[I_];                                             // ... and where it comes from
-        })
-        LV(uint32_t, g0); LV(uint32_t, g1); LV(uint32_t, g2); LV(uint64_t, g3);
-        auto put_pieces = [&](const uint64_t who) {
-            LANES({
-                const bool on = LANE_IN(who);
-                const int len = on ? ml[I_] : 0, at = on ? mdst[I_] : (int)kDecDump;
-                st32u(lb + at, g0[I_]);
-                st32u(lb + at + max_(len - 4, 0), g1[I_]);
-                st32u(lb + (len >= 8 ? at + len - 8 : (int)kDecDump), g2[I_]);
-                st64u(lb + (len >= 12 ? at + 4 : (int)kDecDump + 8), g3[I_]);
-            })
-        };
-        // far matches: their bytes are requested from memory first ...
-        LANES({
-            g0[I_] = 0; g1[I_] = 0; g2[I_] = 0; g3[I_] = 0;
-            if (LANE_IN(far)) {
-                const uint8_t* q = dst + sp[I_]; const int len = ml[I_];
-                g0[I_] = ld32u(q); g1[I_] = ld32u(q + len - 4); g2[I_] = ld32u(q + max_(len - 8, 0)); g3[I_] = ld64u(q + 4);
-            }
-        })
-        // ... the tail of what is already written, if LDS does not hold it (after a sequential step)
-        if (*tailAt != op0) {
-            LANES({ if (LANE < kDecTail) { const int64_t g = op0 - kDecTail + LANE; lb[LANE] = g >= 0 ? dst[g] : (uint8_t)0; } })
-        }
-        // literal bytes: every window byte finds the member it follows
-        LANES({
-            const uint64_t upto = mL & ((LANE >= 63) ? ~0ull : ((2ull << LANE) - 1));
-            const int m  = upto ? 63 - __builtin_clzll(upto) : LANE;
-            const int os = SHFL(outStart, m), lp = SHFL(ll, m);
-            const int lm = lp & 0xFFFF, m1 = m + (lp >> 16);              // m1: the byte before the first literal
-            if (upto && LANE > m1 && LANE <= m1 + lm) lb[kDecTail + (os - (int)op0) + (LANE - m1 - 1)] = (uint8_t)b0[I_];
-        })
-        const unsigned long long td3 = STAT_NOW(); (void)td3;
-        STAT(2, td3 - td2);
-        put_pieces(far);
-        const unsigned long long td4 = STAT_NOW(); (void)td4;
-        STAT(3, td4 - td3);
-        // the rest in dependency order, LDS to LDS (see the memory version below for the rule)
-        for (uint64_t pend = mL & ~far; pend; ) {
-            const int f  = ctz64(pend);
-            const int lo = RL(mdst, f);                                                 // (an offset into lb)
-            LDS_FENCE();
-            if ((coopM >> f) & 1) {
-                const int len = RL(ml, f); const int64_t s0 = op0 + (RL(qoff, f) - kDecTail);
-                if (s0 + len <= op0) { LANES({ for (int i = LANE; i < len; i += 64) lb[lo + i] = dst[s0 + i]; }) }   // older than the window: from memory
-                else wave_copy_match(lb, lo, RL(off, f), len);
-                pend &= pend - 1;
-            } else {
-                STAT(8, 1);
-                const uint64_t go = pend & ~coopM & BALLOT(qoff[I_] + ml[I_] <= lo);
-                LANES({
-                    if (LANE_IN(go)) {
-                        const uint8_t* q = lb + qoff[I_]; const int len = ml[I_];
-                        g0[I_] = ld32u(q); g1[I_] = ld32u(q + len - 4); g2[I_] = ld32u(q + max_(len - 8, 0)); g3[I_] = ld64u(q + 4);
-                    }
-                })
-                LDS_FENCE();
-                put_pieces(go);
-                pend &= ~go;
-            }
-        }
-        LDS_FENCE();
-        const unsigned long long td5 = STAT_NOW(); (void)td5;
-        STAT(4, td5 - td4); STAT(6, 1);
-        // one sweep to memory, 16 bytes per lane (total <= 1024); the last chunk is written whole -- the bytes behind `total` are
-        // the next batch's (or the sequential step's) to write, and the caller has checked that 1088 bytes of room are left --
-        // and the last kDecTail bytes are kept for the next batch: all LDS reads first, one wait, then the stores
-        LV(v16u_t, sw); LV(uint32_t, t8);
-        LANES({
-            const uint64_t q0 = ld64u(lb + kDecTail + LANE * 16), q1 = ld64u(lb + kDecTail + LANE * 16 + 8);
-            sw[I_].w[0] = (uint32_t)q0; sw[I_].w[1] = (uint32_t)(q0 >> 32); sw[I_].w[2] = (uint32_t)q1; sw[I_].w[3] = (uint32_t)(q1 >> 32);
-            t8[I_] = (uint32_t)lb[total + (LANE & (kDecTail - 1))];
-        })
-        LDS_FENCE();
-        LANES({
-            if (LANE * 16 < total) *(v16u_t*)(dst + op0 + LANE * 16) = sw[I_];
-            if (LANE < kDecTail) lb[LANE] = (uint8_t)t8[I_];
-        })
-        *tailAt = op0 + total;
-        *ipp = ipn;
-        *opp = op0 + total;
-        STAT(5, STAT_NOW() - td5); STAT(7, __builtin_popcountll(far));
-        return __builtin_popcountll(members);
-    }
     auto copy_matches = [&](const uint64_t who) {
         LANES({
             if (LANE_IN(who)) {
@@ -1621,6 +1532,173 @@ DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __rest
     return __builtin_popcountll(members);
 }
 
+// The batch assembled in LDS: the steady state of k_decode_rec and of the decode role of k_l1_duplex.  Its control flow is written
+// like the parser's grid batch (a uniform branch costs this machine 80-90 cycles taken or not, a divergent `if` 45-58, a select 13:
+// scripts/micro/branch.hip, execz.hip) as far as that measured faster -- profiles/df_variants.txt has every form tried.  The caller
+// has primed `win` (the 16 bytes from ip0 + lane on) and the staged tail (lb[0, kDecTail): the output bytes before op0) -- at a
+// block's start and after every sequential step -- so the batch tests neither; the token walk makes its hops without a test; the
+// chain cuts are mask arithmetic; a batch without cooperative copies is asked nothing in its dependency rounds but the loop's own
+// test.  One question is left in the middle: a batch without members (lane 0 not plain, or its first sequence must stop) leaves
+// at once and touches nothing -- passing through as an empty batch cost more than the question (818 of them per 4 MiB text block).
+// The far loads, the literal scatter and the rounds' LDS loads keep their divergent `if`: switched-off lanes that load all the same
+// cost the memory pipeline more than the `if` costs the wave.
+// Returns whether the next vector batch may run: this one had members, and its end leaves 160 input bytes and 1088 bytes of room.
+enum : int { kDecHops = 22 };     // a sequence is at least three bytes: 22 tokens is all a 64-byte window holds, so 22 hops finish every walk
+DEV int wave_decode_lds_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int* ipp, int64_t* opp, LVREF(v16u_t, win),
+                              uint8_t* lb, const int iend, const int64_t oend,
+                              unsigned long long* st_ = nullptr)             // (diagnostics build: the caller's counters)
+{
+    const int ip0 = *ipp; const int64_t op0 = *opp;
+    (void)st_;
+    const unsigned long long td0 = STAT_NOW(); (void)td0;
+    LV(uint32_t, b0); LV(int, ll); LV(int, ml); LV(int, off); LV(int, nxt); LV(int, outLen); LV(int, plain); LV(int, coop);
+    const uint64_t plainMask = wave_decode_parse_window(win, b0, ll, ml, off, nxt, outLen, plain, coop);
+    const unsigned long long td1 = STAT_NOW(); (void)td1;
+    STAT(0, td1 - td0);
+    // Follow the token chain through the whole window: kDecHops hops, no test (mark the lane, fetch its successor; a successor
+    // beyond the window reads as lane 0, where the chain started -- walking on from there only re-marks its own members), then cut
+    // the chain at the first sequence that is not plain.  Lane 0 is always marked, so a window whose lane 0 is not plain is cut to
+    // nothing.  ((x & -x) - 1: the bits below the lowest set one, all ones for x == 0.)
+    uint64_t members = 0;
+    {
+        LV(int, nxtC);
+        LANES({ nxtC[I_] = nxt[I_] < 64 ? nxt[I_] : 0; })
+        int cur = 0;
+        for (int u = 0; u < kDecHops; ++u) { BITSET64(members, cur); cur = RL(nxtC, cur); }
+        const uint64_t odd = members & ~plainMask;
+        members &= (odd & (0 - odd)) - 1;
+    }
+    EMU_DEC(0, 1); EMU_DEC(1, __builtin_popcountll(members) == kDecHops);
+
+    // exclusive prefix sum of the members' output lengths -> where each sequence writes
+    LV(int, acc); LV(int, outStart); LV(int, sp);
+    { const uint64_t mL = members; LANES({ acc[I_] = LANE_IN(mL) ? outLen[I_] : 0; }) }
+    SCAN_INCL(acc);
+    {
+        const uint64_t mL = members;
+        LANES({
+            outStart[I_] = (int)op0 + acc[I_] - (LANE_IN(mL) ? outLen[I_] : 0);
+            sp[I_]       = outStart[I_] + (ll[I_] & 0xFFFF) - off[I_];                     // where the match bytes come from
+        })
+        // a source before the start of the output is the sequential step's business (error, or a dictionary); the batch's output
+        // stays inside the room the caller checked; and so is a long match whose source starts before the staged tail and runs
+        // into this batch's output as well
+        const uint64_t stop = mL & (BALLOT(sp[I_] < 0) | BALLOT(acc[I_] > 1024) |
+                                    BALLOT3(coop[I_], sp[I_] < op0 - kDecTail, (int64_t)sp[I_] + ml[I_] > op0));
+        members &= (stop & (0 - stop)) - 1;
+    }
+    const unsigned long long td2 = STAT_NOW(); (void)td2;
+    STAT(1, td2 - td1);
+    EMU_DEC(5, members == 0); EMU_DEC(7, __builtin_popcountll(members));
+    STAT(S_DBATCH, 1); STAT(S_DMEMB, __builtin_popcountll(members));
+    if (!members) return 0;
+    const uint64_t mL = members;
+    const int last  = 63 - __builtin_clzll(members);
+    const int total = RL(acc, last);                           // bytes this batch produces
+    const int ipn   = ip0 + RL(nxt, last);
+    // request the next batch's window now: its latency hides behind this batch's copies (ipn + 63 + 16 < ip0 + 160 <= iend)
+    LANES({ win[I_] = *(const v16u_t*)(src + ipn + LANE); })
+    // Match bytes, 4..18 per member lane.  "Far" sources end before this batch's output: all of them are copied at once.
+    // A "near" source may contain bytes this batch produces; those go in dependency order below.
+    const uint64_t coopM = mL & BALLOT(coop[I_]);
+    const uint64_t far = mL & ~coopM & BALLOT((int64_t)sp[I_] + ml[I_] <= op0);
+    // A match of 4..18 bytes travels as four overlapping pieces: [0,4) and [len-4,len) always, [len-8,len-4) from 8 bytes on,
+    // [4,12) from 12 on -- together they cover every length, and where two overlap they carry the same bytes.  Every piece
+    // has a fixed place per lane and batch, so a round is four loads and four stores; a lane that is not part of the round
+    // (or a piece its length does not have) stores to the dump bytes behind the buffer: a divergent `if` costs this machine
+    // ~45 cycles whether any lane takes it or not, a redirected store costs a select.
+    LV(int, mdst); LV(int, qoff);
+    LANES({
+        mdst[I_] = kDecTail + (outStart[I_] - (int)op0) + (ll[I_] & 0xFFFF);       // where the match goes, as an offset into lb
+        qoff[I_] = mdst[I_] - off[I_];                                             // ... and where it comes from
+    })
+    LV(uint32_t, g0); LV(uint32_t, g1); LV(uint32_t, g2); LV(uint64_t, g3);
+    auto put_pieces = [&](const uint64_t who) {
+        LANES({
+            const bool on = LANE_IN(who);
+            const int len = on ? ml[I_] : 0, at = on ? mdst[I_] : (int)kDecDump;
+            st32u(lb + at, g0[I_]);
+            st32u(lb + at + max_(len - 4, 0), g1[I_]);
+            st32u(lb + (len >= 8 ? at + len - 8 : (int)kDecDump), g2[I_]);
+            st64u(lb + (len >= 12 ? at + 4 : (int)kDecDump + 8), g3[I_]);
+        })
+    };
+    // far matches: their bytes are requested from memory first
+    LANES({
+        g0[I_] = 0; g1[I_] = 0; g2[I_] = 0; g3[I_] = 0;
+        if (LANE_IN(far)) {
+            const uint8_t* q = dst + sp[I_]; const int len = ml[I_];
+            g0[I_] = ld32u(q); g1[I_] = ld32u(q + len - 4); g2[I_] = ld32u(q + max_(len - 8, 0)); g3[I_] = ld64u(q + 4);
+        }
+    })
+    // literal bytes: every window byte finds the member it follows
+    LANES({
+        const uint64_t upto = mL & ((LANE >= 63) ? ~0ull : ((2ull << LANE) - 1));
+        const int m  = upto ? 63 - __builtin_clzll(upto) : LANE;
+        const int os = SHFL(outStart, m), lp = SHFL(ll, m);
+        const int lm = lp & 0xFFFF, m1 = m + (lp >> 16);              // m1: the byte before the first literal
+        if (upto && LANE > m1 && LANE <= m1 + lm) lb[kDecTail + (os - (int)op0) + (LANE - m1 - 1)] = (uint8_t)b0[I_];
+    })
+    const unsigned long long td3 = STAT_NOW(); (void)td3;
+    STAT(2, td3 - td2);
+    put_pieces(far);
+    const unsigned long long td4 = STAT_NOW(); (void)td4;
+    STAT(3, td4 - td3);
+    // The rest in dependency order, LDS to LDS.  Near matches: a round takes every pending one whose source ends before the first
+    // pending match's output (the first one always qualifies: offset >= length), so nothing it reads is still to be written; rounds
+    // follow each other while a near match comes first -- the loop's own test is the only question a batch without cooperative
+    // copies is asked.  Long or overlapping matches: one cooperative copy each, when they come first.
+    for (uint64_t pend = mL & ~far; ; ) {
+        while ((pend & (0 - pend)) & ~coopM) {
+            STAT(8, 1); EMU_DEC(2, 1);
+            const int lo = RL(mdst, ctz64(pend));                                       // (an offset into lb)
+            LDS_FENCE();
+            const uint64_t go = pend & ~coopM & BALLOT(qoff[I_] + ml[I_] <= lo);
+            LANES({
+                if (LANE_IN(go)) {
+                    const uint8_t* q = lb + qoff[I_]; const int len = ml[I_];
+                    g0[I_] = ld32u(q); g1[I_] = ld32u(q + len - 4); g2[I_] = ld32u(q + max_(len - 8, 0)); g3[I_] = ld64u(q + 4);
+                }
+            })
+            LDS_FENCE();
+            put_pieces(go);
+            pend &= ~go;
+        }
+        if (!pend) break;
+        {
+            const int f = ctz64(pend), lo = RL(mdst, f), len = RL(ml, f);
+            const int64_t s0 = op0 + (RL(qoff, f) - kDecTail);
+            EMU_DEC(3, 1); EMU_DEC(4, s0 + len <= op0);
+            LDS_FENCE();
+            if (s0 + len <= op0) { LANES({ for (int i = LANE; i < len; i += 64) lb[lo + i] = dst[s0 + i]; }) }   // older than the window: from memory
+            else wave_copy_match(lb, lo, RL(off, f), len);
+            pend &= pend - 1;
+        }
+    }
+    LDS_FENCE();
+    const unsigned long long td5 = STAT_NOW(); (void)td5;
+    STAT(4, td5 - td4); STAT(6, 1);
+    // one sweep to memory, 16 bytes per lane (total <= 1024); the last chunk is written whole -- the bytes behind `total` are
+    // the next batch's (or the sequential step's) to write, and the caller has checked that 1088 bytes of room are left --
+    // and the last kDecTail bytes are kept for the next batch: all LDS reads first, one wait, then the stores.  (The sweep's store
+    // keeps its `if`: memory has no dump bytes, and a lane behind `total` must write nothing.)
+    LV(v16u_t, sw); LV(uint32_t, t8);
+    LANES({
+        const uint64_t q0 = ld64u(lb + kDecTail + LANE * 16), q1 = ld64u(lb + kDecTail + LANE * 16 + 8);
+        sw[I_].w[0] = (uint32_t)q0; sw[I_].w[1] = (uint32_t)(q0 >> 32); sw[I_].w[2] = (uint32_t)q1; sw[I_].w[3] = (uint32_t)(q1 >> 32);
+        t8[I_] = (uint32_t)lb[total + (LANE & (kDecTail - 1))];
+    })
+    LDS_FENCE();
+    LANES({
+        if (LANE * 16 < total) *(v16u_t*)(dst + op0 + LANE * 16) = sw[I_];
+        lb[LANE < kDecTail ? LANE : (int)kDecDump + (LANE & 15)] = (uint8_t)t8[I_];        // (the upper lanes': to the dump)
+    })
+    *ipp = ipn;
+    *opp = op0 + total;
+    STAT(5, STAT_NOW() - td5); STAT(7, __builtin_popcountll(far));
+    return (members != 0) & (ipn + 160 <= iend) & (op0 + total + 1088 <= oend);
+}
+
 // LZ4_decompress_safe, full block, no dictionary.  Returns decoded size or liblz4's negative error code
 // -(input position)-1.  The reference's fast loop (>= 64 output bytes left) and safe loop reject at
 // different points, so both sets of tests are reproduced (see oracle/plz4_oracle.c for the same shape).
@@ -1641,16 +1719,32 @@ DEV int wave_decode_block(const uint8_t* __restrict__ src, const int n, uint8_t*
     if (cap == 0) return (n == 1 && UNI(src[0]) == 0) ? 0 : -1;
     if (n == 0) return -1;
     bool fast = (oend - op) >= 64;
-    int64_t tailAt = -1;                          // LDS staging: output position the staged tail belongs to
     LV(v16u_t, win); int winIp = -1;              // the vector path's input window, requested one batch ahead
     LANES({ win[I_].w[0] = 0; win[I_].w[1] = 0; win[I_].w[2] = 0; win[I_].w[3] = 0; })
     STAT_DECL;
 
     for (;;) {
-        if (fast && ip + 160 <= iend && op + 1088 <= oend) {
+        if (kLds) {
+            // Into the steady state, at the block's start and after every sequential step: prime the input window and the staged
+            // tail of what is already written, then batch after batch while each says the next may run (wave_decode_lds_batch).
+            // The last one -- one without members, or one that ran out of room -- falls through to the sequential step.
+            if (fast && ip + 160 <= iend && op + 1088 <= oend) {
+                WAVE_FENCE();
+                LANES({
+                    win[I_] = *(const v16u_t*)(src + ip + LANE);
+                    if (LANE < kDecTail) { const int64_t g = op - kDecTail + LANE; lb[LANE] = g >= 0 ? dst[g] : (uint8_t)0; }
+                })
+                LDS_FENCE();
+                EMU_DEC(6, 1);
+                int go;
+                do {
+                    go = wave_decode_lds_batch(src, dst, &ip, &op, win, lb, iend, oend, STAT_PTR);
+                    WAVE_FENCE();
+                } while (go);
+            }
+        } else if (fast && ip + 160 <= iend && op + 1088 <= oend) {
             WAVE_FENCE();
-            const int nm = wave_decode_plain_batch<kLds>(src, dst, &ip, &op, win, &winIp, lb, &tailAt, STAT_PTR);
-            STAT(S_DBATCH, 1); STAT(S_DMEMB, nm);
+            const int nm = wave_decode_plain_batch(src, dst, &ip, &op, win, &winIp);
             if (nm > 0) { WAVE_FENCE(); continue; }
         }
         const uint32_t token = UNI(src[ip]); ip++;

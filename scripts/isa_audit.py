@@ -1,10 +1,10 @@
-"""What the compiler made of the level-1 parser's kernels, without a GPU.
+"""What the compiler made of the level-1 parser's kernels and of the record decoder, without a GPU.
 
     python scripts/isa_audit.py                  build the device code of the tree (hipcc, the product's flags) and audit it
     python scripts/isa_audit.py path/to/lib.so   audit the gfx950 code object inside a built library
     ... --keep DIR                               leave the code object and its disassembly in DIR
 
-Disassembles k_l1_parse<10> and k_l1_duplex<1,1,3> (llvm-objdump) and prints, per kernel: code bytes, branch instructions, s_nops,
+Disassembles k_l1_parse<10>, k_l1_duplex<1,1,3> and k_decode_rec (llvm-objdump) and prints, per kernel: code bytes, branch instructions, s_nops,
 `v_cndmask 0,1 -> v_cmp_ne` pairs (a lane mask turned into a 0/1 vector and back into a mask: what a BALLOT of a conjunction
 compiles to), `v_cndmask 0,1 -> v_readfirstlane` pairs (a wave-uniform bool that travels through a vector register), and the
 registers / spills / scratch / LDS of the kernel's metadata; a build adds the occupancy of -Rpass-analysis=kernel-resource-usage.
@@ -20,7 +20,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = (("k_l1_parse<10>", "10k_l1_parseILi10EE"), ("k_l1_duplex<1,1,3>", "11k_l1_duplexILi1ELi1ELi3EE"))
+KERNELS = (("k_l1_parse<10>", "10k_l1_parseILi10EE"), ("k_l1_duplex<1,1,3>", "11k_l1_duplexILi1ELi1ELi3EE"),
+           ("k_decode_rec", "12k_decode_recE"))
 WINDOW = 12          # instructions within which the consumer of a v_cndmask 0,1 is looked for
 
 
