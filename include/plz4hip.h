@@ -84,8 +84,15 @@
  * The device-resident calls with history outside the block (dev_encode_records_ex, dev_encode_body_ex) take it likewise; a call of
  * more blocks there runs the staged level-1 design with one wavefront per block and holds the level-1 workspace above (2.25 bytes
  * per input byte of a group of blocks), PLZ4HIP_L1X=0 the one-kernel encoder (see section C).
- * Duplex calls and level 2 keep their kernels.  It keeps about 3 bytes per input byte of the call's blocks (the pieces' tables
+ * Duplex calls keep their kernels.  It keeps about 3 bytes per input byte of the call's blocks (the pieces' tables
  * and records) until plz4hip_ctx_trim.  plz4hip_ctx_counters reports what these few-block paths did.
+ * A level-2 call (LZ4MID) of at most PLZ4HIP_MX_MAX_BLOCKS (512; 0: off) independent blocks, the largest above one piece and at most 4 MiB, without
+ * a dictionary, linked blocks or a rider, has its walk cut across the chip the same way: pieces of PLZ4HIP_MX_PIECE_KIB (128), a
+ * guessed start PLZ4HIP_MX_WARMUP_KIB (256) early -- level 2's tables have one slot per four positions of the window, so a wrong
+ * entry lives for a whole window.  Blocks of at most one piece are one piece of the same call.  Output, results, error codes and
+ * capacity verdicts are exactly those of one wavefront per block; a call the path does not take, or whose workspace is refused
+ * (about 5 bytes per input byte: three 128 KiB states and the records per piece, kept until plz4hip_ctx_trim), runs that launch.
+ * Level 2 with a dictionary or linked blocks keeps one wavefront per block.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
  * calls, rounds 1-3), PLZ4HIP_HC12_LAZY (level 12 with its searches made on demand), PLZ4HIP_HC_OVERLAP_OFF / _MIN / _GROUPS (levels 3..11: a call of 2048
  * blocks or more runs in four or more groups, the list builder of the next group on a second stream of the ctx beside the walk
@@ -138,7 +145,9 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
  * route of plz4hip_dev_encode_records_ex / _body_ex (not those the one-kernel encoder took), [9] blocks of at most 4 KiB under a
  * dictionary context encoded by the wave-wide HC parser (levels 2..12), [10] raw blocks above 4 MiB + 8 of capacity answered by the
  * few-block decoder (they count in [3] as well), [11] the jump rounds launched for the last call with such a block, [12] the literal
- * runs and matches that call handed to its grid-wide stage.  Returns how many counters there are (13), or PLZ4HIP_E_*. */
+ * runs and matches that call handed to its grid-wide stage, [13] blocks encoded by the few-block level-2 path, [14] its rounds that
+ * parsed something in the last such call, [15] pieces it parsed more than once.  Returns how many counters there are (16), or
+ * PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */

@@ -676,8 +676,43 @@ DEV void hc_mid_prime(const uint8_t* __restrict__ src, const int size, uint32_t*
 // ip + 1 and no catch-up (its distance is larger than the position).
 struct MidNoCtx { enum : bool { on = false }; DEVM HcMatch find(const uint8_t*, uint32_t, const uint8_t*) const { HcMatch m = {0, 0, 0}; return m; } };
 struct MidDictCtx { enum : bool { on = true }; HcDict d; DEVM HcMatch find(const uint8_t* ipp, uint32_t ipIndex, const uint8_t* mlim) const { return mid_search_ctx(d, ipp, ipIndex, mlim); } };
-template <bool kD = false, class Tab = uint32_t*, class Ctx = MidNoCtx>
-DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab h8t, uint64_t* seq, int* lastAnchor, const int pfxArg = 0, const Ctx ctx = Ctx())
+//
+// kRun / run: the walk of a PIECE of an independent block (lz4_mx_device.inl).  Right after a sequence is finished -- the fills
+// around the match are made (:678-706) and anchor == ip -- the rest of the walk depends on the anchor, the live entries of the two
+// tables (live: index + 65535 >= current, the test of all three uses, :578 / :609 / :623; a dead entry never comes back) and the
+// input; the step (:668) and the catch-up (:673) reach back to the anchor only.  Such a post-match state is where a walk may be
+// started, noted and stopped.
+enum : int { kMxTab = 2 * 16384 };      // words of such a state: the short-hash table, then the long-hash table
+struct MidRun {
+    int       entryAnchor;      // -1: the block's start; else a post-match state at this anchor ...
+    int       primed;           // ... whose tables are in h4t / h8t already (0: all-zero tables, every entry dead: a guess)
+    int       cp;               // >= 0: note the first post-match state at or beyond this position ...
+    uint32_t* cpTab;            // ... both tables copied here (32 Ki words, short hash first), cpAnchor = its anchor; records before it are dropped
+    int       cpAnchor;
+    int       end;              // stop at the first post-match state at or beyond this position: outAnchor, the tables stay in h4t / h8t
+    int       outAnchor;        // -1: none
+    int       seqCap;           // room for records; a walk that fills it is given up (over)
+    int       fin, over;        // reached the block's end / gave up
+};
+// at a post-match state: true = the walk ends here
+DEV bool mid_run_state(MidRun* run, uint32_t* h4t, uint32_t* h8t, SeqSink& out, const int ip, const int anchor, const int mflimit)
+{
+    if (run->cp >= 0 && run->cpAnchor < 0) {
+        if (anchor >= run->cp) {
+            WAVE_FENCE();
+            uint32_t* const t = run->cpTab;
+            LANES({ for (int i = LANE; i < 16384; i += 64) { t[i] = h4t[i]; t[16384 + i] = h8t[i]; } })
+            run->cpAnchor = anchor; out.n = 0;
+        } else if (out.n >= 64) out.n = 0;                                                      // (the warm-up's records need no room)
+    }
+    if (out.n >= run->seqCap) { run->over = 1; return true; }
+    if (ip > mflimit) return false;                                                             // (the block's end: the loop says so)
+    if (anchor >= run->end) { run->outAnchor = anchor; return true; }
+    return false;
+}
+template <bool kD = false, class Tab = uint32_t*, class Ctx = MidNoCtx, bool kRun = false>
+DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab h8t, uint64_t* seq, int* lastAnchor, const int pfxArg = 0, const Ctx ctx = Ctx(),
+                     MidRun* run = nullptr)
 {
     const int pfx = kD ? pfxArg : 0;
     const uint8_t* const src = blk - pfx;
@@ -685,8 +720,12 @@ DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab 
     const uint32_t prefixIdx = kHcBase + (uint32_t)pfx;
     *lastAnchor = 0;
     if constexpr (std::is_pointer<Tab>::value) {
-        LANES({ for (int i = LANE; i < 16384; i += 64) { h4t[i] = 0u; h8t[i] = 0u; } })        // LZ4_initStreamHC: everything zero, lz4hc.c:1582-1583
-        WAVE_FENCE();
+        bool zero = true;
+        if constexpr (kRun) zero = !run->primed;
+        if (zero) {
+            LANES({ for (int i = LANE; i < 16384; i += 64) { h4t[i] = 0u; h8t[i] = 0u; } })    // LZ4_initStreamHC: everything zero, lz4hc.c:1582-1583
+            WAVE_FENCE();
+        }
     }
     if constexpr (kD) hc_mid_prime(src, pfx, h4t, h8t);
     SeqSink out; out.seq = seq; out.n = 0; out.bias = pfx;
@@ -694,6 +733,12 @@ DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab 
     const int mflimit = N - kMfLimit, matchlimit = N - kLastLiterals;
     const uint32_t ilimitIdx = (uint32_t)(N - 8) + kHcBase;
     int ip = pfx, anchor = pfx, width = kMidWidth0;
+    [[maybe_unused]] bool stopped = false;
+    if constexpr (kRun) {
+        if (run->entryAnchor >= 0) { ip = run->entryAnchor; anchor = ip; }
+        if (n < kMinLength || ip > mflimit) { run->fin = 1; *lastAnchor = anchor - pfx; return 0; }
+        if (mid_run_state(run, h4t, h8t, out, ip, anchor, mflimit)) return 0;                  // (a state handed in that lies behind the piece already)
+    }
     if (n < kMinLength || ip > mflimit) { return 0; }
 
     // a batch: the lanes' positions and their bytes (requested as soon as the batch's start is known: before the table fills of
@@ -831,7 +876,9 @@ DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab 
                 }
             } })
         }
+        if constexpr (kRun) { if (mid_run_state(run, h4t, h8t, out, ip, anchor, mflimit)) { stopped = true; break; } }
     }
+    if constexpr (kRun) run->fin = !stopped;
     out.finish();
     *lastAnchor = anchor - pfx;
     return out.n;

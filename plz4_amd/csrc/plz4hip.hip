@@ -29,6 +29,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4hcx_device.inl"
 #include "lz4_dx_device.inl"
 #include "lz4_fx_device.inl"
+#include "lz4_mx_device.inl"
 #include "ws_layout.h"
 #include "route.h"
 
@@ -1222,6 +1223,39 @@ template <bool kD> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_
     }
 }
 
+// ---- level 2 on a few independent blocks cut across the chip (lz4_mx_device.inl): grid (pieces, blocks of the group), one wave each,
+// one launch per round, then the gather into the staged path's records (l1Seq / l1Info) -- launch_emit(Emit::Mid) runs unchanged.
+// Workspace per piece: meta, entry state, two exit states (a piece walks inside its exit slot), records.  cnt: plz4hip_ctx_counters.
+struct MxArgs { FxPiece* meta; uint32_t* tabIn; uint32_t* tabOut; uint64_t* rec; int P, pb, warm, recStride; unsigned long long* cnt; };
+__global__ __launch_bounds__(64) void k_mx_piece(CodecArgs a, MxArgs f, int round)
+{
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    if (n < 0 || n > a.l1MaxLen) {                                           // a block the workspace was not sized for: no result, as k_hc_mid says it
+        if (round == 1 && k == 0 && (threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = -1; inf.lastAnchor = 0; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
+        return;
+    }
+    const int64_t pb0 = (int64_t)i * f.P;
+    mx_piece(a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * kMxTab, f.tabOut + pb0 * 2 * kMxTab,
+             f.rec + pb0 * f.recStride, f.recStride);
+}
+__global__ __launch_bounds__(64) void k_mx_gather(CodecArgs a, MxArgs f)
+{
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    if (n < 0 || n > a.l1MaxLen || k >= mx_pieces(n, f.pb)) return;
+    const int64_t pb0 = (int64_t)i * f.P;
+    const FxPiece* m = f.meta + pb0;
+    const int g = mx_gather(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
+                            (int)a.l1SeqStride - 1, a.l1Info + i);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicMax(&f.cnt[14], (unsigned long long)m[k].lastRound);
+        if (m[k].runs > 1) atomicAdd(&f.cnt[15], 1ull);
+        if (g == 2) atomicAdd(&f.cnt[13], 1ull);
+    }
+}
+__global__ __launch_bounds__(64) void k_mx_begin(unsigned long long* cnt) { if (threadIdx.x == 0) cnt[14] = 0; }
+
 // clz4.NewDictCtxHC (clz4.go:122-147): workgroup 0 builds the level-2 (lz4mid) tables of a dictionary, workgroup 1 the
 // hash-chain tables every other level shares.  tabs = 2 x kHcWorkBytes.
 __global__ __launch_bounds__(64) void k_hc_dict_prime(const uint8_t* dict, int len, uint8_t* tabs)
@@ -1792,6 +1826,8 @@ struct plz4hip_ctx {
     hipStream_t  dxHashStream = nullptr; hipEvent_t evDxFork = nullptr, evDxHash = nullptr;   // records: the block checksums beside the decode
     // the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): pieces' states and records, sized per call
     DeviceBuffer fx;  StreamOrder fxOrder;
+    // level 2 on a few independent blocks cut across the chip (lz4_mx_device.inl): pieces' states and records, sized per call
+    DeviceBuffer mx;  StreamOrder mxOrder;
     // plz4hip_dev_encode_body_ex on the one-kernel encoder (PLZ4HIP_L1X=0, PLZ4HIP_L1_FUSED): its records before they are compacted
     DeviceBuffer xstage;  StreamOrder xstageOrder;
     // plz4hip_ctx_counters: [0] blocks encoded by the few-block level-1 path, [1] its rounds in the last such call, [2] pieces it
@@ -1799,19 +1835,21 @@ struct plz4hip_ctx {
     // linked) answered by it, [5] its jump rounds in the last such call (the maximum over the groups of a call cut into groups),
     // [6] the groups of the last call that was cut into groups, [7] blocks with history outside the block (dictionary, linked)
     // encoded by the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the bulk staged
-    // route (k_l1x_parse), [9] blocks of at most 4 KiB under a dictionary context encoded by the wave-wide HC parser (k_hcx)
-    static constexpr int kCounters = 13;
+    // route (k_l1x_parse), [9] blocks of at most 4 KiB under a dictionary context encoded by the wave-wide HC parser (k_hcx),
+    // [13] blocks encoded by the few-block level-2 path, [14] its rounds that parsed something in the last such call, [15] pieces
+    // it parsed more than once
+    static constexpr int kCounters = 16;
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
     // plz4hip_dev_decode_records_ex: the chainFirst of the last call (int32 each), which that job's kernels read
     DeviceBuffer chainCopy;  StreamOrder chainOrder;
     struct Owned { DeviceBuffer* buf; StreamOrder* order; bool trimmed; };     // trimmed: plz4hip_ctx_trim gives it back
-    std::array<Owned, 10> owned()
+    std::array<Owned, 11> owned()
     {
         return {{{&hc, &hcOrder, true}, {&h12, &hcOrder, true}, {&hcPfx, &hcOrder, false}, {&l1[0], &l1Order[0], true},
                  {&l1[1], &l1Order[1], true}, {&dx, &dxOrder, true}, {&fx, &fxOrder, true}, {&lenCopy, &lenOrder, false},
-                 {&chainCopy, &chainOrder, false}, {&xstage, &xstageOrder, true}}};
+                 {&chainCopy, &chainOrder, false}, {&xstage, &xstageOrder, true}, {&mx, &mxOrder, true}}};
     }
 };
 
@@ -2037,6 +2075,7 @@ void bind_hc_pre(CodecArgs& a, uint8_t* base, const HcPreLayout& L, bool lists)
 // The launchers' switches (route.h), read once at the top of launch_l1 / launch_hc / launch_decode: every call sees the environment
 // as it is when the call is made.
 L1Switches read_l1_switches() { return parse_l1_switches([](const char* n) { return (const char*)getenv(n); }); }
+MxSwitches read_mx_switches() { return parse_mx_switches([](const char* n) { return (const char*)getenv(n); }); }
 HcSwitches read_hc_switches() { return parse_hc_switches([](const char* n) { return (const char*)getenv(n); }); }
 DxSwitches read_dx_switches() { return parse_dx_switches([](const char* n) { return (const char*)getenv(n); }); }
 
@@ -2351,6 +2390,11 @@ FxlBlk* bind_fx(FxArgs& fx, uint8_t* base, const FxLayout& F, bool hist)
     fx.rec = (uint64_t*)(base + F.offRec);
     return hist ? (FxlBlk*)(base + F.offBlk) : nullptr;
 }
+void bind_mx(MxArgs& mx, uint8_t* base, const MxLayout& M)
+{
+    mx.meta = (FxPiece*)(base + M.offMeta); mx.tabIn = (uint32_t*)(base + M.offIn); mx.tabOut = (uint32_t*)(base + M.offOut);
+    mx.rec = (uint64_t*)(base + M.offRec);
+}
 
 // Which of the ctx's level-1 workspaces a call on s takes: the one this stream used last; else one whose last job is over (no second
 // allocation for streams that merely take turns); else one that does not exist yet; else the first one (and the wait for it).
@@ -2419,6 +2463,8 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     const bool mid = midDeclined != nullptr;
     const L1Shape shape{nb, maxLen, rawMode != 0, mid, rider != nullptr, hist, l1x, a.bodyOff != nullptr, hist && a.dictLen >= 8};
     const L1Want want = l1_want(shape, sw);
+    // level 2: whether the few-block walk takes the call (read once; a level-1 call never asks)
+    const MxWant mxWant = mid ? mx_want(MxShape{a.level, nb, maxLen, a.hcEx != 0 || a.hcPfx != nullptr, rider != nullptr}, read_mx_switches()) : MxWant{};
     a.rawMode = rawMode; a.blk0 = 0; a.nBlocks = nb;
     const bool shared = (ws == nullptr);
     int wsi = 0;
@@ -2453,8 +2499,10 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, granted ? "" : " (fused)");
     }
     // from here on the jobs are marked behind whatever was enqueued, whichever way the call ends
-    MarkOnExit job, fxJob;
+    MarkOnExit job, fxJob, mxJob;
     FxArgs fx{};
+    MxArgs mx{};
+    bool mxGranted = false;
     FxlBlk* xb = nullptr;                                                       // hist: per block of a group, its segment (k_fxl_prep)
     L1Layout L{};
     bool fxGranted = false;
@@ -2471,8 +2519,17 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             bool refused = false;  HIPCHK(c, c->fx.reserve(F.total, c->fxOrder, &refused));
             if (!refused) { xb = bind_fx(fx, c->fx.d, F, hist); fxGranted = true; fxJob.arm(c->fxOrder, s); }
         }
+        if (mxWant.mx) {
+            // likewise the few-block level-2 walk's; when it cannot be had, the call walks one wave per block (k_hc_mid): same bytes
+            mx.pb = mxWant.piece; mx.warm = mxWant.warm; mx.P = mxWant.P; mx.recStride = mx_rec_stride_host(mx.pb); mx.cnt = c->d_counters;
+            const MxLayout M = mx_layout(per, mx.P, mx.recStride);
+            HIPCHK(c, c->mxOrder.wait(s));
+            bool refused = false;  HIPCHK(c, c->mx.reserve(M.total, c->mxOrder, &refused));
+            if (!refused) { bind_mx(mx, c->mx.d, M); mxGranted = true; mxJob.arm(c->mxOrder, s); }
+        }
     }
     const L1Route route = l1_route(shape, sw, want, granted, fxGranted);
+    const bool mxOn = route == L1Route::Mid && mx_route(mxWant, granted, mxGranted);
     switch (route) {
     case L1Route::NoMemBody:
         return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
@@ -2487,6 +2544,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, job.leave());
         HIPCHK(c, fxJob.leave());
+        HIPCHK(c, mxJob.leave());
         return PLZ4HIP_OK;
     default: break;
     }
@@ -2503,6 +2561,12 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         } else if (route == L1Route::Mid) c->gatePending = false;
         switch (route) {
         case L1Route::Mid:
+            if (mxOn) {                                                          // P rounds are always enough, as on the Fx route
+                if (g0 == 0) hipLaunchKernelGGL(k_mx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
+                for (int r = 1; r <= mx.P; ++r) hipLaunchKernelGGL(k_mx_piece, dim3(mx.P, ng), dim3(64), 0, s, a, mx, r);
+                hipLaunchKernelGGL(k_mx_gather, dim3(mx.P, ng), dim3(64), 0, s, a, mx);
+                break;
+            }
             hipLaunchKernelGGL(hc_mid_kernel(a.hcPfx != nullptr), dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
             break;
         case L1Route::Fxl:
@@ -2542,6 +2606,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     }
     HIPCHK(c, job.leave());
     HIPCHK(c, fxJob.leave());
+    HIPCHK(c, mxJob.leave());
     return PLZ4HIP_OK;
 }
 

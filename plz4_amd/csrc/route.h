@@ -139,6 +139,31 @@ inline HcPlan hc_route(const HcShape& k, const HcSwitches& sw, bool midDeclined 
     return p;
 }
 
+// ---------------------------------------------------------------------------------------------------- level 2, few blocks (launch_l1)
+// HcRoute::MidStaged on independent blocks: the walk cut into pieces across the chip (lz4_mx_device.inl) instead of k_hc_mid's one
+// wave per block.  The pieces walk about three times the block's bytes, which is free only while the chip has idle waves.
+// PLZ4HIP_MX_MAX_BLOCKS: 512, the largest measured count at which the pieces beat one wave per block by more than both spreads, kernels
+// alone and through host buffers (profiles/mx_rate.json, 4 MiB T blocks: 663 against 984 ms; at 1024 the kernels alone tie, 1 222 ms,
+// at 2048 they lose, 2 357 against 1 556).  The workspace of such a call is 5 bytes per input byte (10 GiB at 512 x 4 MiB).
+constexpr int kMxMaxBlocks = 512;
+struct MxSwitches {
+    int maxBlocks = kMxMaxBlocks;          // PLZ4HIP_MX_MAX_BLOCKS (0: off)
+    int pieceKiB = 128, warmKiB = 256;     // PLZ4HIP_MX_PIECE_KIB in 1..4096, PLZ4HIP_MX_WARMUP_KIB in 0..4096 (rounds per choice)
+};
+struct MxShape { int level, nb, maxLen; bool hcEx, rider; };
+// What the call asks for before anything is reserved: pieces of `piece` bytes, guessed starts `warm` bytes early, P pieces per block.
+struct MxWant { bool mx; int piece, warm, P; };
+inline MxWant mx_want(const MxShape& k, const MxSwitches& sw)
+{
+    MxWant w{};
+    // (a call whose largest block is one piece has nothing to cut: one wave per block either way, so it keeps today's launch)
+    w.mx = k.level == 2 && !k.hcEx && !k.rider && k.nb >= 1 && k.nb <= sw.maxBlocks && k.maxLen > (sw.pieceKiB << 10) && k.maxLen <= kSeqMaxBlock;
+    if (w.mx) { w.piece = sw.pieceKiB << 10; w.warm = sw.warmKiB << 10; w.P = (k.maxLen + w.piece - 1) / w.piece; }
+    return w;
+}
+// ... and given what was granted: the staged call's group workspace and the pieces' own.  false: today's k_hc_mid launch.
+inline bool mx_route(const MxWant& w, bool stagedGranted, bool mxGranted) { return w.mx && stagedGranted && mxGranted; }
+
 // The groups of the segmented route over a workspace of `group` blocks (HcLayout::group).  Without overlap: groups of equal size.
 // With it (the list builder of group g+1 beside the walk of group g, over the two halves of the workspace) only the first group's
 // builder is exposed, so the groups start at an eighth and double (a builder takes about half the time of the walk over the same
@@ -273,6 +298,16 @@ template <class Get> HcSwitches parse_hc_switches(Get&& get)
     { const int w = (int)num("PLZ4HIP_HC_OVERLAP_GROUPS", 4); sw.overlapGroups = w < 2 ? 2 : w; }
     sw.budgetGiB = num("PLZ4HIP_HC_BUDGET_GIB", 0);
     sw.h12Group = (int)num("PLZ4HIP_HC12_GROUP", 0); sw.group = (int)num("PLZ4HIP_HC_GROUP", 0);
+    return sw;
+}
+template <class Get> MxSwitches parse_mx_switches(Get&& get)
+{
+    const auto num = [&](const char* n, int unset) { const char* v = get(n); return v ? atoi(v) : unset; };
+    MxSwitches sw;
+    sw.maxBlocks = num("PLZ4HIP_MX_MAX_BLOCKS", kMxMaxBlocks);
+    if (sw.maxBlocks > 65535) sw.maxBlocks = 65535;                            // (the blocks of a group are the grid's y)
+    { const int x = num("PLZ4HIP_MX_PIECE_KIB", 0); if (x >= 1 && x <= 4096) sw.pieceKiB = x; }
+    { const int x = num("PLZ4HIP_MX_WARMUP_KIB", -1); if (x >= 0 && x <= 4096) sw.warmKiB = x; }
     return sw;
 }
 template <class Get> DxSwitches parse_dx_switches(Get&& get)

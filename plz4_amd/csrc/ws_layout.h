@@ -122,6 +122,22 @@ inline FxLayout fx_layout(int per, int P, int recStride, bool hist, std::vector<
     return L;
 }
 
+// ---------------------------------------------------------------------------------------------------- few-block level-2 parse (c->mx)
+// [FxPiece per piece][state in][states out x 2][records recStride per piece]; a state: both tables, kMxTab words (128 KiB)
+struct MxLayout { size_t offMeta, offIn, offOut, offRec, total; };
+inline MxLayout mx_layout(int per, int P, int recStride, std::vector<WsTake>* log = nullptr)
+{
+    MxLayout L{};
+    Carver c{log};
+    const size_t nP = (size_t)per * (size_t)P;
+    L.offMeta = c.take<FxPiece>(nP);
+    L.offIn = c.take<uint32_t>(nP * kMxTab, 4);
+    L.offOut = c.take<uint32_t>(2 * nP * kMxTab, 4);
+    L.offRec = c.take<uint64_t>(nP * (size_t)recStride, 8);
+    L.total = c.at;
+    return L;
+}
+
 // ---------------------------------------------------------------------------------------------------- HC levels 3..12 (c->h12)
 // Level 12 on independent blocks without dictionary runs in three phases per group of blocks (lz4hc12_device.inl):
 // chain -> search results -> parser.  Per block the group workspace holds the chain (2 B per position) and F (8 B per position).
