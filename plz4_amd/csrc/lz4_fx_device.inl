@@ -10,17 +10,8 @@
 // entry state is the first post-match state at or beyond its start; its exit state the first one at or beyond its end -- which is
 // piece k+1's entry state.
 //
-// Rounds (one launch each, grid (pieces, blocks)):
-//   round 1   piece 0 parses from the block's start (exact).  Piece k > 0 starts `warm` bytes early from a guessed state (every
-//             slot "position 0"), records the state it reaches at its start (inAnchor / tabIn) and keeps the records from there.
-//   round r   piece k runs again iff piece k-1 ran in round r-1, did not reach the block's end, and its exit state differs from
-//             piece k's recorded entry state (same anchor, same live entries); it then starts from that exit state.
-// Exit states are kept per round parity (tabOut[r & 1]): round r reads r-1's and writes r's, so no piece waits for another.
-// Piece 0 is exact after round 1 and, by induction, piece i after round i + 1: P rounds are always enough, and a piece that is
-// exact never runs again.  The gather (one wave per piece) lays the records of the chain 0, 1, ... up to the piece that reached the
-// block's end out as the block's records; the emit kernels of lz4_seq_device.inl run unchanged behind it.
-// A piece whose search runs past its end simply goes on to the next post-match state (or the block's end): the worst case is one
-// exact walk of the rest of the block, as with one wave per block.
+// The rounds, the parity of the exit states, the P-rounds argument, what a piece keeps and the gather: lz4_pieces_device.inl.  Here:
+// the level-1 flavour of that protocol (a guessed state is every slot "position 0"), and what blocks with history need around it.
 //
 // Blocks with history outside the block (kExt: linked blocks, blocks under a dictionary context -- LZ4_compress_fast_continue as
 // wave_encode_block_ext plays it) take the same rounds.  For the encoder they are no chain: block i needs the last <= 64 KiB of
@@ -34,126 +25,75 @@
 // are not this path's: they get an empty parse here and wave_encode_block_dict behind the emit stage.
 #pragma once
 #include "lz4_seq_device.inl"
+#include "lz4_pieces_device.inl"
 
 namespace plz4 {
 
 enum : int { kFxTab = kHashBytes / 4, kFxMinLen = k64KLimit };
 
-// per piece; fields [r & 1] belong to the round that wrote them
-struct FxPiece {
-    int32_t inAnchor;          // the entry state the records are from (-1: none)
-    int32_t nseq, fin, lastAnchor;      // last run: records, reached the block's end, where its last literals start
-    int32_t runs, lastRound;
-    int32_t ran[2], outAnchor[2], outFin[2];
+// The level-1 flavour of piece_round (lz4_pieces_device.inl).  A state: the 4 Ki-slot table.  kExt: src = the block (its segment in
+// front of it, piece 0's entry table in tabIn: fxl_prep), bs = liblz4's index of its first byte; such a block always has a piece 0.
+template <bool kExt = false> struct FxFlavour {
+    enum : int { kTab = kFxTab };
+    static constexpr bool kPiece0 = kExt;
+    typedef FxRun Run;
+    uint32_t* lds;             // 16 KiB owned by the wave
+    int bs;
+    DEVM int base() const { return kExt ? bs : 0; }
+    DEVM bool guessed(int p0) const { return p0 >= base() + 64; }
+    // two states at one anchor: same live entries (dead ones never matter again).  kExt: the flavour's shift, anchor = its index.
+    static DEVM bool same_state(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B, int anchor)
+    {
+        LV(int, bad);
+        LANES({
+            int b = 0;
+            for (int i = LANE; i < kFxTab; i += 64) {
+                const uint32_t x = A[i], y = B[i];
+                const bool lx = (x >> (kExt ? 9 : 10)) + kMaxDist >= (uint32_t)anchor, ly = (y >> (kExt ? 9 : 10)) + kMaxDist >= (uint32_t)anchor;
+                b |= (int)((lx != ly) | (lx & (x != y)));
+            }
+            bad[I_] = b;
+        })
+        return BALLOT(bad[I_] != 0) == 0;
+    }
+    DEVM void arm(FxRun& run, uint32_t* myOut) const { run.entryTab = nullptr; run.outTab = myOut; run.bs = base(); }
+    DEVM void from_start(FxRun& run, uint32_t* tabIn) const
+    {
+        // the block's start: the table liblz4 starts it with.  (The pointer is said to be wave-uniform: as one of three values that
+        // meet at the parser's "is there a table" question, the compiler otherwise keeps it in vector registers and fails on that question.)
+        if (kExt && run.entryAnchor < 0) run.entryTab = (const uint32_t*)(uintptr_t)UNI((uint64_t)(uintptr_t)tabIn);
+    }
+    DEVM void enter(FxRun& run, const uint32_t* T, uint32_t* myIn, uint32_t*) const
+    {
+        run.entryTab = T;
+        LANES({ for (int i = LANE; i < kFxTab; i += 64) myIn[i] = T[i]; })
+    }
+    DEVM int walk(const uint8_t* __restrict__ src, int n, uint64_t* rec, int, int* lastAnchor, FxRun& run, uint32_t*) const
+    {
+        const int ns = wave_parse_l1_tt<false, 2, true, kExt>(src - base(), base() + n, lds, rec, lastAnchor, nullptr, &run);
+        if (kExt && n < kMinLength) run.fin = 1;                         // (no parse at all: the block is its last literals)
+        return ns;
+    }
 };
 
-DEV int fx_pieces(int n, int pb) { return (n + pb - 1) / pb; }
-template <bool kExt> DEV int fx_pieces_of(int n, int pb) { return kExt ? max_(fx_pieces(n, pb), 1) : fx_pieces(n, pb); }
-// records a piece has room for (+ the dump entry): those of its own bytes, one that crosses its end, a batch of warm-up records
-static inline int fx_rec_stride_host(int pb) { return ((pb / 4 + 80) + 7) & ~7; }
-
-// two states at one anchor: same live entries (dead ones never matter again).  kExt: the flavour's shift, anchor = its index.
-template <bool kExt = false>
-DEV bool fx_same_state(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B, int anchor)
-{
-    LV(int, bad);
-    LANES({
-        int b = 0;
-        for (int i = LANE; i < kFxTab; i += 64) {
-            const uint32_t x = A[i], y = B[i];
-            const bool lx = (x >> (kExt ? 9 : 10)) + kMaxDist >= (uint32_t)anchor, ly = (y >> (kExt ? 9 : 10)) + kMaxDist >= (uint32_t)anchor;
-            b |= (int)((lx != ly) | (lx & (x != y)));
-        }
-        bad[I_] = b;
-    })
-    return BALLOT(bad[I_] != 0) == 0;
-}
-
-// One wave: piece k of a block of n bytes in round `round` (1, 2, ...).  meta / tabIn: P entries of the block; tabOut: 2 x P
-// tables (parity major); rec: P x recStride records.  Returns 1 when it parsed.
-// kExt: src = the block (its segment in front of it, piece 0's entry table in tabIn: fxl_prep), bs = liblz4's index of its first byte.
+// The flavour's round and gather by their earlier names and argument lists (kept for one revision only: the emulation sources of the revision before this
+// one call them, and they are built against this tree whenever that revision's tests are run on it; nothing in this tree uses them --
+// delete them with the next change)
+typedef PieceMeta FxPiece;
+DEV int fx_pieces(int n, int pb) { return piece_count<false>(n, pb); }
+template <bool kExt> DEV int fx_pieces_of(int n, int pb) { return piece_count<kExt>(n, pb); }
+static inline int fx_rec_stride_host(int pb) { return piece_rec_stride(pb); }
 template <bool kExt = false>
 DEV int fx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int pb, int warm, FxPiece* meta, uint32_t* tabIn, uint32_t* tabOut,
                  uint64_t* rec, int recStride, uint32_t* lds, const int bs = 0)
 {
-    const int P = fx_pieces_of<kExt>(n, pb);
-    if (k >= P) return 0;
-    const int par = round & 1, start = bs + k * pb, nEnd = bs + n;
-    FxPiece* const me = meta + k;
-    uint32_t* const myIn = tabIn + (int64_t)k * kFxTab;
-    FxRun run;
-    run.entryAnchor = -1; run.entryTab = nullptr; run.cp = -1; run.cpTab = myIn; run.cpAnchor = -1;
-    run.end = min_(nEnd, start + pb); run.outTab = tabOut + ((int64_t)par * P + k) * kFxTab; run.outAnchor = -1;
-    run.seqCap = recStride - 1; run.fin = 0; run.bs = bs;
-    if (round == 1) {
-        if (k > 0) {
-            run.cp = start;
-            const int p0 = start - warm;
-            if (p0 >= bs + 64) run.entryAnchor = p0;                 // (else from the block's start: exact)
-        }
-        // the block's start: the table liblz4 starts it with.  (The pointer is said to be wave-uniform: as one of three values that
-        // meet at the parser's "is there a table" question, the compiler otherwise keeps it in vector registers and fails on that question.)
-        if (kExt && run.entryAnchor < 0) run.entryTab = (const uint32_t*)(uintptr_t)UNI((uint64_t)(uintptr_t)tabIn);
-    } else {
-        bool go = false;
-        if (k > 0 && meta[k - 1].ran[par ^ 1] && !meta[k - 1].outFin[par ^ 1]) {
-            const int a = meta[k - 1].outAnchor[par ^ 1];
-            const uint32_t* T = tabOut + ((int64_t)(par ^ 1) * P + k - 1) * kFxTab;
-            if (a != me->inAnchor || !fx_same_state<kExt>(T, myIn, a)) {
-                go = true;
-                run.entryAnchor = a; run.entryTab = T;
-                LANES({ for (int i = LANE; i < kFxTab; i += 64) myIn[i] = T[i]; })
-            }
-        }
-        if (!go) {
-            LANES({ if (LANE == 0) me->ran[par] = 0; })
-            return 0;
-        }
-    }
-    int lastAnchor = 0;
-    const int ns = wave_parse_l1_tt<false, 2, true, kExt>(src - bs, nEnd, lds, rec + (int64_t)k * recStride, &lastAnchor, nullptr, &run);
-    if (kExt && n < kMinLength) run.fin = 1;                         // (no parse at all: the block is its last literals)
-    const int inA = round == 1 ? (k > 0 ? run.cpAnchor : bs) : run.entryAnchor;
-    const int runs = round == 1 ? 1 : me->runs + 1;
-    WAVE_FENCE();
-    LANES({
-        if (LANE == 0) {
-            me->inAnchor = inA; me->nseq = ns; me->fin = run.fin; me->lastAnchor = lastAnchor;
-            me->runs = runs; me->lastRound = round;
-            me->ran[par] = 1; me->outAnchor[par] = run.outAnchor; me->outFin[par] = run.fin;
-        }
-    })
-    return 1;
+    return piece_round(FxFlavour<kExt>{lds, bs}, src, n, k, round, pb, warm, meta, tabIn, tabOut, rec, recStride);
 }
-
-// One wave: piece k's records into the block's record array, if the block's chain reaches it; the piece that reached the block's
-// end writes the block's SeqInfo.  Returns 0: not in the chain, 1: in it, 2: the last of it.  (Counts beyond the room of a piece
-// or of the block cannot come out of an exact parse; they would fail the block -- kSeqEngineFailed -- rather than be written.)
 template <bool kExt = false>
 DEV int fx_gather(int n, int k, int pb, const FxPiece* __restrict__ meta, const uint64_t* __restrict__ rec, int recStride,
                   uint64_t* __restrict__ seq, int seqCap, SeqInfo* info)
 {
-    const int P = fx_pieces_of<kExt>(n, pb);
-    if (k >= P) return 0;
-    int off = 0;
-    bool over = false;
-    for (int j0 = 0; j0 < k; j0 += 64) {
-        LV(int, c); LV(int, f);
-        LANES({ const int j = j0 + LANE; c[I_] = j < k ? meta[j].nseq : 0; f[I_] = j < k ? meta[j].fin : 0; })
-        if (BALLOT(f[I_] != 0)) return 0;
-        over |= BALLOT(c[I_] >= recStride) != 0;
-        SCAN_INCL(c);
-        off += RL(c, 63);
-    }
-    const int ns = meta[k].nseq, fin = meta[k].fin;
-    const bool room = !over && ns < recStride && off + ns <= seqCap;
-    const uint64_t* r = rec + (int64_t)k * recStride;
-    if (room) LANES({ for (int j = LANE; j < ns; j += 64) seq[off + j] = r[j]; })
-    if (fin) {
-        const int la = meta[k].lastAnchor;
-        LANES({ if (LANE == 0) { SeqInfo inf; inf.nseq = room ? off + ns : kSeqEngineFailed; inf.lastAnchor = la; inf.total = 0; inf.stored = 0; *info = inf; } })
-    }
-    return fin ? 2 : 1;
+    return piece_gather<kExt>(n, k, pb, meta, rec, recStride, seq, seqCap, info);
 }
 
 // ---- blocks with history outside the block

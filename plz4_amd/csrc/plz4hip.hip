@@ -212,44 +212,6 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_l1_parse(CodecArgs 
     l1_parse_loop<2>(a, lds);                  // (ten tables fill the CU's LDS: the windows through the lane exchange, lz4_seq_device.inl)
 }
 
-// ---- the level-1 parse of a few blocks cut across the chip (lz4_fx_device.inl): grid (pieces, blocks of the group), one wave each,
-// one launch per round, then the gather into the staged path's records (l1Seq / l1Info) -- the emit kernels below run unchanged.
-// Workspace per block: P pieces x (meta, entry table, two exit tables, records).  cnt: the ctx's counters (plz4hip_ctx_counters).
-struct FxArgs { FxPiece* meta; uint32_t* tabIn; uint32_t* tabOut; uint64_t* rec; int P, pb, warm, recStride; unsigned long long* cnt; };
-__global__ __launch_bounds__(64) void k_fx_piece(CodecArgs a, FxArgs f, int round)
-{
-    __shared__ uint32_t lds[kHashBytes / 4];
-    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
-    const int n = block_len(a, gi);
-    if (n < kFxMinLen || n > a.l1MaxLen) {
-        // outside the path's scope (byU16 blocks, lengths the workspace was not sized for): the block as k_l1_parse does it
-        if (round != 1 || k != 0) return;
-        int lastAnchor = 0, nseq = -1;
-        if (n >= 0 && n <= a.l1MaxLen) nseq = wave_parse_l1<2>(a.src + (int64_t)gi * a.srcStride, n, lds, a.l1Seq + (int64_t)i * a.l1SeqStride, &lastAnchor);
-        if ((threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = nseq; inf.lastAnchor = lastAnchor; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
-        return;
-    }
-    const int64_t pb0 = (int64_t)i * f.P;
-    fx_piece(a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * kFxTab, f.tabOut + pb0 * 2 * kFxTab,
-             f.rec + pb0 * f.recStride, f.recStride, lds);
-}
-__global__ __launch_bounds__(64) void k_fx_gather(CodecArgs a, FxArgs f)
-{
-    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
-    const int n = block_len(a, gi);
-    if (n < kFxMinLen || n > a.l1MaxLen || k >= fx_pieces(n, f.pb)) return;
-    const int64_t pb0 = (int64_t)i * f.P;
-    const FxPiece* m = f.meta + pb0;
-    const int g = fx_gather(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
-                          (int)a.l1SeqStride - 1, a.l1Info + i);
-    if ((threadIdx.x & 63u) == 0) {
-        atomicMax(&f.cnt[1], (unsigned long long)m[k].lastRound);
-        if (m[k].runs > 1) atomicAdd(&f.cnt[2], 1ull);
-        if (g == 2) atomicAdd(&f.cnt[0], 1ull);
-    }
-}
-__global__ __launch_bounds__(64) void k_fx_begin(unsigned long long* cnt) { if (threadIdx.x == 0) cnt[1] = 0; }
-
 // grid (waves per block / 4, blocks of the group): bytes of every chunk of 1024 sequences.  kBack: the level-1 parser's records
 // (their catch-up is measured here); false: the HC parsers' records, which carry the final match.
 // (kSeg / xb: blocks with an external segment in front of them, k_fxl_sizes / k_fxl_write below)
@@ -451,8 +413,90 @@ __device__ __forceinline__ DictEnc fxl_dict_of(const CodecArgs& a, int i, int n)
     }
     return dc;
 }
+// ---- the parse of a few blocks cut across the chip (lz4_pieces_device.inl): grid (pieces, blocks of the group), one wave each,
+// one launch per round, then the gather into the staged path's records (l1Seq / l1Info) -- the emit kernels run unchanged behind it.
+// Workspace per piece: meta, entry state, two exit states, records (PieceLayout).  cnt: the ctx's counters (plz4hip_ctx_counters).
+struct PieceArgs { PieceMeta* meta; uint32_t* tabIn; uint32_t* tabOut; uint64_t* rec; int P, pb, warm, recStride; unsigned long long* cnt; };
+
+// A flavour at kernel level: the device flavour F, whether the wave needs the 16 KiB LDS table, whether the blocks have an FxlBlk
+// (k_fxl_prep in front), the counters it bumps (blocks, rounds of the last call, pieces parsed again; kBlocksToo: a second block
+// counter or -1), which blocks are the path's and what a block that is not gets as its result (round 1, piece 0).
+struct KFx {                   // level 1, independent blocks (lz4_fx_device.inl)
+    typedef FxFlavour<false> F;
+    enum : int { kLds = 1, kHist = 0, kBlocks = 0, kRounds = 1, kAgain = 2, kBlocksToo = -1 };
+    static DEVM F flavour(const FxlBlk&, uint32_t* lds) { return F{lds, 0}; }
+    static DEVM bool in_scope(const CodecArgs& a, int n, const FxlBlk&) { return n >= kFxMinLen && n <= a.l1MaxLen; }
+    // byU16 blocks, lengths the workspace was not sized for: the block as k_l1_parse does it
+    static DEVM int outside(const CodecArgs& a, int n, int i, int gi, const FxlBlk&, uint32_t* lds, int* lastAnchor)
+    {
+        if (n < 0 || n > a.l1MaxLen) return -1;
+        return wave_parse_l1<2>(a.src + (int64_t)gi * a.srcStride, n, lds, a.l1Seq + (int64_t)i * a.l1SeqStride, lastAnchor);
+    }
+};
+struct KFxl {                  // level 1, history outside the block (the kExt flavour)
+    typedef FxFlavour<true> F;
+    enum : int { kLds = 1, kHist = 1, kBlocks = 0, kRounds = 1, kAgain = 2, kBlocksToo = 7 };
+    static DEVM F flavour(const FxlBlk& b, uint32_t* lds) { return F{lds, b.bs}; }
+    static DEVM bool in_scope(const CodecArgs&, int, const FxlBlk& b) { return b.pfx >= 0; }
+    // not this path's: an empty parse (k_fxl_small writes the block behind the emit stage), or no result (-1, as k_l1_parse says it)
+    static DEVM int outside(const CodecArgs&, int, int, int, const FxlBlk& b, uint32_t*, int*) { return b.pfx == -1 ? 0 : -1; }
+};
+struct KMx {                   // level 2, independent blocks (lz4_mx_device.inl): no LDS
+    typedef MxFlavour F;
+    enum : int { kLds = 0, kHist = 0, kBlocks = 13, kRounds = 14, kAgain = 15, kBlocksToo = -1 };
+    static DEVM F flavour(const FxlBlk&, uint32_t*) { return F{}; }
+    static DEVM bool in_scope(const CodecArgs& a, int n, const FxlBlk&) { return n >= 0 && n <= a.l1MaxLen; }
+    // a block the workspace was not sized for: no result, as k_hc_mid says it
+    static DEVM int outside(const CodecArgs&, int, int, int, const FxlBlk&, uint32_t*, int*) { return -1; }
+};
+
+template <class K> __device__ __forceinline__ void piece_body(const CodecArgs& a, const PieceArgs& f, const FxlBlk* xb, int round, uint32_t* lds)
+{
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    FxlBlk b; b.pfx = 0; b.bs = 0;
+    if (K::kHist) b = xb[i];                                                 // (loaded before anything is stored: scalar loads)
+    if (!K::in_scope(a, n, b)) {
+        if (round != 1 || k != 0) return;
+        int lastAnchor = 0;
+        const int nseq = K::outside(a, n, i, gi, b, lds, &lastAnchor);
+        if ((threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = nseq; inf.lastAnchor = lastAnchor; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
+        return;
+    }
+    typedef typename K::F F;
+    const int64_t pb0 = (int64_t)i * f.P;
+    piece_round(K::flavour(b, lds), a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * F::kTab,
+                f.tabOut + pb0 * 2 * F::kTab, f.rec + pb0 * f.recStride, f.recStride);
+}
+template <class K> __global__ __launch_bounds__(64) void k_piece(CodecArgs a, PieceArgs f, const FxlBlk* xb, int round)
+{
+    if constexpr (K::kLds != 0) {
+        __shared__ uint32_t lds[kHashBytes / 4];
+        piece_body<K>(a, f, xb, round, lds);
+    } else piece_body<K>(a, f, xb, round, nullptr);
+}
+template <class K> __global__ __launch_bounds__(64) void k_piece_gather(CodecArgs a, PieceArgs f, const FxlBlk* xb)
+{
+    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
+    const int n = block_len(a, gi);
+    FxlBlk b; b.pfx = 0; b.bs = 0;
+    if (K::kHist) b = xb[i];
+    if (!K::in_scope(a, n, b) || k >= piece_count<K::F::kPiece0>(n, f.pb)) return;
+    const int64_t pb0 = (int64_t)i * f.P;
+    const PieceMeta* m = f.meta + pb0;
+    const int g = piece_gather<K::F::kPiece0>(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
+                                             (int)a.l1SeqStride - 1, a.l1Info + i);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicMax(&f.cnt[K::kRounds], (unsigned long long)m[k].lastRound);
+        if (m[k].runs > 1) atomicAdd(&f.cnt[K::kAgain], 1ull);
+        if (g == 2) { atomicAdd(&f.cnt[K::kBlocks], 1ull); if (K::kBlocksToo >= 0) atomicAdd(&f.cnt[K::kBlocksToo], 1ull); }
+    }
+}
+// in front of a call's first round: the "rounds of the last call" counter starts over
+__global__ __launch_bounds__(64) void k_piece_begin(unsigned long long* cnt, int index) { if (threadIdx.x == 0) cnt[index] = 0; }
+
 // grid (blocks of the group), one wave each: the segment in front of the block, piece 0's entry table, the block's FxlBlk
-__global__ __launch_bounds__(64) void k_fxl_prep(CodecArgs a, FxArgs f, FxlBlk* xb)
+__global__ __launch_bounds__(64) void k_fxl_prep(CodecArgs a, PieceArgs f, FxlBlk* xb)
 {
     __shared__ uint32_t lds[kHashBytes / 4];
     const int i = blockIdx.x, gi = a.blk0 + i;
@@ -464,35 +508,6 @@ __global__ __launch_bounds__(64) void k_fxl_prep(CodecArgs a, FxArgs f, FxlBlk* 
                      f.tabIn + (int64_t)i * f.P * kFxTab, lds);
     }
     if ((threadIdx.x & 63u) == 0) xb[i] = b;
-}
-__global__ __launch_bounds__(64) void k_fxl_piece(CodecArgs a, FxArgs f, const FxlBlk* xb, int round)
-{
-    __shared__ uint32_t lds[kHashBytes / 4];
-    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
-    const int n = block_len(a, gi), pfx = xb[i].pfx, bs = xb[i].bs;          // (loaded before anything is stored: scalar loads)
-    if (pfx < 0) {
-        // not this path's: an empty parse (k_fxl_small writes the block behind the emit stage), or no result (-1, as k_l1_parse says it)
-        if (round == 1 && k == 0 && (threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = pfx == -1 ? 0 : -1; inf.lastAnchor = 0; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
-        return;
-    }
-    const int64_t pb0 = (int64_t)i * f.P;
-    fx_piece<true>(a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * kFxTab, f.tabOut + pb0 * 2 * kFxTab,
-                   f.rec + pb0 * f.recStride, f.recStride, lds, bs);
-}
-__global__ __launch_bounds__(64) void k_fxl_gather(CodecArgs a, FxArgs f, const FxlBlk* xb)
-{
-    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
-    const int n = block_len(a, gi);
-    if (xb[i].pfx < 0 || k >= fx_pieces_of<true>(n, f.pb)) return;
-    const int64_t pb0 = (int64_t)i * f.P;
-    const FxPiece* m = f.meta + pb0;
-    const int g = fx_gather<true>(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
-                                (int)a.l1SeqStride - 1, a.l1Info + i);
-    if ((threadIdx.x & 63u) == 0) {
-        atomicMax(&f.cnt[1], (unsigned long long)m[k].lastRound);
-        if (m[k].runs > 1) atomicAdd(&f.cnt[2], 1ull);
-        if (g == 2) { atomicAdd(&f.cnt[0], 1ull); atomicAdd(&f.cnt[7], 1ull); }
-    }
 }
 __global__ __launch_bounds__(256) void k_fxl_sizes(CodecArgs a, const FxlBlk* xb) { l1_sizes_body<true, true>(a, xb); }
 __global__ __launch_bounds__(256) void k_fxl_write(CodecArgs a, const FxlBlk* xb) { l1_write_body<true, true>(a, xb); }
@@ -544,7 +559,7 @@ __global__ __launch_bounds__(64) void k_fxl_small(CodecArgs a)
 // of the kExt parser (l1x_block, lz4_fx_device.inl): the segment in front of the block (copied only where it does not lie there
 // already), the starting table built in the wave's own LDS table, the records into the level-1 workspace; xb[i] tells the kSeg emit
 // stage (k_fxl_sizes / k_fxl_write) the segment's bytes.  W waves per workgroup, each with its own 16 KiB table, never synchronised
-// (ENC_WAVE_TABLE): a whole-block run has none of the piece flow's live state (k_fxl_piece: 256 VGPRs + 94 AGPRs, one wave per SIMD)
+// (ENC_WAVE_TABLE): a whole-block run has none of the piece flow's live state (k_piece<KFxl>: 256 VGPRs + 92 AGPRs, one wave per SIMD)
 // and fits the register budget of ten waves per CU (W = 10: 85 VGPRs, no AGPRs, no scratch), so the LDS tables are what bounds it,
 // as with k_l1_parse.
 template <int W> __global__ __launch_bounds__(64 * W) void k_l1x_parse(CodecArgs a, FxlBlk* xb, unsigned long long* cnt)
@@ -1222,39 +1237,6 @@ template <bool kD> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_
         if ((threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = nseq; inf.lastAnchor = lastAnchor; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
     }
 }
-
-// ---- level 2 on a few independent blocks cut across the chip (lz4_mx_device.inl): grid (pieces, blocks of the group), one wave each,
-// one launch per round, then the gather into the staged path's records (l1Seq / l1Info) -- launch_emit(Emit::Mid) runs unchanged.
-// Workspace per piece: meta, entry state, two exit states (a piece walks inside its exit slot), records.  cnt: plz4hip_ctx_counters.
-struct MxArgs { FxPiece* meta; uint32_t* tabIn; uint32_t* tabOut; uint64_t* rec; int P, pb, warm, recStride; unsigned long long* cnt; };
-__global__ __launch_bounds__(64) void k_mx_piece(CodecArgs a, MxArgs f, int round)
-{
-    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
-    const int n = block_len(a, gi);
-    if (n < 0 || n > a.l1MaxLen) {                                           // a block the workspace was not sized for: no result, as k_hc_mid says it
-        if (round == 1 && k == 0 && (threadIdx.x & 63u) == 0) { SeqInfo inf; inf.nseq = -1; inf.lastAnchor = 0; inf.total = 0; inf.stored = 0; a.l1Info[i] = inf; }
-        return;
-    }
-    const int64_t pb0 = (int64_t)i * f.P;
-    mx_piece(a.src + (int64_t)gi * a.srcStride, n, k, round, f.pb, f.warm, f.meta + pb0, f.tabIn + pb0 * kMxTab, f.tabOut + pb0 * 2 * kMxTab,
-             f.rec + pb0 * f.recStride, f.recStride);
-}
-__global__ __launch_bounds__(64) void k_mx_gather(CodecArgs a, MxArgs f)
-{
-    const int k = blockIdx.x, i = blockIdx.y, gi = a.blk0 + i;
-    const int n = block_len(a, gi);
-    if (n < 0 || n > a.l1MaxLen || k >= mx_pieces(n, f.pb)) return;
-    const int64_t pb0 = (int64_t)i * f.P;
-    const FxPiece* m = f.meta + pb0;
-    const int g = mx_gather(n, k, f.pb, m, f.rec + pb0 * f.recStride, f.recStride, a.l1Seq + (int64_t)i * a.l1SeqStride,
-                            (int)a.l1SeqStride - 1, a.l1Info + i);
-    if ((threadIdx.x & 63u) == 0) {
-        atomicMax(&f.cnt[14], (unsigned long long)m[k].lastRound);
-        if (m[k].runs > 1) atomicAdd(&f.cnt[15], 1ull);
-        if (g == 2) atomicAdd(&f.cnt[13], 1ull);
-    }
-}
-__global__ __launch_bounds__(64) void k_mx_begin(unsigned long long* cnt) { if (threadIdx.x == 0) cnt[14] = 0; }
 
 // clz4.NewDictCtxHC (clz4.go:122-147): workgroup 0 builds the level-2 (lz4mid) tables of a dictionary, workgroup 1 the
 // hash-chain tables every other level shares.  tabs = 2 x kHcWorkBytes.
@@ -2376,7 +2358,7 @@ int launch_hc_body(plz4hip_ctx* c, hipStream_t s, const HcSwitches& sw, CodecArg
     return p.route == HcRoute::Segmented ? hc_segmented(k, sw, p, a, forked) : hc_one_thread(k, sw, p, a);
 }
 
-// The pointers of a level-1 group workspace (L1Layout) and of the few-block parse's (FxLayout; returns the blocks' FxlBlk array)
+// The pointers of a level-1 group workspace (L1Layout) and of a few-block parse's (PieceLayout; returns the blocks' FxlBlk array)
 void bind_l1(CodecArgs& a, uint8_t* base, const L1Layout& L)
 {
     a.l1SeqStride = (int64_t)L.seqStride; a.l1MaxChunks = L.maxChunks;
@@ -2384,16 +2366,21 @@ void bind_l1(CodecArgs& a, uint8_t* base, const L1Layout& L)
     a.l1ChunkBytes = (uint32_t*)(base + L.offChunkBytes); a.l1ChunkOff = (uint32_t*)(base + L.offChunkOff);
     a.l1Seq = (uint64_t*)(base + L.offSeq); a.l1Bk = base + L.offBk;
 }
-FxlBlk* bind_fx(FxArgs& fx, uint8_t* base, const FxLayout& F, bool hist)
+FxlBlk* bind_pieces(PieceArgs& pc, uint8_t* base, const PieceLayout& L, bool hist)
 {
-    fx.meta = (FxPiece*)(base + F.offMeta); fx.tabIn = (uint32_t*)(base + F.offIn); fx.tabOut = (uint32_t*)(base + F.offOut);
-    fx.rec = (uint64_t*)(base + F.offRec);
-    return hist ? (FxlBlk*)(base + F.offBlk) : nullptr;
+    pc.meta = (PieceMeta*)(base + L.offMeta); pc.tabIn = (uint32_t*)(base + L.offIn); pc.tabOut = (uint32_t*)(base + L.offOut);
+    pc.rec = (uint64_t*)(base + L.offRec);
+    return hist ? (FxlBlk*)(base + L.offBlk) : nullptr;
 }
-void bind_mx(MxArgs& mx, uint8_t* base, const MxLayout& M)
+// The rounds of one group of a few-block call and the gather behind them (K: KFx, KFxl, KMx).  P rounds are always enough
+// (lz4_pieces_device.inl); the rounds after the last change find nothing to do.  first: the call's first group.
+template <class K> void launch_piece_rounds(hipStream_t s, const CodecArgs& a, const PieceArgs& pc, FxlBlk* xb, int ng, bool first)
 {
-    mx.meta = (FxPiece*)(base + M.offMeta); mx.tabIn = (uint32_t*)(base + M.offIn); mx.tabOut = (uint32_t*)(base + M.offOut);
-    mx.rec = (uint64_t*)(base + M.offRec);
+    if (first) hipLaunchKernelGGL(k_piece_begin, dim3(1), dim3(64), 0, s, pc.cnt, (int)K::kRounds);
+    // (every block reads block gi - 1's plaintext tail out of the call's input, whichever group that block is in)
+    if (K::kHist) hipLaunchKernelGGL(k_fxl_prep, dim3(ng), dim3(64), 0, s, a, pc, xb);
+    for (int r = 1; r <= pc.P; ++r) hipLaunchKernelGGL(k_piece<K>, dim3(pc.P, ng), dim3(64), 0, s, a, pc, (const FxlBlk*)xb, r);
+    hipLaunchKernelGGL(k_piece_gather<K>, dim3(pc.P, ng), dim3(64), 0, s, a, pc, (const FxlBlk*)xb);
 }
 
 // Which of the ctx's level-1 workspaces a call on s takes: the one this stream used last; else one whose last job is over (no second
@@ -2499,37 +2486,32 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
             fprintf(stderr, "plz4hip: level 1, %d blocks of <= %d: free %zu MiB, workspace %zu MiB, groups of %d%s\n", nb, maxLen, freeB >> 20, ws->bytes >> 20, per, granted ? "" : " (fused)");
     }
     // from here on the jobs are marked behind whatever was enqueued, whichever way the call ends
-    MarkOnExit job, fxJob, mxJob;
-    FxArgs fx{};
-    MxArgs mx{};
-    bool mxGranted = false;
+    MarkOnExit job, pcJob;
+    PieceArgs pc{};
+    bool pcGranted = false;                                                     // the pieces' workspace of this call (c->fx, or c->mx for level 2)
     FxlBlk* xb = nullptr;                                                       // hist: per block of a group, its segment (k_fxl_prep)
     L1Layout L{};
-    bool fxGranted = false;
     if (granted) {
         if (order) { HIPCHK(c, order->wait(s)); job.arm(*order, s); }
         L = l1_layout(per, maxLen, l1x);
         a.l1MaxLen = maxLen;
         bind_l1(a, ws->d, L);
-        if (want.fx) {
-            // the few-block parse's workspace is sized per call (a group of `per` blocks); when it cannot be had, the call parses as the others
-            fx.pb = want.piece; fx.warm = want.warm; fx.P = want.P; fx.recStride = fx_rec_stride_host(fx.pb); fx.cnt = c->d_counters;
-            const FxLayout F = fx_layout(per, fx.P, fx.recStride, hist);
-            HIPCHK(c, c->fxOrder.wait(s));
-            bool refused = false;  HIPCHK(c, c->fx.reserve(F.total, c->fxOrder, &refused));
-            if (!refused) { xb = bind_fx(fx, c->fx.d, F, hist); fxGranted = true; fxJob.arm(c->fxOrder, s); }
-        }
-        if (mxWant.mx) {
-            // likewise the few-block level-2 walk's; when it cannot be had, the call walks one wave per block (k_hc_mid): same bytes
-            mx.pb = mxWant.piece; mx.warm = mxWant.warm; mx.P = mxWant.P; mx.recStride = mx_rec_stride_host(mx.pb); mx.cnt = c->d_counters;
-            const MxLayout M = mx_layout(per, mx.P, mx.recStride);
-            HIPCHK(c, c->mxOrder.wait(s));
-            bool refused = false;  HIPCHK(c, c->mx.reserve(M.total, c->mxOrder, &refused));
-            if (!refused) { bind_mx(mx, c->mx.d, M); mxGranted = true; mxJob.arm(c->mxOrder, s); }
+        const PieceCut cut = mid ? mxWant.cut() : want.cut();
+        if (cut.on) {
+            // a few-block parse's workspace is sized per call (a group of `per` blocks); when it cannot be had, the call parses as the
+            // others: level 1 on the ordinary parse, level 2 one wave per block (k_hc_mid) -- same bytes
+            DeviceBuffer& buf = mid ? c->mx : c->fx;
+            StreamOrder& ord = mid ? c->mxOrder : c->fxOrder;
+            pc.pb = cut.piece; pc.warm = cut.warm; pc.P = cut.P; pc.recStride = piece_rec_stride(pc.pb); pc.cnt = c->d_counters;
+            const bool blk = hist && !mid;                                      // (level 2's pieces never carry an FxlBlk array)
+            const PieceLayout PL = piece_layout(per, pc.P, pc.recStride, mid ? kMxTab : kFxTab, blk);
+            HIPCHK(c, ord.wait(s));
+            bool refused = false;  HIPCHK(c, buf.reserve(PL.total, ord, &refused));
+            if (!refused) { xb = bind_pieces(pc, buf.d, PL, blk); pcGranted = true; pcJob.arm(ord, s); }
         }
     }
-    const L1Route route = l1_route(shape, sw, want, granted, fxGranted);
-    const bool mxOn = route == L1Route::Mid && mx_route(mxWant, granted, mxGranted);
+    const L1Route route = l1_route(shape, sw, want, granted, pcGranted);
+    const bool mxOn = route == L1Route::Mid && mx_route(mxWant, granted, pcGranted);
     switch (route) {
     case L1Route::NoMemBody:
         return fail(c, PLZ4HIP_E_NOMEM, "records straight into a frame body need the staged call's workspace (blocks up to 4 MiB)");
@@ -2543,8 +2525,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         if (route == L1Route::Fused && rider) { launch_rec_verify(s, *rider); hipLaunchKernelGGL(k_decode_rec, dim3(grid_for(rider->nBlocks, c->decWaves)), dim3(64), 0, s, *rider); }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, job.leave());
-        HIPCHK(c, fxJob.leave());
-        HIPCHK(c, mxJob.leave());
+        HIPCHK(c, pcJob.leave());
         return PLZ4HIP_OK;
     default: break;
     }
@@ -2561,27 +2542,11 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         } else if (route == L1Route::Mid) c->gatePending = false;
         switch (route) {
         case L1Route::Mid:
-            if (mxOn) {                                                          // P rounds are always enough, as on the Fx route
-                if (g0 == 0) hipLaunchKernelGGL(k_mx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
-                for (int r = 1; r <= mx.P; ++r) hipLaunchKernelGGL(k_mx_piece, dim3(mx.P, ng), dim3(64), 0, s, a, mx, r);
-                hipLaunchKernelGGL(k_mx_gather, dim3(mx.P, ng), dim3(64), 0, s, a, mx);
-                break;
-            }
-            hipLaunchKernelGGL(hc_mid_kernel(a.hcPfx != nullptr), dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
+            if (mxOn) launch_piece_rounds<KMx>(s, a, pc, xb, ng, g0 == 0);
+            else hipLaunchKernelGGL(hc_mid_kernel(a.hcPfx != nullptr), dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
             break;
-        case L1Route::Fxl:
-            // (every block reads block gi - 1's plaintext tail out of the call's input, whichever group that block is in)
-            if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
-            hipLaunchKernelGGL(k_fxl_prep, dim3(ng), dim3(64), 0, s, a, fx, xb);
-            for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fxl_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, (const FxlBlk*)xb, r);
-            hipLaunchKernelGGL(k_fxl_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx, (const FxlBlk*)xb);
-            break;
-        case L1Route::Fx:
-            // P rounds are always enough (lz4_fx_device.inl); the rounds after the last change find nothing to do
-            if (g0 == 0) hipLaunchKernelGGL(k_fx_begin, dim3(1), dim3(64), 0, s, c->d_counters);
-            for (int r = 1; r <= fx.P; ++r) hipLaunchKernelGGL(k_fx_piece, dim3(fx.P, ng), dim3(64), 0, s, a, fx, r);
-            hipLaunchKernelGGL(k_fx_gather, dim3(fx.P, ng), dim3(64), 0, s, a, fx);
-            break;
+        case L1Route::Fxl: launch_piece_rounds<KFxl>(s, a, pc, xb, ng, g0 == 0); break;
+        case L1Route::Fx:  launch_piece_rounds<KFx>(s, a, pc, xb, ng, g0 == 0); break;
         case L1Route::L1x:                                                       // one wave per block, every block one exact run
             ENC_LAUNCH(k_l1x_parse, ng, c, s, a, xb, c->d_counters);
             break;
@@ -2605,8 +2570,7 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, job.leave());
-    HIPCHK(c, fxJob.leave());
-    HIPCHK(c, mxJob.leave());
+    HIPCHK(c, pcJob.leave());
     return PLZ4HIP_OK;
 }
 

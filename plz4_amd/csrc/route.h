@@ -12,6 +12,24 @@ namespace plz4 {
 
 constexpr int kUnset = INT_MIN;            // a switch that is not in the environment, where that differs from every value
 
+// ---------------------------------------------------------------------------------------------------- few-block parses: the cut
+// What a call that takes a few-block parse (lz4_pieces_device.inl) asks for before anything is reserved: pieces of `piece` bytes,
+// guessed starts `warm` bytes early, P pieces per block of maxLen.
+struct PieceCut { bool on; int piece, warm, P; };
+inline PieceCut piece_cut(bool on, int maxLen, int pieceKiB, int warmKiB)
+{
+    PieceCut c{};
+    c.on = on;
+    if (on) { c.piece = pieceKiB << 10; c.warm = warmKiB << 10; c.P = (maxLen + c.piece - 1) / c.piece; }
+    return c;
+}
+// PLZ4HIP_*_PIECE_KIB in 1..4096, PLZ4HIP_*_WARMUP_KIB in 0..4096; anything else leaves the default
+template <class Get> void parse_piece_kib(Get&& get, const char* pieceName, const char* warmName, int* pieceKiB, int* warmKiB)
+{
+    if (const char* v = get(pieceName)) { const int x = (int)atol(v); if (x >= 1 && x <= 4096) *pieceKiB = x; }
+    if (const char* v = get(warmName)) { const int x = (int)atol(v); if (x >= 0 && x <= 4096) *warmKiB = x; }
+}
+
 // ---------------------------------------------------------------------------------------------------- level 1 (launch_l1)
 constexpr int  kFxMaxBlocks = 128;         // PLZ4HIP_FX_MAX_BLOCKS: the few-block level-1 parse up to this many blocks (profiles/fx_rate.json)
 constexpr bool kL1xDefault = true;         // PLZ4HIP_L1X unset: the staged design (profiles/l1x_rate.json)
@@ -43,8 +61,8 @@ inline bool l1x_on(const L1Switches& sw) { return !sw.fused && (sw.l1x == kUnset
 enum class L1Route { Fused, DictKernels, Parse, Duplex, Mid, Fx, Fxl, L1x, MidDeclined, NoMemBody };
 struct L1Shape { int nb, maxLen; bool raw, mid, rider, hist, l1x, body, ctx; };     // ctx: a dictionary context of dictLen >= 8
 // What the call asks for before anything is reserved.  staged: the group workspace (else the fused / dictionary kernels, which need
-// none); fx: the few-block parse in pieces of `piece` bytes, guessed starts `warm` bytes early, P pieces per block.
-struct L1Want { bool staged, fx; int piece, warm, P; };
+// none); fx: the few-block parse, with its cut (piece_cut).
+struct L1Want { bool staged, fx; int piece, warm, P; PieceCut cut() const { return PieceCut{fx, piece, warm, P}; } };
 inline L1Want l1_want(const L1Shape& k, const L1Switches& sw)
 {
     L1Want w{};
@@ -52,8 +70,9 @@ inline L1Want l1_want(const L1Shape& k, const L1Switches& sw)
     const bool fxl = fxl_wanted(sw, k.nb, k.maxLen);
     // history outside the block: staged for the few-block parse, and for the bulk route where the entry point has one
     w.staged = inRange && (!k.hist || fxl || (k.l1x && l1x_on(sw)));
-    w.fx = w.staged && !k.mid && !k.rider && k.nb <= sw.fxMax && k.maxLen >= kFxMinLen && k.maxLen <= kSeqMaxBlock && (!(k.hist || k.l1x) || fxl);
-    if (w.fx) { w.piece = sw.fxPieceKiB << 10; w.warm = sw.fxWarmKiB << 10; w.P = (k.maxLen + w.piece - 1) / w.piece; }
+    const bool fx = w.staged && !k.mid && !k.rider && k.nb <= sw.fxMax && k.maxLen >= kFxMinLen && k.maxLen <= kSeqMaxBlock && (!(k.hist || k.l1x) || fxl);
+    const PieceCut c = piece_cut(fx, k.maxLen, sw.fxPieceKiB, sw.fxWarmKiB);
+    w.fx = c.on; w.piece = c.piece; w.warm = c.warm; w.P = c.P;
     return w;
 }
 // The route, given what was granted: ws -- a group workspace of at least one block; fx -- the few-block parse's own.  Duplex is the
@@ -151,15 +170,14 @@ struct MxSwitches {
     int pieceKiB = 128, warmKiB = 256;     // PLZ4HIP_MX_PIECE_KIB in 1..4096, PLZ4HIP_MX_WARMUP_KIB in 0..4096 (rounds per choice)
 };
 struct MxShape { int level, nb, maxLen; bool hcEx, rider; };
-// What the call asks for before anything is reserved: pieces of `piece` bytes, guessed starts `warm` bytes early, P pieces per block.
-struct MxWant { bool mx; int piece, warm, P; };
+// What the call asks for before anything is reserved: mx -- the walk in pieces, with its cut (piece_cut).
+struct MxWant { bool mx; int piece, warm, P; PieceCut cut() const { return PieceCut{mx, piece, warm, P}; } };
 inline MxWant mx_want(const MxShape& k, const MxSwitches& sw)
 {
-    MxWant w{};
     // (a call whose largest block is one piece has nothing to cut: one wave per block either way, so it keeps today's launch)
-    w.mx = k.level == 2 && !k.hcEx && !k.rider && k.nb >= 1 && k.nb <= sw.maxBlocks && k.maxLen > (sw.pieceKiB << 10) && k.maxLen <= kSeqMaxBlock;
-    if (w.mx) { w.piece = sw.pieceKiB << 10; w.warm = sw.warmKiB << 10; w.P = (k.maxLen + w.piece - 1) / w.piece; }
-    return w;
+    const bool mx = k.level == 2 && !k.hcEx && !k.rider && k.nb >= 1 && k.nb <= sw.maxBlocks && k.maxLen > (sw.pieceKiB << 10) && k.maxLen <= kSeqMaxBlock;
+    const PieceCut c = piece_cut(mx, k.maxLen, sw.pieceKiB, sw.warmKiB);
+    return MxWant{c.on, c.piece, c.warm, c.P};
 }
 // ... and given what was granted: the staged call's group workspace and the pieces' own.  false: today's k_hc_mid launch.
 inline bool mx_route(const MxWant& w, bool stagedGranted, bool mxGranted) { return w.mx && stagedGranted && mxGranted; }
@@ -270,8 +288,7 @@ template <class Get> L1Switches parse_l1_switches(Get&& get)
     sw.fused = get("PLZ4HIP_L1_FUSED") != nullptr;
     sw.fxLinked = (int)num("PLZ4HIP_FX_LINKED", kUnset);
     if (const char* v = get("PLZ4HIP_FX_MAX_BLOCKS")) sw.fxMax = atoi(v);
-    { const int x = (int)num("PLZ4HIP_FX_PIECE_KIB", 0); if (x >= 1 && x <= 4096) sw.fxPieceKiB = x; }
-    { const int x = (int)num("PLZ4HIP_FX_WARMUP_KIB", -1); if (x >= 0 && x <= 4096) sw.fxWarmKiB = x; }
+    parse_piece_kib(get, "PLZ4HIP_FX_PIECE_KIB", "PLZ4HIP_FX_WARMUP_KIB", &sw.fxPieceKiB, &sw.fxWarmKiB);
     sw.l1x = (int)num("PLZ4HIP_L1X", kUnset);
     sw.oneWorkspace = num("PLZ4HIP_L1_WORKSPACES", 0) == 1;
     sw.budgetGiB = num("PLZ4HIP_L1_BUDGET_GIB", 0);
@@ -306,8 +323,7 @@ template <class Get> MxSwitches parse_mx_switches(Get&& get)
     MxSwitches sw;
     sw.maxBlocks = num("PLZ4HIP_MX_MAX_BLOCKS", kMxMaxBlocks);
     if (sw.maxBlocks > 65535) sw.maxBlocks = 65535;                            // (the blocks of a group are the grid's y)
-    { const int x = num("PLZ4HIP_MX_PIECE_KIB", 0); if (x >= 1 && x <= 4096) sw.pieceKiB = x; }
-    { const int x = num("PLZ4HIP_MX_WARMUP_KIB", -1); if (x >= 0 && x <= 4096) sw.warmKiB = x; }
+    parse_piece_kib(get, "PLZ4HIP_MX_PIECE_KIB", "PLZ4HIP_MX_WARMUP_KIB", &sw.pieceKiB, &sw.warmKiB);
     return sw;
 }
 template <class Get> DxSwitches parse_dx_switches(Get&& get)

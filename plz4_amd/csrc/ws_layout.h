@@ -104,39 +104,31 @@ inline L1Layout l1_layout(int per, int maxLen, bool l1x, std::vector<WsTake>* lo
     return L;
 }
 
-// ---------------------------------------------------------------------------------------------------- few-block parse (c->fx)
-// [FxPiece per piece][table in][tables out x 2][records recStride per piece][hist: FxlBlk per block]
-struct FxLayout { size_t offMeta, offIn, offOut, offRec, offBlk, total; };
-inline FxLayout fx_layout(int per, int P, int recStride, bool hist, std::vector<WsTake>* log = nullptr)
+// ---------------------------------------------------------------------------------------------------- few-block parses (c->fx, c->mx)
+// [PieceMeta per piece][state in][states out x 2][records recStride per piece][hist: FxlBlk per block]; a state: tabWords words
+// (kFxTab: level 1's table, 16 KiB; kMxTab: level 2's two tables, 128 KiB)
+struct PieceLayout { size_t offMeta, offIn, offOut, offRec, offBlk, total; };
+inline PieceLayout piece_layout(int per, int P, int recStride, int tabWords, bool hist, std::vector<WsTake>* log = nullptr)
 {
-    FxLayout L{};
+    PieceLayout L{};
     Carver c{log};
     const size_t nP = (size_t)per * (size_t)P;
-    L.offMeta = c.take<FxPiece>(nP);
-    L.offIn = c.take<uint32_t>(nP * kFxTab, 4);
-    L.offOut = c.take<uint32_t>(2 * nP * kFxTab, 4);
+    L.offMeta = c.take<PieceMeta>(nP);
+    L.offIn = c.take<uint32_t>(nP * (size_t)tabWords, 4);
+    L.offOut = c.take<uint32_t>(2 * nP * (size_t)tabWords, 4);
     L.offRec = c.take<uint64_t>(nP * (size_t)recStride, 8);
     L.offBlk = c.at;
     if (hist) L.offBlk = c.take<FxlBlk>((size_t)per);
     L.total = c.at;
     return L;
 }
-
-// ---------------------------------------------------------------------------------------------------- few-block level-2 parse (c->mx)
-// [FxPiece per piece][state in][states out x 2][records recStride per piece]; a state: both tables, kMxTab words (128 KiB)
-struct MxLayout { size_t offMeta, offIn, offOut, offRec, total; };
-inline MxLayout mx_layout(int per, int P, int recStride, std::vector<WsTake>* log = nullptr)
-{
-    MxLayout L{};
-    Carver c{log};
-    const size_t nP = (size_t)per * (size_t)P;
-    L.offMeta = c.take<FxPiece>(nP);
-    L.offIn = c.take<uint32_t>(nP * kMxTab, 4);
-    L.offOut = c.take<uint32_t>(2 * nP * kMxTab, 4);
-    L.offRec = c.take<uint64_t>(nP * (size_t)recStride, 8);
-    L.total = c.at;
-    return L;
-}
+// The two flavours' layouts by their earlier names (kept for one revision only: the emulation sources of the revision before this
+// one call them, and they are built against this tree whenever that revision's tests are run on it; nothing in this tree uses them --
+// delete them with the next change)
+typedef PieceLayout FxLayout;
+typedef PieceLayout MxLayout;
+inline FxLayout fx_layout(int per, int P, int recStride, bool hist, std::vector<WsTake>* log = nullptr) { return piece_layout(per, P, recStride, kFxTab, hist, log); }
+inline MxLayout mx_layout(int per, int P, int recStride, std::vector<WsTake>* log = nullptr) { return piece_layout(per, P, recStride, kMxTab, false, log); }
 
 // ---------------------------------------------------------------------------------------------------- HC levels 3..12 (c->h12)
 // Level 12 on independent blocks without dictionary runs in three phases per group of blocks (lz4hc12_device.inl):

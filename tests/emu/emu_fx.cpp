@@ -3,7 +3,7 @@
 // (lz4.c:1040-1300) that can be started from a saved state, to check the restart argument without the wave code.
 // Test infrastructure only: built into tests/emu/_build/, never loaded by plz4_amd, not a CPU fallback.
 #define PLZ4_EMU 1
-#include "../../plz4_amd/csrc/lz4_fx_device.inl"
+#include "piece_rounds.h"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -92,43 +92,23 @@ int emu_fx_sim(const uint8_t* src, int n, int stops, uint64_t* out, int cap, int
     return (int)seq.size();
 }
 
-// The few-block path over one block of n (kFxMinLen <= n <= 4 MiB): rounds of fx_piece over the pieces (in descending piece order
-// when `order` is 1), fx_gather, then the emit stage of lz4_seq_device.inl.  Returns the block's compressed size (0: does not fit
+// The few-block path over one block of n (kFxMinLen <= n <= 4 MiB): the rounds over the pieces (in descending piece order when
+// `order` is 1) and the gather (piece_rounds.h), then the emit stage of lz4_seq_device.inl.  Returns the block's compressed size (0: does not fit
 // cap), stats[0] = rounds that parsed, [1] = pieces parsed more than once, [2] = pieces, [3] = records; seqOut (optional) gets the
 // records.
 int emu_fx_encode(const uint8_t* src, int n, uint8_t* dst, int cap, int pieceBytes, int warmBytes, int order, long long* stats, uint64_t* seqOut)
 {
     if (n < kFxMinLen || n > kSeqMaxBlock || pieceBytes < 1024) return -1;
     static thread_local uint32_t lds[kHashBytes / 4];
-    const int P = fx_pieces(n, pieceBytes), recStride = fx_rec_stride_host(pieceBytes);
-    std::vector<FxPiece> meta(P);
-    memset(meta.data(), 0, sizeof(FxPiece) * P);
-    std::vector<uint32_t> tabIn((size_t)P * kFxTab), tabOut((size_t)2 * P * kFxTab);
-    std::vector<uint64_t> rec((size_t)P * recStride);
-    int rounds = 0;
-    for (int r = 1; r <= P; ++r) {
-        int ran = 0;
-        for (int j = 0; j < P; ++j) {
-            const int k = order ? P - 1 - j : j;
-            ran += fx_piece(src, n, k, r, pieceBytes, warmBytes, meta.data(), tabIn.data(), tabOut.data(), rec.data(), recStride, lds);
-        }
-        if (ran) rounds = r;
-        // (the kernels run all P rounds; later ones find nothing to do -- kept here as a check that they really would not)
-    }
+    PieceEmuBlock<FxFlavour<false>> B(n, pieceBytes);
+    const int rounds = B.run(FxFlavour<false>{lds, 0}, src, warmBytes, order);
     const int seqStride = seq_capacity(n) + 1;
     std::vector<uint64_t> seq((size_t)seqStride);
     SeqInfo info; info.nseq = -1; info.lastAnchor = 0;
-    int chained = 0, last = 0;
-    long long again = 0;
-    for (int j = 0; j < P; ++j) {
-        const int k = order ? P - 1 - j : j;
-        const int g = fx_gather(n, k, pieceBytes, meta.data(), rec.data(), recStride, seq.data(), seqStride - 1, &info);
-        chained += g > 0; last += g == 2;
-        again += meta[k].runs > 1;
-    }
-    if (last != 1 || info.nseq < 0) return -3;
+    int chained = 0;
+    if (!B.gather(seq.data(), seqStride - 1, &info, order, &chained) || info.nseq < 0) return -3;
     const int nseq = info.nseq;
-    if (stats) { stats[0] = rounds; stats[1] = again; stats[2] = P; stats[3] = nseq; }
+    if (stats) { stats[0] = rounds; stats[1] = B.again(); stats[2] = B.P; stats[3] = nseq; }
     if (seqOut) memcpy(seqOut, seq.data(), (size_t)nseq * 8);
     const int nChunks = (nseq + kSeqChunk - 1) / kSeqChunk;
     std::vector<uint32_t> cb(nChunks + 1), co(nChunks + 1);

@@ -1,10 +1,10 @@
 // Lane-emulation harness of the few-block level-1 path for blocks with history outside the block (the kExt flavour of
-// plz4_amd/csrc/lz4_fx_device.inl): fxl_prep, the rounds of piece parses, the gather and the emit stage with the segment's catch-up
-// room, as the kernels run them, over one block; a block that is not the path's (<= 4 KiB under a dictionary context) gets the empty
+// plz4_amd/csrc/lz4_fx_device.inl): fxl_prep, the rounds of piece parses and the gather (piece_rounds.h) and the emit stage with the
+// segment's catch-up room, as the kernels run them, over one block; a block that is not the path's (<= 4 KiB under a dictionary context) gets the empty
 // parse and then wave_encode_block_dict, as k_fxl_small does it.
 // Test infrastructure only: built into tests/emu/_build/, never loaded by plz4_amd, not a CPU fallback.
 #define PLZ4_EMU 1
-#include "../../plz4_amd/csrc/lz4_fx_device.inl"
+#include "piece_rounds.h"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -31,12 +31,8 @@ int emu_fxl_encode(const uint8_t* src, int n, const uint8_t* seg, int segLen, in
     memset(buf.data(), 0xA7, buf.size());
     uint8_t* const blk = buf.data() + 65536;
     if (n) memcpy(blk, src, (size_t)n);
-    const int P = fx_pieces_of<true>(n, pieceBytes), recStride = fx_rec_stride_host(pieceBytes);
-    std::vector<FxPiece> meta(P);
-    memset(meta.data(), 0, sizeof(FxPiece) * P);
-    std::vector<uint32_t> tabIn((size_t)P * kFxTab), tabOut((size_t)2 * P * kFxTab);
-    std::vector<uint64_t> rec((size_t)P * recStride);
-    const FxlBlk xb = fxl_prep(blk, n, mode, seg, segLen, dictTable, tabIn.data(), lds);
+    PieceEmuBlock<FxFlavour<true>> B(n, pieceBytes, -1, true);
+    const FxlBlk xb = *B.xb = fxl_prep(blk, n, mode, seg, segLen, dictTable, B.tabIn, lds);
     const int seqStride = seq_capacity(n) + 1;
     std::vector<uint64_t> seq((size_t)seqStride);
     SeqInfo info; info.nseq = -1; info.lastAnchor = 0;
@@ -44,25 +40,13 @@ int emu_fxl_encode(const uint8_t* src, int n, const uint8_t* seg, int segLen, in
     long long again = 0;
     if (xb.pfx < 0) { info.nseq = 0; info.lastAnchor = 0; }
     else {
-        for (int r = 1; r <= P; ++r) {
-            int ran = 0;
-            for (int j = 0; j < P; ++j) {
-                const int k = order ? P - 1 - j : j;
-                ran += fx_piece<true>(blk, n, k, r, pieceBytes, warmBytes, meta.data(), tabIn.data(), tabOut.data(), rec.data(), recStride, lds, xb.bs);
-            }
-            if (ran) rounds = r;
-        }
-        int last = 0;
-        for (int j = 0; j < P; ++j) {
-            const int k = order ? P - 1 - j : j;
-            const int g = fx_gather<true>(n, k, pieceBytes, meta.data(), rec.data(), recStride, seq.data(), seqStride - 1, &info);
-            last += g == 2;
-            again += meta[k].runs > 1;
-        }
-        if (last != 1 || info.nseq < 0) return -3;
+        rounds = B.run(FxFlavour<true>{lds, xb.bs}, blk, warmBytes, order);
+        int chained = 0;
+        if (!B.gather(seq.data(), seqStride - 1, &info, order, &chained) || info.nseq < 0) return -3;
+        again = B.again();
     }
     const int nseq = info.nseq, pfx = xb.pfx < 0 ? 0 : xb.pfx;
-    if (stats) { stats[0] = rounds; stats[1] = again; stats[2] = P; stats[3] = nseq; stats[4] = xb.pfx >= 0; }
+    if (stats) { stats[0] = rounds; stats[1] = again; stats[2] = B.P; stats[3] = nseq; stats[4] = xb.pfx >= 0; }
     const int nChunks = (nseq + kSeqChunk - 1) / kSeqChunk;
     std::vector<uint32_t> cb(nChunks + 1), co(nChunks + 1);
     std::vector<uint8_t> bk((size_t)seqStride);

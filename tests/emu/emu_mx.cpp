@@ -3,7 +3,7 @@
 // every saved boundary state; the path's layout and route functions.
 // Test infrastructure only: built into tests/emu/_build/, never loaded by plz4_amd, not a CPU fallback.
 #define PLZ4_EMU 1
-#include "mx_rounds.h"
+#include "piece_rounds.h"
 #include "../../plz4_amd/csrc/route.h"
 #include <string.h>
 #include <string>
@@ -25,7 +25,7 @@ int emu_mx_whole(const uint8_t* src, int n, uint64_t* out, int* lastAnchor)
     return hc_mid_parse(padded.data(), n, tabs.data(), tabs.data() + 16384, out, lastAnchor);
 }
 
-// The few-block path over one block of 0 <= n <= 4 MiB (mx_rounds.h), then the emit stage of lz4_seq_device.inl.  Returns the
+// The few-block path over one block of 0 <= n <= 4 MiB (piece_rounds.h), then the emit stage of lz4_seq_device.inl.  Returns the
 // block's compressed size (0: does not fit cap), stats[0] = rounds that walked, [1] = pieces walked more than once, [2] = pieces,
 // [3] = records, [4] = pieces in the chain, [5] = bytes walked in all rounds; seqOut (optional) gets the records.
 int emu_mx_encode(const uint8_t* src, int n, uint8_t* dst, int cap, int pieceBytes, int warmBytes, int order, long long* stats, uint64_t* seqOut)
@@ -33,16 +33,14 @@ int emu_mx_encode(const uint8_t* src, int n, uint8_t* dst, int cap, int pieceByt
     if (n < 0 || n > kSeqMaxBlock || pieceBytes < 1024) return -1;
     std::vector<uint8_t> padded((size_t)n + 64, 0);
     if (n > 0) memcpy(padded.data(), src, (size_t)n);
-    MxEmuBlock B(n, pieceBytes);
-    const int rounds = B.run(padded.data(), warmBytes, order);
+    PieceEmuBlock<MxFlavour> B(n, pieceBytes);
+    const int rounds = B.run(MxFlavour{}, padded.data(), warmBytes, order);
     const int seqStride = seq_capacity(n) + 1;
     std::vector<uint64_t> seq((size_t)seqStride);
     SeqInfo info; info.nseq = -1; info.lastAnchor = 0;
     int chained = 0;
     if (!B.gather(seq.data(), seqStride - 1, &info, order, &chained) || info.nseq < 0) return -3;
-    long long again = 0;
-    for (int k = 0; k < B.P; ++k) again += B.meta[k].runs > 1;
-    if (stats) { stats[0] = rounds; stats[1] = again; stats[2] = B.P; stats[3] = info.nseq; stats[4] = chained; stats[5] = B.walked; }
+    if (stats) { stats[0] = rounds; stats[1] = B.again(); stats[2] = B.P; stats[3] = info.nseq; stats[4] = chained; stats[5] = B.walked; }
     if (seqOut) memcpy(seqOut, seq.data(), (size_t)info.nseq * 8);
     const int nseq = info.nseq, nChunks = (nseq + kSeqChunk - 1) / kSeqChunk;
     std::vector<uint32_t> cb(nChunks + 1), co(nChunks + 1);
@@ -91,11 +89,11 @@ int emu_mx_restart(const uint8_t* src, int n, int stops)
     return tried;
 }
 
-// mx_layout: out = offMeta, offIn, offOut, offRec, total, then per take (off, bytes); returns the takes
+// piece_layout of the level-2 flavour: out = offMeta, offIn, offOut, offRec, total, then per take (off, bytes); returns the takes
 int emu_mx_layout(int per, int P, int recStride, long long* out, int cap)
 {
     std::vector<WsTake> log;
-    const MxLayout L = mx_layout(per, P, recStride, &log);
+    const PieceLayout L = piece_layout(per, P, recStride, kMxTab, false, &log);
     long long v[5] = {(long long)L.offMeta, (long long)L.offIn, (long long)L.offOut, (long long)L.offRec, (long long)L.total};
     int at = 0;
     for (int i = 0; i < 5 && at < cap; ++i) out[at++] = v[i];

@@ -3,7 +3,7 @@
 // the parser's counters -- among them how the grid batches left the steady state.
 // Test infrastructure only: built into tests/emu/_build/, never loaded by plz4_amd, not a CPU fallback.
 #define PLZ4_EMU 1
-#include "../../plz4_amd/csrc/lz4_fx_device.inl"
+#include "piece_rounds.h"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -55,29 +55,19 @@ int emu_pf_encode(const uint8_t* src, int n, uint8_t* dst, int cap, int win)
     return emit(src, n, seq.data(), nseq, lastAnchor, dst, cap);
 }
 
-// one block of kFxMinLen..4 MiB through the pieces' parser: rounds of fx_piece, fx_gather, emit.  *rounds <- rounds that parsed.
+// one block of kFxMinLen..4 MiB through the pieces' parser: the rounds and the gather (piece_rounds.h), emit.  *rounds <- rounds that parsed.
 int emu_pf_fx_encode(const uint8_t* src, int n, uint8_t* dst, int cap, int pieceBytes, int warmBytes, int* rounds)
 {
     if (n < kFxMinLen || n > kSeqMaxBlock || pieceBytes < 1024) return -1;
     static thread_local uint32_t lds[kHashBytes / 4];
-    const int P = fx_pieces(n, pieceBytes), recStride = fx_rec_stride_host(pieceBytes);
-    std::vector<FxPiece> meta(P);
-    memset(meta.data(), 0, sizeof(FxPiece) * P);
-    std::vector<uint32_t> tabIn((size_t)P * kFxTab), tabOut((size_t)2 * P * kFxTab);
-    std::vector<uint64_t> rec((size_t)P * recStride);
-    int last = 0;
-    for (int r = 1; r <= P; ++r) {
-        int ran = 0;
-        for (int k = 0; k < P; ++k) ran += fx_piece(src, n, k, r, pieceBytes, warmBytes, meta.data(), tabIn.data(), tabOut.data(), rec.data(), recStride, lds);
-        if (ran) last = r;
-    }
+    PieceEmuBlock<FxFlavour<false>> B(n, pieceBytes);
+    const int last = B.run(FxFlavour<false>{lds, 0}, src, warmBytes, 0);
     if (rounds) *rounds = last;
     const int seqStride = seq_capacity(n) + 1;
     std::vector<uint64_t> seq((size_t)seqStride);
     SeqInfo info; info.nseq = -1; info.lastAnchor = 0;
-    int ends = 0;
-    for (int k = 0; k < P; ++k) ends += fx_gather(n, k, pieceBytes, meta.data(), rec.data(), recStride, seq.data(), seqStride - 1, &info) == 2;
-    if (ends != 1 || info.nseq < 0) return -3;
+    int chained = 0;
+    if (!B.gather(seq.data(), seqStride - 1, &info, 0, &chained) || info.nseq < 0) return -3;
     return emit(src, n, seq.data(), info.nseq, info.lastAnchor, dst, cap);
 }
 

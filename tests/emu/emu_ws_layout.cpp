@@ -46,7 +46,7 @@ int wsl_run(const char* kind, const int64_t* in)
         const L1Layout L = l1_layout((int)in[0], (int)in[1], in[2] != 0, &takes);
         F(seqStride); F(maxChunks); F(perBlock); F(offInfo); F(offChunkBytes); F(offChunkOff); F(offSeq); F(offBk); F(offBlk); F(total);
     } else if (k == "fx") {
-        const FxLayout L = fx_layout((int)in[0], (int)in[1], (int)in[2], in[3] != 0, &takes);
+        const PieceLayout L = piece_layout((int)in[0], (int)in[1], (int)in[2], kFxTab, in[3] != 0, &takes);
         F(offMeta); F(offIn); F(offOut); F(offRec); F(offBlk); F(total);
     } else if (k == "hc") {
         const HcLayout L = hc_layout((int)in[0], (int)in[1], in[2] != 0, in[3] != 0, (int)in[4], &takes);

@@ -18,7 +18,8 @@ from plz4_amd import synth
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_fx.cpp")
 SO = os.path.join(ROOT, "tests", "emu", "_build", "libemu_fx.so")
-DEPS = [SRC] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in ("lz4_fx_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h")]
+DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "piece_rounds.h")] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in (
+    "lz4_fx_device.inl", "lz4_pieces_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h", "ws_layout.h")]
 N_MIN = 65547          # liblz4's byU32 tables from here on (lz4.c:1389)
 
 

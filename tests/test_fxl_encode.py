@@ -18,7 +18,8 @@ from plz4_amd import synth
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_fxl.cpp")
 SO = os.path.join(ROOT, "tests", "emu", "_build", "libemu_fxl.so")
-DEPS = [SRC] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in ("lz4_fx_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h")]
+DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "piece_rounds.h")] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in (
+    "lz4_fx_device.inl", "lz4_pieces_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h", "ws_layout.h")]
 FRESH, LOAD, CTX_COPY, CTX_LOOKUP, NONE = 0, 1, 2, 3, 4           # kDict* (lz4_device.inl)
 SIZES = (65547, 65548, 100000, 262161, 1 << 20)
 

@@ -16,8 +16,8 @@ from plz4_amd import synth
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_mx.cpp")
 SO = os.path.join(ROOT, "tests", "emu", "_build", "libemu_mx.so")
-DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "mx_rounds.h")] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in (
-    "lz4_mx_device.inl", "lz4_fx_device.inl", "lz4hc_lazy_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h", "ws_layout.h", "route.h")]
+DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "piece_rounds.h")] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in (
+    "lz4_mx_device.inl", "lz4_fx_device.inl", "lz4_pieces_device.inl", "lz4hc_lazy_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h", "ws_layout.h", "route.h")]
 BSZ = 4 << 20
 
 

@@ -20,7 +20,8 @@ from plz4_amd import synth
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_parse_flow.cpp")
 SO = os.path.join(ROOT, "tests", "emu", "_build", "libemu_pf.so")
-DEPS = [SRC] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in ("lz4_fx_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h")]
+DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "piece_rounds.h")] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in (
+    "lz4_fx_device.inl", "lz4_pieces_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h", "ws_layout.h")]
 N_MIN = 65547          # liblz4's byU32 tables from here on (lz4.c:1389)
 CNT = {"batches": 0, "primes": 1, "misorder": 2, "measured": 4, "second_round": 6, "no_regs": 7, "ext_loads": 10,
        "gave_up": 12, "done": 13, "missed": 14, "far": 15, "tail": 16, "piece": 17, "warmup": 18, "took36": 19}

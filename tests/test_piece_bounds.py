@@ -1,7 +1,8 @@
-"""The few-block level-2 path touches no byte outside its workspaces: tests/emu/mx_bounds_main.cpp, a program of its own on the
+"""The few-block parses touch no byte outside their workspaces: tests/emu/piece_bounds_main.cpp, a program of its own on the
 lane-emulated device code, built with the address and undefined-behaviour sanitizers and run as a child process (the sanitizers
-never enter this process; CPU only).  Every workspace array is an allocation of exactly what mx_layout plans; the program checks
-every block's records against the unbroken walk and exits non-zero on a wrong one; a bad access ends it with the sanitizer's report."""
+never enter this process; CPU only).  Every workspace array is an allocation of exactly what piece_layout plans; for each flavour
+(level 2, level 1, level 1 with history outside the block) the program checks every block's records against the unbroken parse and
+exits non-zero on a wrong one; a bad access ends it with the sanitizer's report."""
 import os
 import subprocess
 
@@ -9,8 +10,8 @@ import pytest
 
 from orclib import ROOT
 
-SRC = os.path.join(ROOT, "tests", "emu", "mx_bounds_main.cpp")
-EXE = os.path.join(ROOT, "tests", "emu", "_build", "mx_bounds")
+SRC = os.path.join(ROOT, "tests", "emu", "piece_bounds_main.cpp")
+EXE = os.path.join(ROOT, "tests", "emu", "_build", "piece_bounds")
 # (the runtimes linked statically: the program stands alone, whatever else the environment has the loader bring in)
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
 
@@ -21,7 +22,7 @@ def _sanitizers_link(tmp_path):
     return subprocess.run(["g++"] + SAN + ["-o", str(tmp_path / "probe"), str(probe)], capture_output=True).returncode == 0
 
 
-def test_mx_rounds_stay_inside_their_workspaces(tmp_path):
+def test_piece_rounds_stay_inside_their_workspaces(tmp_path):
     if not _sanitizers_link(tmp_path):
         pytest.skip("the sanitizer runtimes cannot be linked on this machine")
     os.makedirs(os.path.dirname(EXE), exist_ok=True)
@@ -30,3 +31,5 @@ def test_mx_rounds_stay_inside_their_workspaces(tmp_path):
     print(run.stdout)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-6000:]
     assert "no access outside a buffer" in run.stdout
+    for flavour in ("level 2", "level 1", "level 1 linked"):
+        assert "%s: no access outside a buffer, every block the unbroken parse's" % flavour in run.stdout, flavour
