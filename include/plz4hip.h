@@ -92,7 +92,13 @@
  * entry lives for a whole window.  Blocks of at most one piece are one piece of the same call.  Output, results, error codes and
  * capacity verdicts are exactly those of one wavefront per block; a call the path does not take, or whose workspace is refused
  * (about 5 bytes per input byte: three 128 KiB states and the records per piece, kept until plz4hip_ctx_trim), runs that launch.
- * Level 2 with a dictionary or linked blocks keeps one wavefront per block.
+ * A level-2 call with a dictionary and/or linked blocks (compress_batch_dict, encode_records_ex, dev_encode_records_ex,
+ * dev_encode_body_ex and the multi-GPU / host-layer routes that end there; host buffers: per staging chunk) of at most
+ * PLZ4HIP_MXL_MAX_BLOCKS (512; 0: off; read per call) blocks, the largest above one piece and at most 4 MiB, without a rider, takes the same
+ * walk in pieces behind every block's external segment -- the previous block's tail or the dictionary -- under the same
+ * PLZ4HIP_MX_PIECE_KIB / PLZ4HIP_MX_WARMUP_KIB and with the same workspace (about 5 bytes per input byte, kept until
+ * plz4hip_ctx_trim); blocks of at most 4 KiB under a dictionary context keep their wave-wide parser.  Same bytes, results and
+ * capacity verdicts; a call the path does not take, or whose workspace is refused, runs one wavefront per block.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
  * calls, rounds 1-3), PLZ4HIP_HC12_LAZY (level 12 with its searches made on demand), PLZ4HIP_HC_OVERLAP_OFF / _MIN / _GROUPS (levels 3..11: a call of 2048
  * blocks or more runs in four or more groups, the list builder of the next group on a second stream of the ctx beside the walk
@@ -146,7 +152,8 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
  * dictionary context encoded by the wave-wide HC parser (levels 2..12), [10] raw blocks above 4 MiB + 8 of capacity answered by the
  * few-block decoder (they count in [3] as well), [11] the jump rounds launched for the last call with such a block, [12] the literal
  * runs and matches that call handed to its grid-wide stage, [13] blocks encoded by the few-block level-2 path, [14] its rounds that
- * parsed something in the last such call, [15] pieces it parsed more than once.  Returns how many counters there are (16), or
+ * parsed something in the last such call, [15] pieces it parsed more than once ([14] and [15]: with or without history outside the block), [16] blocks with history outside
+ * the block encoded by the few-block level-2 path (a subset of [13]).  Returns how many counters there are (17), or
  * PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 

@@ -1,5 +1,6 @@
-// lz4_mx_device.inl -- the level-2 parse (hc_mid_parse, lz4hc_lazy_device.inl) of a call of few independent blocks cut across the
-// whole chip: lz4_fx_device.inl's design for LZ4MID_compress.
+// lz4_mx_device.inl -- the level-2 parse (hc_mid_parse, lz4hc_lazy_device.inl) of a call of few blocks cut across the whole chip:
+// lz4_fx_device.inl's design for LZ4MID_compress.  Independent blocks (MxFlavour), and blocks with history outside the block -- a
+// dictionary, linked blocks -- behind their external segment (MxlFlavour).
 //
 // A level-2 block is one serial chain of dependent memory round trips: one wave walks it, however empty the chip is.  Here a block
 // of up to 4 MiB is cut into pieces of `pb` bytes and every piece gets a wave of its own.
@@ -64,20 +65,23 @@ struct MxFlavour {
     }
 };
 
-// The flavour's round and gather by their earlier names and argument lists (kept for one revision only: the emulation sources of the revision before this
-// one call them, and they are built against this tree whenever that revision's tests are run on it; nothing in this tree uses them --
-// delete them with the next change)
-DEV int mx_pieces(int n, int pb) { return piece_count<true>(n, pb); }
-static inline int mx_rec_stride_host(int pb) { return piece_rec_stride(pb); }
-DEV int mx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int pb, int warm, PieceMeta* meta, uint32_t* tabIn, uint32_t* tabOut,
-                 uint64_t* rec, int recStride)
-{
-    return piece_round(MxFlavour{}, src, n, k, round, pb, warm, meta, tabIn, tabOut, rec, recStride);
-}
-DEV int mx_gather(int n, int k, int pb, const PieceMeta* __restrict__ meta, const uint64_t* __restrict__ rec, int recStride,
-                  uint64_t* __restrict__ seq, int seqCap, SeqInfo* info)
-{
-    return piece_gather<true>(n, k, pb, meta, rec, recStride, seq, seqCap, info);
-}
+// ... on a block BEHIND an external segment of pfx bytes (a linked block, a block > 4 KiB under an attached dictionary: hc_mid_parse's
+// kD).  Positions are the parser's: the segment's first byte is 0, the block's first byte pfx (base()); records and lastAnchor are
+// block-relative.  `src` is the block; the segment lies right in front of it.  Piece 0 -- and every piece whose start - warm is not
+// beyond the block's first byte -- walks from the block's start over zeroed tables primed over the segment (exact); a guessed start
+// begins over zeroed tables, primed as well while it lies within 64 KiB of the block's first byte (mid_guess_primes); a state handed
+// on is installed as it is.  Why a restart is exact behind
+// a segment as well: lz4hc_lazy_device.inl, at hc_mid_parse.
+struct MxlFlavour : MxFlavour {
+    int pfx;
+    DEVM explicit MxlFlavour(int pfx_) : pfx(pfx_) {}
+    DEVM int base() const { return pfx; }
+    DEVM bool guessed(int p0) const { return p0 > pfx; }
+    DEVM int walk(const uint8_t* __restrict__ blk, int n, uint64_t* rec, int recStride, int* lastAnchor, MidRun& run, uint32_t* work) const
+    {
+        const int ns = hc_mid_parse<true, uint32_t*, MidNoCtx, true>(blk, n, work, work + 16384, rec, lastAnchor, pfx, MidNoCtx(), &run);
+        return run.over ? recStride : ns;
+    }
+};
 
 }  // namespace plz4

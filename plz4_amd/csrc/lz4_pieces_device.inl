@@ -1,7 +1,7 @@
 // lz4_pieces_device.inl -- the round protocol of the few-block parses: one block's serial parse cut into pieces, every piece on a
-// wave of its own, re-run in rounds until every piece starts from the exact state its predecessor ends in.  Three flavours share
-// it: level 1 on independent blocks and on blocks with history outside the block (lz4_fx_device.inl), level 2 on independent
-// blocks (lz4_mx_device.inl).  Those files say why, for their parser, a parse restarted from a post-match state (anchor + live
+// wave of its own, re-run in rounds until every piece starts from the exact state its predecessor ends in.  Four flavours share
+// it: levels 1 and 2, each on independent blocks and on blocks with history outside the block (lz4_fx_device.inl,
+// lz4_mx_device.inl).  Those files say why, for their parser, a parse restarted from a post-match state (anchor + live
 // table entries) gives exactly the records of the unbroken parse; everything below rests on that alone.
 //
 // A block of n bytes is cut into P pieces of `pb` bytes.  Piece k's entry state is the first post-match state at or beyond its

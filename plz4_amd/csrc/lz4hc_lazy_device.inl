@@ -710,6 +710,21 @@ DEV bool mid_run_state(MidRun* run, uint32_t* h4t, uint32_t* h8t, SeqSink& out, 
     if (anchor >= run->end) { run->outAnchor = anchor; return true; }
     return false;
 }
+// kD and kRun together: the walk of a piece of a block BEHIND an external segment (MxlFlavour, lz4_mx_device.inl).  MidRun's
+// positions are the parser's (the segment's first byte is 0, the block's is pfx); records and lastAnchor stay block-relative.  The
+// restart argument holds unchanged: what the segment adds to a sequence -- the safeLen cut of a candidate inside it, no look at
+// ip + 1 and no catch-up there -- are functions of positions (the candidate's, pfx) and of the input only, lowPos = pfx bounds the
+// catch-up whatever the anchor; liveness is the same test; and a table entry that points into the segment is part of the state like
+// any other (same_state compares it while it is live).
+// A guessed start at p0 > pfx over zeroed tables lacks the segment's entries, which are live while p0 - pfx < 64 Ki.  Priming the
+// guess over the segment brings them back (not the block's own inserts that have overwritten some of them since: it stays a
+// guess, and any guess is correct).  Rounds on the emulation, primed / not primed: a block that starts with a copy of
+// its segment, 4 KiB pieces without warm-up 32 / 34, 8 KiB pieces with 16 KiB of warm-up 14 / 15; every other block and cut tried: the
+// same.  So a guess that near the block's start is primed.  (At the default cut no guess is: the first guessed start is 128 KiB in.)
+#ifndef PLZ4_MXL_PRIME_GUESS
+#define PLZ4_MXL_PRIME_GUESS 1
+#endif
+DEV bool mid_guess_primes(int p0, int pfx) { return PLZ4_MXL_PRIME_GUESS != 0 && p0 - pfx < 65536; }
 template <bool kD = false, class Tab = uint32_t*, class Ctx = MidNoCtx, bool kRun = false>
 DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab h8t, uint64_t* seq, int* lastAnchor, const int pfxArg = 0, const Ctx ctx = Ctx(),
                      MidRun* run = nullptr)
@@ -727,7 +742,11 @@ DEV int hc_mid_parse(const uint8_t* __restrict__ blk, const int n, Tab h4t, Tab 
             WAVE_FENCE();
         }
     }
-    if constexpr (kD) hc_mid_prime(src, pfx, h4t, h8t);
+    if constexpr (kD && kRun) {
+        // a piece behind a segment: from the block's start zeroed and primed (what LZ4_loadDictHC leaves: exact); from a predecessor's
+        // exit state neither (priming again would bring stale segment entries back over live ones); a guessed start: mid_guess_primes
+        if (!run->primed && (run->entryAnchor < 0 || mid_guess_primes(run->entryAnchor, pfx))) hc_mid_prime(src, pfx, h4t, h8t);
+    } else if constexpr (kD) hc_mid_prime(src, pfx, h4t, h8t);
     SeqSink out; out.seq = seq; out.n = 0; out.bias = pfx;
     LANES({ out.buf[I_] = 0; })
     const int mflimit = N - kMfLimit, matchlimit = N - kLastLiterals;

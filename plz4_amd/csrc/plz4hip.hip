@@ -419,11 +419,12 @@ __device__ __forceinline__ DictEnc fxl_dict_of(const CodecArgs& a, int i, int n)
 struct PieceArgs { PieceMeta* meta; uint32_t* tabIn; uint32_t* tabOut; uint64_t* rec; int P, pb, warm, recStride; unsigned long long* cnt; };
 
 // A flavour at kernel level: the device flavour F, whether the wave needs the 16 KiB LDS table, whether the blocks have an FxlBlk
-// (k_fxl_prep in front), the counters it bumps (blocks, rounds of the last call, pieces parsed again; kBlocksToo: a second block
-// counter or -1), which blocks are the path's and what a block that is not gets as its result (round 1, piece 0).
+// (k_fxl_prep in front) or only a segment length (kPfx: a.hcPfx, k_hc_ext_prep in front), the counters it bumps (blocks, rounds of
+// the last call, pieces parsed again; kBlocksToo: a second block counter or -1), which blocks are the path's and what a block that
+// is not gets as its result (round 1, piece 0).
 struct KFx {                   // level 1, independent blocks (lz4_fx_device.inl)
     typedef FxFlavour<false> F;
-    enum : int { kLds = 1, kHist = 0, kBlocks = 0, kRounds = 1, kAgain = 2, kBlocksToo = -1 };
+    enum : int { kLds = 1, kHist = 0, kPfx = 0, kBlocks = 0, kRounds = 1, kAgain = 2, kBlocksToo = -1 };
     static DEVM F flavour(const FxlBlk&, uint32_t* lds) { return F{lds, 0}; }
     static DEVM bool in_scope(const CodecArgs& a, int n, const FxlBlk&) { return n >= kFxMinLen && n <= a.l1MaxLen; }
     // byU16 blocks, lengths the workspace was not sized for: the block as k_l1_parse does it
@@ -435,7 +436,7 @@ struct KFx {                   // level 1, independent blocks (lz4_fx_device.inl
 };
 struct KFxl {                  // level 1, history outside the block (the kExt flavour)
     typedef FxFlavour<true> F;
-    enum : int { kLds = 1, kHist = 1, kBlocks = 0, kRounds = 1, kAgain = 2, kBlocksToo = 7 };
+    enum : int { kLds = 1, kHist = 1, kPfx = 0, kBlocks = 0, kRounds = 1, kAgain = 2, kBlocksToo = 7 };
     static DEVM F flavour(const FxlBlk& b, uint32_t* lds) { return F{lds, b.bs}; }
     static DEVM bool in_scope(const CodecArgs&, int, const FxlBlk& b) { return b.pfx >= 0; }
     // not this path's: an empty parse (k_fxl_small writes the block behind the emit stage), or no result (-1, as k_l1_parse says it)
@@ -443,10 +444,19 @@ struct KFxl {                  // level 1, history outside the block (the kExt f
 };
 struct KMx {                   // level 2, independent blocks (lz4_mx_device.inl): no LDS
     typedef MxFlavour F;
-    enum : int { kLds = 0, kHist = 0, kBlocks = 13, kRounds = 14, kAgain = 15, kBlocksToo = -1 };
+    enum : int { kLds = 0, kHist = 0, kPfx = 0, kBlocks = 13, kRounds = 14, kAgain = 15, kBlocksToo = -1 };
     static DEVM F flavour(const FxlBlk&, uint32_t*) { return F{}; }
     static DEVM bool in_scope(const CodecArgs& a, int n, const FxlBlk&) { return n >= 0 && n <= a.l1MaxLen; }
     // a block the workspace was not sized for: no result, as k_hc_mid says it
+    static DEVM int outside(const CodecArgs&, int, int, int, const FxlBlk&, uint32_t*, int*) { return -1; }
+};
+struct KMxl {                  // level 2, history outside the block (MxlFlavour): no LDS, the segment's length out of a.hcPfx
+    typedef MxlFlavour F;
+    enum : int { kLds = 0, kHist = 0, kPfx = 1, kBlocks = 13, kRounds = 14, kAgain = 15, kBlocksToo = 16 };
+    static DEVM F flavour(const FxlBlk& b, uint32_t*) { return F(b.pfx); }
+    static DEVM bool in_scope(const CodecArgs& a, int n, const FxlBlk& b) { return n >= 0 && n <= a.l1MaxLen && b.pfx >= 0; }
+    // a length the workspace was not sized for, or a block <= 4 KiB under a dictionary context (pfx -1: the emit stage lays it down
+    // stored, hc_ctx_blocks writes it afterwards): no result, as k_hc_mid<true> says it
     static DEVM int outside(const CodecArgs&, int, int, int, const FxlBlk&, uint32_t*, int*) { return -1; }
 };
 
@@ -456,6 +466,7 @@ template <class K> __device__ __forceinline__ void piece_body(const CodecArgs& a
     const int n = block_len(a, gi);
     FxlBlk b; b.pfx = 0; b.bs = 0;
     if (K::kHist) b = xb[i];                                                 // (loaded before anything is stored: scalar loads)
+    if (K::kPfx) b.pfx = a.hcPfx[gi];
     if (!K::in_scope(a, n, b)) {
         if (round != 1 || k != 0) return;
         int lastAnchor = 0;
@@ -481,6 +492,7 @@ template <class K> __global__ __launch_bounds__(64) void k_piece_gather(CodecArg
     const int n = block_len(a, gi);
     FxlBlk b; b.pfx = 0; b.bs = 0;
     if (K::kHist) b = xb[i];
+    if (K::kPfx) b.pfx = a.hcPfx[gi];
     if (!K::in_scope(a, n, b) || k >= piece_count<K::F::kPiece0>(n, f.pb)) return;
     const int64_t pb0 = (int64_t)i * f.P;
     const PieceMeta* m = f.meta + pb0;
@@ -1820,7 +1832,7 @@ struct plz4hip_ctx {
     // route (k_l1x_parse), [9] blocks of at most 4 KiB under a dictionary context encoded by the wave-wide HC parser (k_hcx),
     // [13] blocks encoded by the few-block level-2 path, [14] its rounds that parsed something in the last such call, [15] pieces
     // it parsed more than once
-    static constexpr int kCounters = 16;
+    static constexpr int kCounters = 17;
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
@@ -2372,7 +2384,7 @@ FxlBlk* bind_pieces(PieceArgs& pc, uint8_t* base, const PieceLayout& L, bool his
     pc.rec = (uint64_t*)(base + L.offRec);
     return hist ? (FxlBlk*)(base + L.offBlk) : nullptr;
 }
-// The rounds of one group of a few-block call and the gather behind them (K: KFx, KFxl, KMx).  P rounds are always enough
+// The rounds of one group of a few-block call and the gather behind them (K: KFx, KFxl, KMx, KMxl).  P rounds are always enough
 // (lz4_pieces_device.inl); the rounds after the last change find nothing to do.  first: the call's first group.
 template <class K> void launch_piece_rounds(hipStream_t s, const CodecArgs& a, const PieceArgs& pc, FxlBlk* xb, int ng, bool first)
 {
@@ -2451,7 +2463,10 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
     const L1Shape shape{nb, maxLen, rawMode != 0, mid, rider != nullptr, hist, l1x, a.bodyOff != nullptr, hist && a.dictLen >= 8};
     const L1Want want = l1_want(shape, sw);
     // level 2: whether the few-block walk takes the call (read once; a level-1 call never asks)
-    const MxWant mxWant = mid ? mx_want(MxShape{a.level, nb, maxLen, a.hcEx != 0 || a.hcPfx != nullptr, rider != nullptr}, read_mx_switches()) : MxWant{};
+    // (a.hcPfx: the blocks have history outside the block and k_hc_ext_prep has noted their segments -- mxl_want's calls)
+    const bool mxl = mid && a.hcPfx != nullptr;
+    const MxShape mxShape{a.level, nb, maxLen, a.hcEx != 0 || a.hcPfx != nullptr, rider != nullptr};
+    const MxWant mxWant = !mid ? MxWant{} : mxl ? mxl_want(mxShape, read_mx_switches()) : mx_want(mxShape, read_mx_switches());
     a.rawMode = rawMode; a.blk0 = 0; a.nBlocks = nb;
     const bool shared = (ws == nullptr);
     int wsi = 0;
@@ -2542,7 +2557,8 @@ int launch_l1(plz4hip_ctx* c, hipStream_t s, CodecArgs a, int nb, int maxLen, in
         } else if (route == L1Route::Mid) c->gatePending = false;
         switch (route) {
         case L1Route::Mid:
-            if (mxOn) launch_piece_rounds<KMx>(s, a, pc, xb, ng, g0 == 0);
+            if (mxOn && mxl) launch_piece_rounds<KMxl>(s, a, pc, xb, ng, g0 == 0);
+            else if (mxOn) launch_piece_rounds<KMx>(s, a, pc, xb, ng, g0 == 0);
             else hipLaunchKernelGGL(hc_mid_kernel(a.hcPfx != nullptr), dim3(grid_for(ng, c->hcWaves)), dim3(64), 0, s, a);
             break;
         case L1Route::Fxl: launch_piece_rounds<KFxl>(s, a, pc, xb, ng, g0 == 0); break;

@@ -165,9 +165,14 @@ inline HcPlan hc_route(const HcShape& k, const HcSwitches& sw, bool midDeclined 
 // alone and through host buffers (profiles/mx_rate.json, 4 MiB T blocks: 663 against 984 ms; at 1024 the kernels alone tie, 1 222 ms,
 // at 2048 they lose, 2 357 against 1 556).  The workspace of such a call is 5 bytes per input byte (10 GiB at 512 x 4 MiB).
 constexpr int kMxMaxBlocks = 512;
+// PLZ4HIP_MXL_MAX_BLOCKS: the same bar for blocks with history outside the block (a dictionary, linked blocks: mxl_want), measured
+// on its own: 512 (profiles/mxl_rate.json, 4 MiB linked T blocks behind a 64 KiB dictionary: 681 against 1 023 ms kernels alone, 762
+// against 1 136 through host buffers; at 1024 the kernels alone lose, 1 250 against 1 213, while host buffers still win).
+constexpr int kMxlMaxBlocks = 512;
 struct MxSwitches {
     int maxBlocks = kMxMaxBlocks;          // PLZ4HIP_MX_MAX_BLOCKS (0: off)
     int pieceKiB = 128, warmKiB = 256;     // PLZ4HIP_MX_PIECE_KIB in 1..4096, PLZ4HIP_MX_WARMUP_KIB in 0..4096 (rounds per choice)
+    int mxlMaxBlocks = kMxlMaxBlocks;      // PLZ4HIP_MXL_MAX_BLOCKS (0: off): the same walk behind external segments (mxl_want)
 };
 struct MxShape { int level, nb, maxLen; bool hcEx, rider; };
 // What the call asks for before anything is reserved: mx -- the walk in pieces, with its cut (piece_cut).
@@ -176,6 +181,14 @@ inline MxWant mx_want(const MxShape& k, const MxSwitches& sw)
 {
     // (a call whose largest block is one piece has nothing to cut: one wave per block either way, so it keeps today's launch)
     const bool mx = k.level == 2 && !k.hcEx && !k.rider && k.nb >= 1 && k.nb <= sw.maxBlocks && k.maxLen > (sw.pieceKiB << 10) && k.maxLen <= kSeqMaxBlock;
+    const PieceCut c = piece_cut(mx, k.maxLen, sw.pieceKiB, sw.warmKiB);
+    return MxWant{c.on, c.piece, c.warm, c.P};
+}
+// The same question for a level-2 call whose blocks have history outside the block (hcEx: a dictionary, linked blocks; k_hc_mid<true>
+// otherwise): no rider, 1 .. mxlMaxBlocks blocks, the largest above one piece and at most 4 MiB.  Piece and warm-up are mx_want's.
+inline MxWant mxl_want(const MxShape& k, const MxSwitches& sw)
+{
+    const bool mx = k.level == 2 && k.hcEx && !k.rider && k.nb >= 1 && k.nb <= sw.mxlMaxBlocks && k.maxLen > (sw.pieceKiB << 10) && k.maxLen <= kSeqMaxBlock;
     const PieceCut c = piece_cut(mx, k.maxLen, sw.pieceKiB, sw.warmKiB);
     return MxWant{c.on, c.piece, c.warm, c.P};
 }
@@ -323,6 +336,8 @@ template <class Get> MxSwitches parse_mx_switches(Get&& get)
     MxSwitches sw;
     sw.maxBlocks = num("PLZ4HIP_MX_MAX_BLOCKS", kMxMaxBlocks);
     if (sw.maxBlocks > 65535) sw.maxBlocks = 65535;                            // (the blocks of a group are the grid's y)
+    sw.mxlMaxBlocks = num("PLZ4HIP_MXL_MAX_BLOCKS", kMxlMaxBlocks);
+    if (sw.mxlMaxBlocks > 65535) sw.mxlMaxBlocks = 65535;
     parse_piece_kib(get, "PLZ4HIP_MX_PIECE_KIB", "PLZ4HIP_MX_WARMUP_KIB", &sw.pieceKiB, &sw.warmKiB);
     return sw;
 }
