@@ -21,9 +21,27 @@
 //   E  dx_gather         out[p] <- out[ptr[p]].
 //
 // Raw blocks above kDxMaxOut (up to 1 GiB) take the same stages with B cut once more, long runs handed to the whole grid and more
-// jump rounds: dxb_* at the end of this file.
+// jump rounds: dxb_* below.  Blocks with history outside the block share one pointer space: dxl_* below.
 //
-// Compiled for the CPU as-is by tests/emu (emu_dx_decode, emu_dx_big) and checked there against the oracle on valid and corrupt blocks.
+// THE STAGE TRAIN, stated once (the dx_stage_* bodies at the end of this file; the kernels of plz4hip.hip are shells over them and
+// tests/emu/dx_train.h runs the same bodies on the CPU).  A call of nb blocks, its workspace laid out for blocks of up to maxIn input
+// and maxOut output bytes (ws_layout.h: per block a row of T, of pointers, of maxSeg units, a DxInfo); DxBlk is one block's view.
+//
+//   stage     grid                              body               a flagged block (DxInfo::bad)
+//   tables    (maxSeg, nb) waves                dx_stage_tables    -- (not known yet; a block longer than its row of T gets no table)
+//   stitch    nb waves                          dx_stage_stitch    set here: a misfit (dx_misfit: larger than the rows were sized
+//             [dxb: compose / hop / units]      dxb_stage_*          for), or a chain the stitch cannot follow; DxInfo starts here
+//   fill      (maxSeg, nb) waves                dx_stage_fill      skipped; a unit that fails, or that does not stop where the next
+//                                                                    one starts, flags its block -- the block's OTHER units still run
+//   jump      (chunks of 1024 bytes, nb) x 4    dx_stage_jump      skipped; one launch per round, dx_rounds_for(span) of them; a
+//             waves, once per round                                  block sits a round out once its row of moved[] says it is at rest
+//   gather    as jump, once                     dx_stage_gather    skipped: its output is the one-wave decoder's, which runs behind
+//
+// A flavour (DxF: blocks up to kDxMaxOut; DxbF: raw blocks above; DxlF: history outside the block) supplies what differs: the fill's
+// <kHist, kBig> and whether it lists runs, where the block's row of moved[] is, the jump and the gather (the block's own pointer row,
+// or the call's pointer space), the rounds a call launches.  The verdict and the counters behind the gather are the kernels'.
+//
+// Compiled for the CPU as-is by tests/emu (dx_train.h) and checked there against the oracle on valid and corrupt blocks.
 #pragma once
 #include "lz4_device.inl"
 
@@ -32,7 +50,7 @@ namespace plz4 {
 enum : int { kDxSeg = 8192,                 // input bytes per table segment / fill unit
              kDxExt = 32,                   // length bytes a table entry looks through (longer: the stitch parses that sequence itself)
              kDxMaxOut = (4 << 20) + 8,     // the path is taken for outputs up to here (blk/pool.go:23-26: bsz + 8)
-             kDxRounds = 24 };              // jump rounds launched (2^24 > kDxMaxOut; a block stops taking part once nothing moves)
+             kDxRounds = 24 };              // jump rounds launched: dx_rounds_for(kDxMaxOut) below (a block stops taking part once nothing moves)
 
 struct DxUnit { int32_t ip, op, stop, pad; };               // where the true chain enters a segment (ip < 0: it does not), the output position there, where the unit ends
 struct DxInfo { int32_t bad, outLen, tailFrom, pad; uint32_t moved[kDxRounds + 1]; };
@@ -167,8 +185,10 @@ struct DxRun  { uint32_t op, from, len, kind; };
 struct DxRuns { DxRun* list; uint32_t* count; int room; int thr; };
 #if defined(PLZ4_EMU)
 DEV uint32_t dx_count_up(uint32_t* p) { return (*p)++; }
+DEV void     dx_flag(int32_t* p) { *p |= 1; }
 #else
 DEV uint32_t dx_count_up(uint32_t* p) { return atomicAdd(p, 1u); }
+DEV void     dx_flag(int32_t* p) { atomicOr(p, 1); }
 #endif
 DEV bool dxb_note(const DxRuns* r, const uint32_t kind, const int64_t op, const int64_t from, const int64_t len)
 {
@@ -460,6 +480,10 @@ DEV void dx_gather(uint8_t* __restrict__ out, const uint32_t* __restrict__ ptr, 
 // A chain is answered up to its first block that is not plainly good; from there on the one-wave chain walk takes over, starting
 // from the window the good blocks leave (dxl_window).
 enum : int { kDxlMaxRounds = 32, kDxlHist = 65536 };
+// The rounds rule: a copy chain over a span of N bytes is at most N deep, ceil(log2 N) jump rounds bring every pointer home, and one
+// more round sees that nothing moves; at most kDxlMaxRounds (a row of moved[] has one entry more).
+static constexpr int dx_rounds_for(const int64_t span) { int r = 1; while (r < kDxlMaxRounds && ((int64_t)1 << (r - 1)) < span) ++r; return r; }
+static_assert(dx_rounds_for(kDxMaxOut) == kDxRounds, "DxInfo::moved is sized by kDxRounds");
 
 struct DxlCall {
     uint32_t*       ptr;   int64_t P;   int nb;                 // ptr[b * P + pos]
@@ -727,7 +751,7 @@ struct DxbInfo  { uint32_t runs, pad; uint32_t moved[kDxlMaxRounds + 1]; };
 static inline int    dxb_groups(const int64_t maxSeg, const int G) { return (int)((maxSeg + G - 1) / G); }
 static inline size_t dxb_ptr_stride(const int64_t maxOut) { return ((size_t)maxOut + 64 + 1023) / 1024 * 1024; }
 static inline int    dxb_run_room(const int64_t maxIn, const int64_t maxOut, const int thr) { return (int)(maxIn / thr + maxOut / thr + 2); }
-static inline int    dxb_rounds(const int64_t maxOut) { int r = 1; while (r < kDxlMaxRounds && ((int64_t)1 << (r - 1)) < maxOut) ++r; return r; }
+static inline int    dxb_rounds(const int64_t maxOut) { return dx_rounds_for(maxOut); }
 // the group size a call is laid out for: the power of two next to the square root of its segments
 static inline int    dxb_group_for(const int64_t maxSeg) { int g = 2; while (g < kDxbMaxGroup && (int64_t)g * g < maxSeg) g *= 2; return g; }
 
@@ -849,5 +873,141 @@ DEV void dxb_run_piece(const DxRun& r, const uint32_t c, const uint8_t* __restri
     else dx_fill_match<false>(ptr, (int64_t)r.op + at, (int)r.from, len);
 }
 DEV uint32_t dxb_run_pieces(const DxRun& r) { return (r.len + (uint32_t)kDxbPiece - 1u) / (uint32_t)kDxbPiece; }
+
+// ---- The stage train (the table at the head of this file): one block's view of the call, the body of every stage, the flavours.
+// DxBlk: plain pointers and numbers -- the block (dx_src / dx_len / dx_cap of plz4hip.hip), its rows of the call's tables and what
+// they were sized for, its DxInfo, its number in the call.
+struct DxBlk {
+    const uint8_t* src; int n; uint8_t* dst; int cap;
+    uint64_t* T; uint32_t* ptr; DxUnit* units;
+    int64_t tStride, pStride; int maxSeg;
+    DxInfo* info;
+    int b;
+};
+
+// The misfit rule: a block larger than what the tables, units and pointers were sized for is left to the one-wave kernel.  (The
+// first term alone keeps the tables stage off a row of T that is too short; the stitch stage flags the block.)
+DEV bool dx_table_misfit(const DxBlk& k) { return (int64_t)k.n > k.tStride - 64; }
+DEV bool dx_misfit(const DxBlk& k) { return dx_segments(k.n) > k.maxSeg || dx_table_misfit(k) || (int64_t)k.cap > k.pStride - 64; }
+
+// Where a block's state starts: the stitch stage's verdict, no output yet, no round has moved anything (bi: the big path's state too).
+DEV void dx_info_begin(const DxBlk& k, const int bad, DxbInfo* bi = nullptr)
+{
+    LANES({
+        if (LANE == 0) {
+            DxInfo inf; inf.bad = bad; inf.outLen = 0; inf.tailFrom = dx_tail_from(dx_segments(k.n)); inf.pad = 0;
+            for (int r = 0; r <= kDxRounds; ++r) inf.moved[r] = 0;
+            *k.info = inf;
+            if (bi) {
+                DxbInfo x; x.runs = 0; x.pad = 0;
+                for (int r = 0; r <= kDxlMaxRounds; ++r) x.moved[r] = 0;
+                *bi = x;
+            }
+        }
+    })
+}
+
+// tables: wave j of `shares` lays down its share of the pointer row as the identity, then the table of input segment j
+DEV void dx_stage_tables(const DxBlk& k, const int j, const uint32_t shares)
+{
+    const int64_t share = (k.pStride + shares - 1) / shares;
+    const int64_t lo = (int64_t)j * share, hi = lo + share < k.pStride ? lo + share : k.pStride;
+    LANES({ for (int64_t p = lo + LANE; p < hi; p += 64) k.ptr[p] = (uint32_t)p; })
+    if (k.n <= 0 || (int64_t)j * kDxSeg >= k.n || dx_table_misfit(k)) return;
+    dx_segment_table(k.src, k.n, j, k.T);
+}
+// stitch (DxF, DxlF): one wave per block
+DEV void dx_stage_stitch(const DxBlk& k)
+{
+    const int bad = dx_misfit(k) ? 1 : dx_stitch(k.src, k.n, k.cap, k.T, k.units, dx_segments(k.n));
+    dx_info_begin(k, bad);
+}
+// fill: unit j of the block.  Where a unit stops is where the next one starts, or the block is flagged.  What it found, for whoever
+// looks: units that do not meet are a bug of the stitch, and the emulation tells them from a block the fill declines.
+enum : int { kDxFillIdle = 0, kDxFillOk = 1, kDxFillLeft = 2, kDxFillDisagree = 3 };
+template <class F> DEV int dx_stage_fill(const F& f, const DxBlk& k, const int j)
+{
+    DxInfo* const inf = k.info;
+    if (inf->bad || j > inf->tailFrom) return kDxFillIdle;
+    const int jt = inf->tailFrom;
+    const DxUnit u = k.units[j];
+    if (j < jt && u.ip < 0) return kDxFillIdle;
+    const DxRuns runs = f.runs();
+    const int64_t r = wave_dx_fill<F::kHist, F::kBig>(k.src, k.n, k.dst, k.cap, k.ptr, u.ip, u.op, u.stop, j == jt, F::kBig ? &runs : nullptr);
+    bool ok = r >= 0;
+    if (ok && j < jt) {
+        int nx = j + 1; while (nx < jt && k.units[nx].ip < 0) ++nx;
+        ok = k.units[nx].op == (int)r;
+    }
+    LANES({ if (LANE == 0) { if (!ok) dx_flag(&inf->bad); else if (j == jt) inf->outLen = (int)r; } })
+    return ok ? kDxFillOk : (r >= 0 ? kDxFillDisagree : kDxFillLeft);
+}
+// jump: round r over the 64 x 4 pointers from p0 on
+template <class F> DEV void dx_stage_jump(const F& f, const DxBlk& k, const int r, const int p0)
+{
+    uint32_t* const moved = f.moved(k);
+    if (k.info->bad || (r > 0 && !moved[r - 1])) return;
+    const int outLen = k.info->outLen;
+    if (p0 >= outLen) return;
+    if (f.jump(k, p0, outLen)) { LANES({ if (LANE == 0) moved[r] = 1u; }) }
+}
+// gather: the 64 x 4 bytes from p0 on
+template <class F> DEV void dx_stage_gather(const F& f, const DxBlk& k, const int p0)
+{
+    if (k.info->bad) return;
+    const int outLen = k.info->outLen;
+    if (p0 >= outLen) return;
+    f.gather(k, p0, outLen);
+}
+
+// The flavours.  rounds(nb, maxOut): the jump rounds a call of nb blocks with outputs of up to maxOut bytes launches.
+struct DxF {                                                                // blocks up to kDxMaxOut, raw or records
+    static constexpr bool kHist = false, kBig = false;
+    static constexpr int rounds(int, int64_t) { return dx_rounds_for(kDxMaxOut); }
+    DEVM DxRuns runs() const { return DxRuns{nullptr, nullptr, 0, 0}; }
+    DEVM uint32_t* moved(const DxBlk& k) const { return k.info->moved; }   // kDxRounds + 1 entries
+    DEVM bool jump(const DxBlk& k, int p0, int outLen) const { return dx_jump(k.ptr, p0, outLen); }
+    DEVM void gather(const DxBlk& k, int p0, int outLen) const { dx_gather(k.dst, k.ptr, p0, outLen); }
+};
+struct DxbF {                                                               // raw blocks above kDxMaxOut: the block's rows of the big path's arrays
+    static constexpr bool kHist = false, kBig = true;
+    static int rounds(int, int64_t maxOut) { return dxb_rounds(maxOut); }
+    uint64_t* TG; DxbEntry* ent; int G;                                     // the stitch in three steps: dxb_stage_* below
+    DxRun* list; int room, thr; DxbInfo* bi;
+    DEVM DxRuns runs() const { return DxRuns{list, &bi->runs, room, thr}; }
+    DEVM uint32_t* moved(const DxBlk&) const { return bi->moved; }         // kDxlMaxRounds + 1 entries
+    DEVM bool jump(const DxBlk& k, int p0, int outLen) const { return dx_jump(k.ptr, p0, outLen); }
+    DEVM void gather(const DxBlk& k, int p0, int outLen) const { dx_gather(k.dst, k.ptr, p0, outLen); }
+};
+struct DxlF {                                                               // history outside the block: the call's one pointer space
+    static constexpr bool kHist = true, kBig = false;
+    static int rounds(int nb, int64_t maxOut) { return dx_rounds_for((int64_t)nb * (maxOut < kDxMaxOut ? maxOut : (int64_t)kDxMaxOut) + kDxlHist); }
+    DxlCall call; uint32_t* movedAll;                                       // per block kDxlMaxRounds + 1 entries
+    DEVM DxRuns runs() const { return DxRuns{nullptr, nullptr, 0, 0}; }
+    DEVM uint32_t* moved(const DxBlk& k) const { return movedAll + (int64_t)k.b * (kDxlMaxRounds + 1); }
+    DEVM bool jump(const DxBlk& k, int p0, int outLen) const { return dxl_jump(call.ptr, dxl_hist0(call), (uint32_t)((int64_t)k.b * call.P), p0, outLen); }
+    DEVM void gather(const DxBlk& k, int p0, int outLen) const { dxl_gather(call, k.b, p0, outLen); }
+};
+
+// The big path's stitch, three stages: compose -- (groups x 128, nb) waves, wave `sub` of group g; hop -- nb waves, and the block's
+// state starts here; units -- (groups, nb) waves.
+DEV void dxb_stage_compose(const DxbF& f, const DxBlk& k, const int g, const int sub)
+{
+    if (k.n <= 0 || dx_misfit(k)) return;
+    if ((g + 1) * f.G > dx_tail_from(dx_segments(k.n))) return;             // (only groups with all their segments are hopped over)
+    dxb_compose(k.T, f.TG, k.n, g, f.G, sub);
+}
+DEV void dxb_stage_hop(const DxbF& f, const DxBlk& k)
+{
+    const int bad = dx_misfit(k) ? 1 : dxb_hop(k.src, k.n, k.cap, k.T, f.TG, f.ent, k.units, dx_segments(k.n), f.G);
+    dx_info_begin(k, bad, f.bi);
+}
+DEV void dxb_stage_units(const DxbF& f, const DxBlk& k, const int g)
+{
+    if (k.info->bad) return;
+    const int nseg = dx_segments(k.n);
+    if (g * f.G >= dx_tail_from(nseg)) return;
+    dxb_group_units(k.src, k.n, k.T, f.ent, k.units, nseg, f.G, g);
+}
 
 }  // namespace plz4

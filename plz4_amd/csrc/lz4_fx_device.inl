@@ -76,26 +76,6 @@ template <bool kExt = false> struct FxFlavour {
     }
 };
 
-// The flavour's round and gather by their earlier names and argument lists (kept for one revision only: the emulation sources of the revision before this
-// one call them, and they are built against this tree whenever that revision's tests are run on it; nothing in this tree uses them --
-// delete them with the next change)
-typedef PieceMeta FxPiece;
-DEV int fx_pieces(int n, int pb) { return piece_count<false>(n, pb); }
-template <bool kExt> DEV int fx_pieces_of(int n, int pb) { return piece_count<kExt>(n, pb); }
-static inline int fx_rec_stride_host(int pb) { return piece_rec_stride(pb); }
-template <bool kExt = false>
-DEV int fx_piece(const uint8_t* __restrict__ src, int n, int k, int round, int pb, int warm, FxPiece* meta, uint32_t* tabIn, uint32_t* tabOut,
-                 uint64_t* rec, int recStride, uint32_t* lds, const int bs = 0)
-{
-    return piece_round(FxFlavour<kExt>{lds, bs}, src, n, k, round, pb, warm, meta, tabIn, tabOut, rec, recStride);
-}
-template <bool kExt = false>
-DEV int fx_gather(int n, int k, int pb, const FxPiece* __restrict__ meta, const uint64_t* __restrict__ rec, int recStride,
-                  uint64_t* __restrict__ seq, int seqCap, SeqInfo* info)
-{
-    return piece_gather<kExt>(n, k, pb, meta, rec, recStride, seq, seqCap, info);
-}
-
 // ---- blocks with history outside the block
 struct FxlBlk { int32_t pfx, bs; };       // the segment's bytes (-1: not this path's block) and liblz4's index of the block's first byte
 

@@ -1265,136 +1265,103 @@ __global__ __launch_bounds__(64) void k_hc_dict_prime(const uint8_t* dict, int l
 __device__ __forceinline__ int dx_cap(const CodecArgs& a, int b) { return a.dstCap ? a.dstCap[b] : a.dstCapAll; }
 __device__ __forceinline__ const uint8_t* dx_src(const CodecArgs& a, int b) { return a.src + (a.dxSrcOff ? a.dxSrcOff[b] : (int64_t)b * a.srcStride); }
 __device__ __forceinline__ int dx_len(const CodecArgs& a, int b) { return a.dxLen ? a.dxLen[b] : a.srcLen[b]; }
-__global__ __launch_bounds__(64) void k_dx_tables(CodecArgs a)
+// One block's view of the call for the stage bodies (dx_stage_*, lz4_dx_device.inl)
+__device__ __forceinline__ DxBlk dx_blk(const CodecArgs& a, int b)
 {
-    const int j = blockIdx.x, b = blockIdx.y;
-    const int n = dx_len(a, b);
-    {   // the pointer table starts as the identity: this workgroup's share of it
-        const int64_t share = (a.dxPtrStride + gridDim.x - 1) / gridDim.x;
-        uint32_t* const ptr = a.dxPtr + (int64_t)b * a.dxPtrStride;
-        const int64_t lo = (int64_t)j * share, hi = lo + share < a.dxPtrStride ? lo + share : a.dxPtrStride;
-        for (int64_t p = lo + (threadIdx.x & 63u); p < hi; p += 64) ptr[p] = (uint32_t)p;
-    }
-    if (n <= 0 || (int64_t)j * kDxSeg >= n || n > a.dxTStride - 64) return;           // (a block beyond what the tables were sized for is flagged by the stitch)
-    dx_segment_table(dx_src(a, b), n, j, a.dxT + (int64_t)b * a.dxTStride);
+    DxBlk k;
+    k.src = dx_src(a, b); k.n = dx_len(a, b); k.dst = a.dst + (int64_t)b * a.dstStride; k.cap = dx_cap(a, b);
+    k.T = a.dxT + (int64_t)b * a.dxTStride; k.ptr = a.dxPtr + (int64_t)b * a.dxPtrStride; k.units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
+    k.tStride = a.dxTStride; k.pStride = a.dxPtrStride; k.maxSeg = a.dxMaxSeg;
+    k.info = a.dxInfo + b; k.b = b;
+    return k;
 }
-__global__ __launch_bounds__(64) void k_dx_stitch(CodecArgs a)
+__device__ __forceinline__ DxlCall dxl_call(const CodecArgs& a)
 {
-    const int b = blockIdx.x;
-    const int n = dx_len(a, b);
-    const int nseg = dx_segments(n);
-    int bad = (nseg > a.dxMaxSeg || n > a.dxTStride - 64 || dx_cap(a, b) > a.dxPtrStride - 64) ? 1 : dx_stitch(dx_src(a, b), n, dx_cap(a, b), a.dxT + (int64_t)b * a.dxTStride,
-                                                a.dxUnits + (int64_t)b * a.dxMaxSeg, nseg);
-    if ((threadIdx.x & 63u) == 0) {
-        DxInfo inf; inf.bad = bad; inf.outLen = 0; inf.tailFrom = dx_tail_from(nseg); inf.pad = 0;
-        for (int r = 0; r <= kDxRounds; ++r) inf.moved[r] = 0;
-        a.dxInfo[b] = inf;
-    }
+    DxlCall c;
+    c.ptr = a.dxPtr; c.P = a.dxPtrStride; c.nb = a.nBlocks; c.info = a.dxInfo; c.len = a.dxLen; c.first = a.dxlFirst; c.chain = a.dxlChain;
+    if (a.linked) { c.hist = a.window; c.histStride = 131072; c.histLen = a.windowLen; c.histLenAll = 0; }
+    else { c.hist = a.dict; c.histStride = 0; c.histLen = nullptr; c.histLenAll = (a.dict && a.dictLen > 0) ? a.dictLen : 0; }
+    c.dst = a.dst; c.dstStride = a.dstStride;
+    return c;
 }
-__global__ __launch_bounds__(64) void k_dx_fill(CodecArgs a)
-{
-    const int j = blockIdx.x, b = blockIdx.y;
-    DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad || j > inf->tailFrom) return;
-    const int jt = inf->tailFrom;
-    const DxUnit* const units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
-    const DxUnit u = units[j];
-    if (j < jt && u.ip < 0) return;
-    const int64_t r = wave_dx_fill(dx_src(a, b), dx_len(a, b), a.dst + (int64_t)b * a.dstStride, dx_cap(a, b),
-                                   a.dxPtr + (int64_t)b * a.dxPtrStride, u.ip, u.op, u.stop, j == jt);
-    bool ok = r >= 0;
-    if (ok && j < jt) {                                              // where this unit stops is where the next one starts
-        int k = j + 1; while (k < jt && units[k].ip < 0) ++k;
-        ok = units[k].op == (int)r;
-    }
-    if ((threadIdx.x & 63u) == 0) { if (!ok) atomicOr(&inf->bad, 1); else if (j == jt) inf->outLen = (int)r; }
-}
-__global__ __launch_bounds__(256) void k_dx_jump(CodecArgs a)
-{
-    const int b = blockIdx.y, r = a.dxRound;
-    DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad || (r > 0 && !inf->moved[r - 1])) return;
-    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
-    if (p0 >= outLen) return;
-    if (dx_jump(a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen) && (threadIdx.x & 63u) == 0) inf->moved[r] = 1u;
-}
-__global__ __launch_bounds__(256) void k_dx_gather(CodecArgs a, unsigned long long* cnt)
-{
-    const int b = blockIdx.y;
-    const DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad) return;
-    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd(&cnt[3], 1ull);                                           // (plz4hip_ctx_counters: blocks this path answered)
+
+// A flavour at kernel level: the device flavour F for block b of the call, and the block's verdict behind the gather (one thread;
+// cnt: plz4hip_ctx_counters).
+struct KDx {                   // blocks up to kDxMaxOut
+    typedef DxF F;
+    static DEVM F flavour(const CodecArgs&, int) { return F{}; }
+    static DEVM void verdict(const CodecArgs& a, int b, int outLen, unsigned long long* cnt)
+    {
+        atomicAdd(&cnt[3], 1ull);                                           // (blocks this path answered)
         // (records: the payload's checksum is verified beside this path, k_dx_rec_hash; frame.go:114-127 rejects before it decodes)
         const bool hashBad = a.dxHashBad && a.dxHashBad[b];
         a.result[b] = hashBad ? 0 : outLen;
         if (a.status) a.status[b] = hashBad ? PLZ4HIP_BLK_HASH_MISMATCH : PLZ4HIP_BLK_OK;
     }
-    if (p0 >= outLen) return;
-    dx_gather(a.dst + (int64_t)b * a.dstStride, a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen);
+};
+struct KDxb {                  // raw blocks above kDxMaxOut (dxb_*): the stitch in three steps, long runs written down by the fill
+    typedef DxbF F;            // and run over the whole grid (k_dxb_runs), the jump rounds the call's largest capacity asks for
+    static DEVM F flavour(const CodecArgs& a, int b)
+    {
+        return F{a.dxbTG + (int64_t)b * a.dxbTGStride, a.dxbEnt + (int64_t)b * a.dxbGroups, a.dxbG,
+                 a.dxbRuns + (int64_t)b * a.dxbRunRoom, a.dxbRunRoom, a.dxbThr, a.dxbInfo + b};
+    }
+    static DEVM void verdict(const CodecArgs& a, int b, int outLen, unsigned long long* cnt)
+    {
+        atomicAdd(&cnt[3], 1ull);
+        if (dx_cap(a, b) > kDxMaxOut) { atomicAdd(&cnt[10], 1ull); atomicAdd(&cnt[12], (unsigned long long)min_(a.dxbInfo[b].runs, (uint32_t)a.dxbRunRoom)); }
+        a.result[b] = outLen;
+        if (a.status) a.status[b] = PLZ4HIP_BLK_OK;
+    }
+};
+struct KDxl {                  // history outside the block (dxl_*): k_dxl_link in front of the fill, k_dxl_resolve behind it; the verdicts
+    typedef DxlF F;            // are k_dxl_finish's (linked) or k_dxl_verdict's (under a dictionary), behind the gather
+    static DEVM F flavour(const CodecArgs& a, int) { return F{dxl_call(a), a.dxlMoved}; }
+    static DEVM void verdict(const CodecArgs&, int, int, unsigned long long*) {}
+};
+
+__global__ __launch_bounds__(64) void k_dx_tables(CodecArgs a)
+{
+    dx_stage_tables(dx_blk(a, blockIdx.y), blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(64) void k_dx_stitch(CodecArgs a)
+{
+    dx_stage_stitch(dx_blk(a, blockIdx.x));
+}
+template <class K> __global__ __launch_bounds__(64) void k_dx_fill(CodecArgs a)
+{
+    const int j = blockIdx.x, b = blockIdx.y;
+    dx_stage_fill(K::flavour(a, b), dx_blk(a, b), j);
+}
+template <class K> __global__ __launch_bounds__(256) void k_dx_jump(CodecArgs a)
+{
+    const int b = blockIdx.y, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    dx_stage_jump(K::flavour(a, b), dx_blk(a, b), a.dxRound, p0);
+}
+template <class K> __global__ __launch_bounds__(256) void k_dx_gather(CodecArgs a, unsigned long long* cnt)
+{
+    const int b = blockIdx.y, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
+    const DxBlk k = dx_blk(a, b);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && !k.info->bad) K::verdict(a, b, k.info->outLen, cnt);
+    dx_stage_gather(K::flavour(a, b), k, p0);
 }
 
-// ---- ... of raw blocks above kDxMaxOut (dxb_*, lz4_dx_device.inl): k_dx_tables as above, then the stitch in three steps, the fill
-// with its long runs written down, the runs over the whole grid, the jump rounds the call's largest capacity asks for, the gather.
-// Kernels of their own: the ones above stay what they are for blocks up to 4 MiB.
-__device__ __forceinline__ bool dxb_misfit(const CodecArgs& a, int b, int n)
-{
-    return dx_segments(n) > a.dxMaxSeg || n > a.dxTStride - 64 || dx_cap(a, b) > a.dxPtrStride - 64;
-}
+// ---- ... of raw blocks above kDxMaxOut (KDxb): the three steps of its stitch, and the listed runs behind its fill
 __global__ __launch_bounds__(256) void k_dxb_compose(CodecArgs a)
 {
     const int b = blockIdx.y, w = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);     // 128 waves to a group
-    const int g = w >> 7, sub = w & 127;
-    const int n = dx_len(a, b);
-    if (n <= 0 || dxb_misfit(a, b, n)) return;
-    if ((g + 1) * a.dxbG > dx_tail_from(dx_segments(n))) return;                     // (only groups with all their segments are hopped over)
-    dxb_compose(a.dxT + (int64_t)b * a.dxTStride, a.dxbTG + (int64_t)b * a.dxbTGStride, n, g, a.dxbG, sub);
+    dxb_stage_compose(KDxb::flavour(a, b), dx_blk(a, b), w >> 7, w & 127);
 }
 __global__ __launch_bounds__(64) void k_dxb_hop(CodecArgs a, unsigned long long* cnt)
 {
     const int b = blockIdx.x;
-    const int n = dx_len(a, b);
-    const int nseg = dx_segments(n);
-    const int bad = dxb_misfit(a, b, n) ? 1 : dxb_hop(dx_src(a, b), n, dx_cap(a, b), a.dxT + (int64_t)b * a.dxTStride, a.dxbTG + (int64_t)b * a.dxbTGStride,
-                                                      a.dxbEnt + (int64_t)b * a.dxbGroups, a.dxUnits + (int64_t)b * a.dxMaxSeg, nseg, a.dxbG);
-    if ((threadIdx.x & 63u) == 0) {
-        DxInfo inf; inf.bad = bad; inf.outLen = 0; inf.tailFrom = dx_tail_from(nseg); inf.pad = 0;
-        for (int r = 0; r <= kDxRounds; ++r) inf.moved[r] = 0;
-        a.dxInfo[b] = inf;
-        DxbInfo bi; bi.runs = 0; bi.pad = 0;
-        for (int r = 0; r <= kDxlMaxRounds; ++r) bi.moved[r] = 0;
-        a.dxbInfo[b] = bi;
-        if (b == 0) { cnt[11] = (unsigned long long)a.dxbRounds; cnt[12] = 0ull; }   // (plz4hip_ctx_counters: the last call of this kind)
-    }
+    dxb_stage_hop(KDxb::flavour(a, b), dx_blk(a, b));
+    if (b == 0 && (threadIdx.x & 63u) == 0) { cnt[11] = (unsigned long long)a.dxbRounds; cnt[12] = 0ull; }   // (plz4hip_ctx_counters: the last call of this kind)
 }
 __global__ __launch_bounds__(64) void k_dxb_units(CodecArgs a)
 {
     const int g = blockIdx.x, b = blockIdx.y;
-    if (a.dxInfo[b].bad) return;
-    const int n = dx_len(a, b), nseg = dx_segments(n);
-    if (g * a.dxbG >= dx_tail_from(nseg)) return;
-    dxb_group_units(dx_src(a, b), n, a.dxT + (int64_t)b * a.dxTStride, a.dxbEnt + (int64_t)b * a.dxbGroups,
-                    a.dxUnits + (int64_t)b * a.dxMaxSeg, nseg, a.dxbG, g);
-}
-__global__ __launch_bounds__(64) void k_dxb_fill(CodecArgs a)
-{
-    const int j = blockIdx.x, b = blockIdx.y;
-    DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad || j > inf->tailFrom) return;
-    const int jt = inf->tailFrom;
-    const DxUnit* const units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
-    const DxUnit u = units[j];
-    if (j < jt && u.ip < 0) return;
-    DxRuns runs; runs.list = a.dxbRuns + (int64_t)b * a.dxbRunRoom; runs.count = &a.dxbInfo[b].runs; runs.room = a.dxbRunRoom; runs.thr = a.dxbThr;
-    const int64_t r = wave_dx_fill<false, true>(dx_src(a, b), dx_len(a, b), a.dst + (int64_t)b * a.dstStride, dx_cap(a, b),
-                                                a.dxPtr + (int64_t)b * a.dxPtrStride, u.ip, u.op, u.stop, j == jt, &runs);
-    bool ok = r >= 0;
-    if (ok && j < jt) {                                              // where this unit stops is where the next one starts
-        int k = j + 1; while (k < jt && units[k].ip < 0) ++k;
-        ok = units[k].op == (int)r;
-    }
-    if ((threadIdx.x & 63u) == 0) { if (!ok) atomicOr(&inf->bad, 1); else if (j == jt) inf->outLen = (int)r; }
+    dxb_stage_units(KDxb::flavour(a, b), dx_blk(a, b), g);
 }
 __global__ __launch_bounds__(256) void k_dxb_runs(CodecArgs a)
 {
@@ -1412,31 +1379,6 @@ __global__ __launch_bounds__(256) void k_dxb_runs(CodecArgs a)
         for (uint32_t c = first; c < pieces; c += W) dxb_run_piece(r, c, dx_src(a, b), a.dst + (int64_t)b * a.dstStride, a.dxPtr + (int64_t)b * a.dxPtrStride);
         first = (first + W - pieces % W) % W;
     }
-}
-__global__ __launch_bounds__(256) void k_dxb_jump(CodecArgs a)
-{
-    const int b = blockIdx.y, r = a.dxRound;
-    const DxInfo* const inf = a.dxInfo + b;
-    DxbInfo* const bi = a.dxbInfo + b;
-    if (inf->bad || (r > 0 && !bi->moved[r - 1])) return;
-    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
-    if (p0 >= outLen) return;
-    if (dx_jump(a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen) && (threadIdx.x & 63u) == 0) bi->moved[r] = 1u;
-}
-__global__ __launch_bounds__(256) void k_dxb_gather(CodecArgs a, unsigned long long* cnt)
-{
-    const int b = blockIdx.y;
-    const DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad) return;
-    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd(&cnt[3], 1ull);                                           // (plz4hip_ctx_counters: blocks this path answered)
-        if (dx_cap(a, b) > kDxMaxOut) { atomicAdd(&cnt[10], 1ull); atomicAdd(&cnt[12], (unsigned long long)min_(a.dxbInfo[b].runs, (uint32_t)a.dxbRunRoom)); }
-        a.result[b] = outLen;
-        if (a.status) a.status[b] = PLZ4HIP_BLK_OK;
-    }
-    if (p0 >= outLen) return;
-    dx_gather(a.dst + (int64_t)b * a.dstStride, a.dxPtr + (int64_t)b * a.dxPtrStride, p0, outLen);
 }
 
 // records on the few-block path: which records are compressed payloads of a sane size (FrameReader._read's checks, blk/frame.go:
@@ -1464,18 +1406,9 @@ __global__ __launch_bounds__(64) void k_dx_rec_hash(CodecArgs a)
     if ((threadIdx.x & 63u) == 0) a.dxHashBad[b] = bad;
 }
 
-// ---- ... of blocks with history outside the block (dxl_*, lz4_dx_device.inl): k_dx_rec_prep / k_dx_rec_hash / k_dx_tables /
-// k_dx_stitch as above, then k_dxl_link, k_dxl_fill, k_dxl_resolve, the jump rounds, k_dxl_gather and, per chain, k_dxl_finish
-// (linked) or, per block, k_dxl_verdict (independent blocks under a dictionary; the flagged ones run k_decode_*_dict behind).
-__device__ __forceinline__ DxlCall dxl_call(const CodecArgs& a)
-{
-    DxlCall c;
-    c.ptr = a.dxPtr; c.P = a.dxPtrStride; c.nb = a.nBlocks; c.info = a.dxInfo; c.len = a.dxLen; c.first = a.dxlFirst; c.chain = a.dxlChain;
-    if (a.linked) { c.hist = a.window; c.histStride = 131072; c.histLen = a.windowLen; c.histLenAll = 0; }
-    else { c.hist = a.dict; c.histStride = 0; c.histLen = nullptr; c.histLenAll = (a.dict && a.dictLen > 0) ? a.dictLen : 0; }
-    c.dst = a.dst; c.dstStride = a.dstStride;
-    return c;
-}
+// ---- ... of blocks with history outside the block (KDxl): k_dx_rec_prep / k_dx_rec_hash / k_dx_tables / k_dx_stitch as above,
+// then k_dxl_link, the fill, k_dxl_resolve, the jump rounds, the gather and, per chain, k_dxl_finish (linked) or, per block,
+// k_dxl_verdict (independent blocks under a dictionary; the flagged ones run k_decode_*_dict behind).
 __device__ __forceinline__ DxlFin dxl_fin(const CodecArgs& a)
 {
     DxlFin f; f.hashBad = a.dxHashBad; f.moved = a.dxlMoved; f.rounds = a.dxlRounds; f.result = a.result; f.status = a.status;
@@ -1502,48 +1435,11 @@ __global__ __launch_bounds__(256) void k_dxl_link(CodecArgs a, unsigned long lon
     if (a.linked && dxl_chain_dead(a.dxLen, first, i, a.dxlDead ? a.dxlDead[ch] : 0)) a.dxInfo[i].bad = 1;
     for (int r = 0; r <= kDxlMaxRounds; ++r) a.dxlMoved[(int64_t)i * (kDxlMaxRounds + 1) + r] = 0;
 }
-__global__ __launch_bounds__(64) void k_dxl_fill(CodecArgs a)
-{
-    const int j = blockIdx.x, b = blockIdx.y;
-    DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad || j > inf->tailFrom) return;
-    const int jt = inf->tailFrom;
-    const DxUnit* const units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
-    const DxUnit u = units[j];
-    if (j < jt && u.ip < 0) return;
-    const int64_t r = wave_dx_fill<true>(dx_src(a, b), dx_len(a, b), a.dst + (int64_t)b * a.dstStride, dx_cap(a, b),
-                                         a.dxPtr + (int64_t)b * a.dxPtrStride, u.ip, u.op, u.stop, j == jt);
-    bool ok = r >= 0;
-    if (ok && j < jt) {
-        int k = j + 1; while (k < jt && units[k].ip < 0) ++k;
-        ok = units[k].op == (int)r;
-    }
-    if ((threadIdx.x & 63u) == 0) { if (!ok) atomicOr(&inf->bad, 1); else if (j == jt) inf->outLen = (int)r; }
-}
 __global__ __launch_bounds__(256) void k_dxl_resolve(CodecArgs a)
 {
     const int b = blockIdx.y, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
     if (p0 >= a.dxPtrStride) return;
     if (!dxl_resolve(dxl_call(a), b, p0, (int)a.dxPtrStride) && (threadIdx.x & 63u) == 0) atomicOr(&a.dxInfo[b].bad, 1);
-}
-__global__ __launch_bounds__(256) void k_dxl_jump(CodecArgs a)
-{
-    const int b = blockIdx.y, r = a.dxRound;
-    const DxInfo* const inf = a.dxInfo + b;
-    uint32_t* const moved = a.dxlMoved + (int64_t)b * (kDxlMaxRounds + 1);
-    if (inf->bad || (r > 0 && !moved[r - 1])) return;
-    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
-    if (p0 >= outLen) return;
-    if (dxl_jump(a.dxPtr, (uint32_t)((int64_t)a.nBlocks * a.dxPtrStride), (uint32_t)((int64_t)b * a.dxPtrStride), p0, outLen) && (threadIdx.x & 63u) == 0) moved[r] = 1u;
-}
-__global__ __launch_bounds__(256) void k_dxl_gather(CodecArgs a)
-{
-    const int b = blockIdx.y;
-    const DxInfo* const inf = a.dxInfo + b;
-    if (inf->bad) return;
-    const int outLen = inf->outLen, p0 = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 256;
-    if (p0 >= outLen) return;
-    dxl_gather(dxl_call(a), b, p0, outLen);
 }
 // independent blocks under a dictionary: which blocks the path answers
 __global__ __launch_bounds__(256) void k_dxl_verdict(CodecArgs a, unsigned long long* cnt)
@@ -2627,10 +2523,10 @@ void launch_dxb(plz4hip_ctx* c, hipStream_t s, CodecArgs& a, int nb, int64_t max
     hipLaunchKernelGGL(k_dxb_compose, dim3(L.groups * 32, nb), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_dxb_hop, dim3(nb), dim3(64), 0, s, a, c->d_counters);
     hipLaunchKernelGGL(k_dxb_units, dim3(L.groups, nb), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(k_dxb_fill, dim3(L.maxSeg, nb), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_dx_fill<KDxb>, dim3(L.maxSeg, nb), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_dxb_runs, dim3(1024, nb), dim3(256), 0, s, a);
-    for (int r = 0; r < w.rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxb_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-    hipLaunchKernelGGL(k_dxb_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+    for (int r = 0; r < w.rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump<KDxb>, dim3(chunks, nb), dim3(256), 0, s, a); }
+    hipLaunchKernelGGL(k_dx_gather<KDxb>, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
 }
 
 // Dx, and one group of DxGrouped: the stage train over a's nb blocks (the call, or the group's view of it), L: their layout.  hist:
@@ -2661,20 +2557,19 @@ int launch_dx_train(plz4hip_ctx* c, hipStream_t s, CodecArgs& a, int nb, const D
     hipLaunchKernelGGL(k_dx_tables, dim3(maxSeg, nb), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_dx_stitch, dim3(nb), dim3(64), 0, s, a);
     if (!hist) {
-        hipLaunchKernelGGL(k_dx_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
-        for (int r = 0; r < kDxRounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
+        hipLaunchKernelGGL(k_dx_fill<KDx>, dim3(maxSeg, nb), dim3(64), 0, s, a);
+        for (int r = 0; r < DxF::rounds(nb, maxOut); ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump<KDx>, dim3(chunks, nb), dim3(256), 0, s, a); }
         if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
-        hipLaunchKernelGGL(k_dx_gather, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
+        hipLaunchKernelGGL(k_dx_gather<KDx>, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
     } else {
-        // the copy chain of a call (of a group) can be as deep as its output is long: ceil(log2) rounds bring every pointer home, one more sees that
-        int rounds = 1;
-        while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * outB + kDxlHist) ++rounds;
+        // the copy chain of a call (of a group) can be as deep as its output and the history in front of it are long
+        const int rounds = DxlF::rounds(nb, maxOut);                           // dx_rounds_for(nb * outB + kDxlHist)
         a.dxlRounds = rounds;
         hipLaunchKernelGGL(k_dxl_link, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);
-        hipLaunchKernelGGL(k_dxl_fill, dim3(maxSeg, nb), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_dx_fill<KDxl>, dim3(maxSeg, nb), dim3(64), 0, s, a);
         hipLaunchKernelGGL(k_dxl_resolve, dim3((int)(L.pStride / 1024), nb), dim3(256), 0, s, a);
-        for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dxl_jump, dim3(chunks, nb), dim3(256), 0, s, a); }
-        hipLaunchKernelGGL(k_dxl_gather, dim3(chunks, nb), dim3(256), 0, s, a);
+        for (int r = 0; r < rounds; ++r) { a.dxRound = r; hipLaunchKernelGGL(k_dx_jump<KDxl>, dim3(chunks, nb), dim3(256), 0, s, a); }
+        hipLaunchKernelGGL(k_dx_gather<KDxl>, dim3(chunks, nb), dim3(256), 0, s, a, c->d_counters);
         if (hashed) HIPCHK(c, hipStreamWaitEvent(s, c->evDxHash, 0));
         if (hist == kHistLinked) hipLaunchKernelGGL(k_dxl_finish, dim3(nChG), dim3(64), 0, s, a, c->d_counters);
         else                     hipLaunchKernelGGL(k_dxl_verdict, dim3((nb + 255) / 256), dim3(256), 0, s, a, c->d_counters);

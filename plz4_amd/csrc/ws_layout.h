@@ -122,13 +122,6 @@ inline PieceLayout piece_layout(int per, int P, int recStride, int tabWords, boo
     L.total = c.at;
     return L;
 }
-// The two flavours' layouts by their earlier names (kept for one revision only: the emulation sources of the revision before this
-// one call them, and they are built against this tree whenever that revision's tests are run on it; nothing in this tree uses them --
-// delete them with the next change)
-typedef PieceLayout FxLayout;
-typedef PieceLayout MxLayout;
-inline FxLayout fx_layout(int per, int P, int recStride, bool hist, std::vector<WsTake>* log = nullptr) { return piece_layout(per, P, recStride, kFxTab, hist, log); }
-inline MxLayout mx_layout(int per, int P, int recStride, std::vector<WsTake>* log = nullptr) { return piece_layout(per, P, recStride, kMxTab, false, log); }
 
 // ---------------------------------------------------------------------------------------------------- HC levels 3..12 (c->h12)
 // Level 12 on independent blocks without dictionary runs in three phases per group of blocks (lz4hc12_device.inl):

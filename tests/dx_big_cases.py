@@ -14,7 +14,7 @@ from plz4_amd import synth
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_dx_big.cpp")
 SO = os.path.join(ROOT, "tests", "emu", "_build", "libemu_dx_big.so")
-DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "dx_big_train.h")] + \
+DEPS = [SRC, os.path.join(ROOT, "tests", "emu", "dx_train.h")] + \
        [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in ("lz4_dx_device.inl", "lz4_device.inl", "wave.h")]
 u8p = C.POINTER(C.c_uint8)
 

@@ -10,16 +10,17 @@
 //   4  the train with history outside the block, one call of a few records   (k_dx_rec_prep, k_dxl_*; linked chain behind a window,
 //      dictionary; a damaged block or a record with a lying size word at each place of the call)
 //   5  the record head (rec_head) on records of 0 .. 11 bytes at the end of a body
+//   6  the three flavours of the train on a call of two raw blocks laid out for the smaller one: the other on each side of every
+//      term of the misfit rule (a row of T, a row of pointers, the units)
+//   7  the three flavours on blocks of three and four segments with a unit that flags its block: the other units still run
+// Paths 3, 4, 6 and 7 run the stage bodies the kernels run, over the kernels' grids (tests/emu/dx_train.h).
 // Inputs: blocks built sequence by sequence around the vector path's boundaries (tests/lz4blocks.py is the same generator), then
 // truncated, bit-flipped, 0xFF-ed and with zeroed offsets, over the reference's end-of-output margins as capacities.
 // `--long`: a wider set (minutes).  Prints one line of counts; exit status 1 on a wrong answer, the sanitizer's on a bad access.
 #define PLZ4_EMU 1
-#include "../../plz4_amd/csrc/lz4_dx_device.inl"
+#include "dx_train.h"
 #include "../../oracle/plz4_oracle.h"
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
 
 int plz4_emu_descending = 0;
 
@@ -121,30 +122,14 @@ void run_dx(const std::vector<uint8_t>& comp, int n, int cap, int caseNo)
 {
     Exact src((size_t)n, srcShift++ & 15);
     if (n) memcpy(src.p, comp.data(), (size_t)n);
-    const int64_t maxIn = n > 0 ? n : 1, maxOut = cap > 0 ? cap : 1;
-    const size_t tStride = dx_t_stride(maxIn), pStride = dx_ptr_stride(maxOut);
-    const int maxSeg = dx_max_seg(maxIn), nseg = dx_segments(n), jt = dx_tail_from(nseg);
-    Exact Tb(tStride * 8), Pb(pStride * 4), Ub((size_t)maxSeg * sizeof(DxUnit)), dst((size_t)cap), d3((size_t)cap);
-    uint64_t* const T = (uint64_t*)Tb.p; uint32_t* const ptr = (uint32_t*)Pb.p; DxUnit* const units = (DxUnit*)Ub.p;
-    for (size_t p = 0; p < pStride; ++p) ptr[p] = (uint32_t)p;                         // k_dx_tables
-    if (n > 0 && (int64_t)n <= (int64_t)tStride - 64) for (int j = nseg - 1; j >= 0; --j) dx_segment_table(src.p, n, j, T);
-    int64_t outLen = -1;
-    bool bad = nseg > maxSeg || (int64_t)n > (int64_t)tStride - 64 || (int64_t)cap > (int64_t)pStride - 64 || dx_stitch(src.p, n, cap, T, units, nseg) != 0;   // k_dx_stitch
-    for (int j = jt; j >= 0 && !bad; --j) {                                             // k_dx_fill
-        if (j < jt && units[j].ip < 0) continue;
-        const int64_t r = wave_dx_fill(src.p, n, dst.p, cap, ptr, units[j].ip, units[j].op, units[j].stop, j == jt);
-        if (r < 0) { bad = true; break; }
-        if (j == jt) outLen = r;
-        else { int k = j + 1; while (k < jt && units[k].ip < 0) ++k; if (units[k].op != (int)r) wrong("dx: units do not meet", caseNo, n, cap, (int)r, units[k].op); }
-    }
+    Exact dst((size_t)cap), d3((size_t)cap);
+    DxEmuTrain t;
+    const uint8_t* const sp = src.p; const int32_t len = n, room = cap;
+    dx_emu_train(DxF{}, t, DxEmuCall{1, &sp, &len, &room, dst.p, 0}, n > 0 ? n : 1, cap > 0 ? cap : 1);
+    if (t.disagree) wrong("dx: units do not meet", caseNo, n, cap, 0, 0);
     ++nDx;
-    if (bad) return;
-    for (int rounds = 0; rounds < kDxRounds; ++rounds) {                                // k_dx_jump
-        bool moved = false;
-        for (int p0 = (((int)outLen - 1) / 256) * 256; p0 >= 0; p0 -= 256) moved |= dx_jump(ptr, p0, (int)outLen);
-        if (!moved) break;
-    }
-    for (int p0 = 0; p0 < (int)outLen; p0 += 256) dx_gather(dst.p, ptr, p0, (int)outLen);  // k_dx_gather
+    if (t.info[0].bad) return;
+    const int outLen = t.info[0].outLen;
     const int want = orc_decompress_safe(src.p, n, d3.p, cap);
     if ((int)outLen != want) wrong("dx", caseNo, n, cap, (int)outLen, want);
     if (want > 0 && memcmp(dst.p, d3.p, (size_t)want)) wrong("dx: bytes", caseNo, n, cap, (int)outLen, want);
@@ -169,60 +154,28 @@ void run_dxl(const std::vector<std::vector<uint8_t>>& recs, const std::vector<in
     off[nb] = (int64_t)total;
     Exact body(total, srcShift++ & 15);
     for (int i = 0; i < nb; ++i) { st32u(body.p + off[i], i == lie ? (uint32_t)bsz + 1u : (uint32_t)recs[i].size()); if (!recs[i].empty()) memcpy(body.p + off[i] + 4, recs[i].data(), recs[i].size()); }
-    const size_t tStride = dx_t_stride(bsz), P = dx_ptr_stride(maxCap);
-    const int maxSeg = dx_max_seg(bsz);
     const int64_t dstStride = maxCap;
-    Exact Tb((size_t)nb * tStride * 8), Pb((size_t)nb * P * 4), Ub((size_t)nb * maxSeg * sizeof(DxUnit)), dst((size_t)nb * dstStride), win(131072), winRef(65536);
+    Exact dst((size_t)nb * dstStride), win(131072), winRef(65536);
     Exact dictCopy(linked ? 0 : (size_t)histLen);
-    std::vector<DxInfo> info(nb); std::vector<int32_t> len(nb), first(nb, 0), chain(nb, 0);
-    std::vector<uint32_t> moved((size_t)nb * (kDxlMaxRounds + 1), 0);
-    uint64_t* const T = (uint64_t*)Tb.p; uint32_t* const ptr = (uint32_t*)Pb.p; DxUnit* const units = (DxUnit*)Ub.p;
+    std::vector<int32_t> len(nb), first(nb, 0), chain(nb, 0), room(caps.begin(), caps.end());
+    std::vector<const uint8_t*> src(nb);
     int winLen = linked ? histLen : 0;
     memset(dst.p, kFill, (size_t)nb * (size_t)dstStride);
     if (linked) { if (histLen) memcpy(win.p, hist, (size_t)histLen); }
     else { if (histLen) memcpy(dictCopy.p, hist, (size_t)histLen); for (int i = 0; i < nb; ++i) first[i] = i; }
-    DxlCall c;
-    c.ptr = ptr; c.P = (int64_t)P; c.nb = nb; c.info = info.data(); c.len = len.data(); c.first = first.data(); c.chain = chain.data();
+    DxlCall c{};
+    c.first = first.data(); c.chain = chain.data();
     if (linked) { c.hist = win.p; c.histStride = 131072; c.histLen = &winLen; c.histLenAll = 0; }
     else { c.hist = dictCopy.p; c.histStride = 0; c.histLen = nullptr; c.histLenAll = histLen; }
-    c.dst = dst.p; c.dstStride = dstStride;
-    for (int b = 0; b < nb; ++b) {
-        len[b] = dx_rec_len(body.p + off[b], off[b + 1] - off[b], bsz, false, maxCap);  // k_dx_rec_prep
-        const uint8_t* const s = body.p + off[b] + 4; const int n = len[b];
-        for (size_t p = 0; p < P; ++p) ptr[(size_t)b * P + p] = (uint32_t)p;             // k_dx_tables, k_dx_stitch, k_dxl_fill
-        const int nseg = dx_segments(n), jt = dx_tail_from(nseg);
-        DxUnit* const u = units + (size_t)b * maxSeg;
-        info[b].bad = 1; info[b].outLen = 0; info[b].tailFrom = jt;
-        if (n <= 0) continue;
-        for (int j = nseg - 1; j >= 0; --j) dx_segment_table(s, n, j, T + (size_t)b * tStride);
-        if (linked && dxl_chain_dead(len.data(), 0, b, 0)) continue;                    // k_dxl_link
-        if (nseg > maxSeg || caps[b] > (int64_t)P - 64 || dx_stitch(s, n, caps[b], T + (size_t)b * tStride, u, nseg) != 0) continue;
-        bool bad = false;
-        for (int j = jt; j >= 0 && !bad; --j) {
-            if (j < jt && u[j].ip < 0) continue;
-            const int64_t r = wave_dx_fill<true>(s, n, dst.p + (int64_t)b * dstStride, caps[b], ptr + (size_t)b * P, u[j].ip, u[j].op, u[j].stop, j == jt);
-            if (r < 0) { bad = true; break; }
-            if (j == jt) info[b].outLen = (int)r;
-            else { int k = j + 1; while (k < jt && u[k].ip < 0) ++k; if (u[k].op != (int)r) wrong("dxl: units do not meet", caseNo, n, caps[b], (int)r, u[k].op); }
-        }
-        info[b].bad = bad ? 1 : 0;
-    }
-    for (int b = nb - 1; b >= 0; --b)                                                   // k_dxl_resolve
-        for (int64_t p0 = 0; p0 < (int64_t)P; p0 += 256) if (!dxl_resolve(c, b, (int)p0, (int)P)) info[b].bad = 1;
-    int rounds = 1;
-    while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)nb * maxCap + kDxlHist) ++rounds;
-    const uint32_t hist0 = dxl_hist0(c);
-    for (int r = 0; r < rounds; ++r)                                                    // k_dxl_jump
-        for (int b = nb - 1; b >= 0; --b) {
-            uint32_t* const mv = &moved[(size_t)b * (kDxlMaxRounds + 1)];
-            if (info[b].bad || (r > 0 && !mv[r - 1])) continue;
-            const int outLen = info[b].outLen;
-            for (int p0 = outLen > 0 ? ((outLen - 1) / 256) * 256 : -1; p0 >= 0; p0 -= 256)
-                if (dxl_jump(ptr, hist0, (uint32_t)((int64_t)b * (int64_t)P), p0, outLen)) mv[r] = 1u;
-        }
-    for (int b = 0; b < nb; ++b) if (!info[b].bad) for (int p0 = 0; p0 < info[b].outLen; p0 += 256) dxl_gather(c, b, p0, info[b].outLen);   // k_dxl_gather
+    for (int b = 0; b < nb; ++b) { len[b] = dx_rec_len(body.p + off[b], off[b + 1] - off[b], bsz, false, maxCap); src[b] = body.p + off[b] + 4; }   // k_dx_rec_prep
+    DxEmuTrain t;
+    DxInfo*& info = t.info;
+    dx_emu_train(DxlF{}, t, DxEmuCall{nb, src.data(), len.data(), room.data(), dst.p, dstStride}, c, nb, bsz, maxCap, true, 0,
+                 [&] { for (int b = 0; b < nb; ++b) if (linked && dxl_chain_dead(len.data(), 0, b, 0)) info[b].bad = 1; });   // k_dxl_link
+    if (t.disagree) wrong("dxl: units do not meet", caseNo, nb, maxCap, 0, 0);
+    const int rounds = t.launched;
     std::vector<int32_t> result(nb, 0), status(nb, 0);
-    DxlFin f; f.hashBad = nullptr; f.moved = moved.data(); f.rounds = rounds; f.result = result.data(); f.status = status.data();
+    DxlFin f; f.hashBad = nullptr; f.moved = t.moved; f.rounds = rounds; f.result = result.data(); f.status = status.data();
     Exact lds(kDecLdsBytes);
     auto rec = [&](int i, const uint8_t* h, int hl, int* r, int* st, bool* stored) {     // decode_one_record, without checksums
         uint32_t word;
@@ -304,6 +257,88 @@ void run_heads()
             }
             ++nHead;
         }
+    }
+}
+
+// path 6: a call of two raw blocks whose workspace is laid out for maxIn / maxOut, through flavour fl of the train (dx_emu_raw_call:
+// DxF, DxbF, DxlF under the dictionary dict).  Block 0 (x) is the one under test, block 1 the sibling that fits.  misfit: x is larger
+// than the rows were sized for and must be left; else it must be answered.  The sibling is answered either way, and every answer is
+// the oracle's.  Both outputs lie in one allocation at a stride of the larger capacity, source and outputs are exact.
+long nMisfit = 0;
+void run_pair(const int fl, const Block& x, const int capX, const Block& sib, const int64_t maxIn, const int64_t maxOut, const bool misfit,
+              const uint8_t* dict, const int dictLen, const int caseNo)
+{
+    const Block* const blk[2] = {&x, &sib};
+    const int32_t len[2] = {(int32_t)x.comp.size(), (int32_t)sib.comp.size()}, cap[2] = {capX, (int32_t)sib.plain.size()};
+    Exact s0((size_t)len[0], srcShift++ & 15), s1((size_t)len[1], srcShift++ & 15);
+    memcpy(s0.p, x.comp.data(), (size_t)len[0]); memcpy(s1.p, sib.comp.data(), (size_t)len[1]);
+    const uint8_t* const src[2] = {s0.p, s1.p};
+    const int64_t dstStride = cap[0] > cap[1] ? cap[0] : cap[1];
+    Exact dst((size_t)(dstStride + cap[1]));
+    int32_t answer[2] = {0, 0};
+    if (dx_emu_raw_call(fl, DxEmuCall{2, src, len, cap, dst.p, dstStride}, maxIn, maxOut, fl == 2 ? dict : nullptr, fl == 2 ? dictLen : 0, 0, answer))
+        wrong("pair: units do not meet", caseNo, len[0], capX, fl, 0);
+    for (int b = 0; b < 2; ++b) {
+        if (b == 0 && misfit) { if (answer[0] != kDxEmuLeft) wrong("pair: a misfit block is answered", caseNo, len[0], capX, answer[0], kDxEmuLeft); continue; }
+        Exact ref((size_t)cap[b]);
+        const int want = fl == 2 ? orc_decompress_safe_dict(src[b], len[b], ref.p, cap[b], dict, dictLen) : orc_decompress_safe(src[b], len[b], ref.p, cap[b]);
+        if (answer[b] != want || want != (int)blk[b]->plain.size()) wrong(b ? "pair: the sibling" : "pair: the fitting block", caseNo, len[b], cap[b], answer[b], want);
+        if (memcmp(dst.p + b * dstStride, ref.p, (size_t)want)) wrong("pair: bytes", caseNo, len[b], cap[b], answer[b], want);
+    }
+    ++nMisfit;
+}
+// a valid block whose compressed size is at least minComp, and is `mod` modulo 64 (mod < 0: any)
+Block block_of(Rng& r, const int minComp, const int mod, const uint8_t* dict = nullptr, const int dictLen = 0)
+{
+    for (int nseq = minComp / 150 + 1;; ++nseq) {
+        Block b = make_block(r, nseq, dict, dictLen);
+        if ((int)b.comp.size() >= minComp && (mod < 0 || (int)b.comp.size() % 64 == mod)) return b;
+    }
+}
+// both sides of every term of the misfit rule (dx_misfit, lz4_dx_device.inl), for the three flavours
+void run_misfits(Rng& r, int& caseNo)
+{
+    Exact dict(5000);
+    for (int i = 0; i < 5000; ++i) dict.p[i] = (uint8_t)r.next();
+    for (int fl = 0; fl < 3; ++fl) {
+        const uint8_t* const d = fl == 2 ? dict.p : nullptr; const int dl = fl == 2 ? 5000 : 0;
+        const Block sib = block_of(r, 200, -1, d, dl);
+        const Block x0 = block_of(r, 1500, 0, d, dl), x1 = block_of(r, 1500, 1, d, dl), x3 = block_of(r, 2 * kDxSeg + 64, -1, d, dl);
+        // n == tStride - 64 and n == tStride - 63: a row of T for blocks of up to maxIn bytes has maxIn rounded up to 64, + 64 entries
+        const int p0 = (int)x0.plain.size(), p1 = (int)x1.plain.size(), p3 = (int)x3.plain.size();
+        if ((int)dx_t_stride((int64_t)x0.comp.size()) - 64 != (int)x0.comp.size() || (int)dx_t_stride((int64_t)x1.comp.size() - 1) - 63 != (int)x1.comp.size()) wrong("pair: the edge of T", caseNo, 0, 0, 0, 0);
+        run_pair(fl, x0, p0, sib, (int64_t)x0.comp.size(), p0, false, d, dl, caseNo++);
+        run_pair(fl, x1, p1, sib, (int64_t)x1.comp.size() - 1, p1, true, d, dl, caseNo++);
+        // cap == pStride - 64 and cap == pStride - 63
+        const int64_t P = fl == 1 ? (int64_t)dxb_ptr_stride(p0) : (int64_t)dx_ptr_stride(p0);
+        run_pair(fl, x0, (int)P - 64, sib, (int64_t)x0.comp.size(), p0, false, d, dl, caseNo++);
+        run_pair(fl, x0, (int)P - 63, sib, (int64_t)x0.comp.size(), p0, true, d, dl, caseNo++);
+        // dx_segments(n) == maxSeg and == maxSeg + 1: three segments in a call laid out for three, and for two
+        run_pair(fl, x3, p3, sib, (int64_t)x3.comp.size(), p3, false, d, dl, caseNo++);
+        run_pair(fl, x3, p3, sib, 2 * kDxSeg, p3, true, d, dl, caseNo++);
+    }
+}
+
+// path 7: a flagged unit does not stop the others.  Blocks of three and of four segments with an offset zeroed in the middle segment:
+// the stitch follows the chain as ever, the unit that meets the offset flags the block, and the driver goes on through every unit
+// of the grid as the kernel does (dx_stage_fill) -- the block is left, and no access leaves an allocation.
+long nFlagged = 0;
+void run_flagged(Rng& r, int& caseNo)
+{
+    for (int segs = 3; segs <= 4; ++segs) for (int fl = 0; fl < 3; ++fl) {
+        Block b = block_of(r, (segs - 1) * kDxSeg + 64, -1);
+        if (dx_segments((int)b.comp.size()) != segs) wrong("flagged: the generator", caseNo, (int)b.comp.size(), 0, dx_segments((int)b.comp.size()), segs);
+        size_t k = 0;
+        while (k < b.offAt.size() && b.offAt[k] < kDxSeg + kDxSeg / 2) ++k;
+        if (k >= b.offAt.size() || b.offAt[k] >= 2 * kDxSeg) wrong("flagged: no offset in the middle segment", caseNo, (int)b.comp.size(), 0, 0, 0);
+        b.comp[(size_t)b.offAt[k]] = 0; b.comp[(size_t)b.offAt[k] + 1] = 0;
+        const int n = (int)b.comp.size(), cap = (int)b.plain.size();
+        Exact src((size_t)n, srcShift++ & 15), dst((size_t)cap);
+        memcpy(src.p, b.comp.data(), (size_t)n);
+        const uint8_t* const sp = src.p; const int32_t len = n, room = cap; int32_t answer = 0;
+        if (dx_emu_raw_call(fl, DxEmuCall{1, &sp, &len, &room, dst.p, 0}, n, cap, nullptr, 0, 0, &answer)) wrong("flagged: units do not meet", caseNo, n, cap, fl, 0);
+        if (answer != kDxEmuLeft) wrong("flagged: the block is answered", caseNo, n, cap, answer, kDxEmuLeft);
+        ++nFlagged; ++caseNo;
     }
 }
 
@@ -442,7 +477,12 @@ int main(int argc, char** argv)
         }
     }
 
+    plz4_emu_descending = 0;
+    run_misfits(r, caseNo);
+    run_flagged(r, caseNo);
+
     printf("decode bounds: %ld one-wave decodes, %ld under a dictionary, %ld few-block runs (%ld answered), %ld calls with history (%ld blocks answered), "
-           "%ld record heads: the oracle's answers, no access outside a buffer\n", nWave, nDict, nDx, nDxTaken, nDxl, nDxlTaken, nHead);
+           "%ld record heads, %ld pairs around the misfit rule, %ld blocks with a flagged unit: the oracle's answers, no access outside a buffer\n",
+           nWave, nDict, nDx, nDxTaken, nDxl, nDxlTaken, nHead, nMisfit, nFlagged);
     return 0;
 }

@@ -1,7 +1,7 @@
 // The few-block decoder's big path (raw blocks above 4 MiB + 8; dxb_* in plz4_amd/csrc/lz4_dx_device.inl) on hostile input reads
 // no byte outside [src, src + n) and writes none outside [dst, dst + cap), and every workspace access stays inside what
 // launch_decode reserves: a program of its own for the address and undefined-behaviour sanitizers (never loaded into Python, never
-// run on a GPU).  The stage train is tests/emu/dx_big_train.h: tables, pointers, units, the groups' composed rows and entries and
+// run on a GPU).  The stage train is tests/emu/dx_train.h: tables, pointers, units, the groups' composed rows and entries and
 // the run list are heap allocations of exactly the reserved size, source and destination of exactly n and cap bytes.  What the
 // train answers is checked against the oracle (oracle/plz4_oracle.c), and the run list never holds more than its reserved count.
 // Inputs: blocks of 5-6 MiB built sequence by sequence around the vector path's boundaries (the generator of
@@ -10,7 +10,7 @@
 // sizes 2, 4 and the default and run thresholds of 4 KiB and the default.
 // Prints one line of counts; exit status 1 on a wrong answer, the sanitizer's on a bad access.
 #define PLZ4_EMU 1
-#include "dx_big_train.h"
+#include "dx_train.h"
 #include "../../oracle/plz4_oracle.h"
 #include <stdio.h>
 #include <vector>
@@ -87,15 +87,15 @@ long nRun = 0, nTaken = 0, nRuns = 0;
 // one block of a call whose strides are maxIn / maxOut
 void run(const std::vector<uint8_t>& comp, int n, int cap, int64_t maxIn, int64_t maxOut, int G, int thr, int caseNo)
 {
-    dxbig::Heap<uint8_t> src((size_t)n), dst((size_t)cap), ref((size_t)cap);
+    DxEmuHeap<uint8_t> src((size_t)n), dst((size_t)cap), ref((size_t)cap);
     if (n) memcpy(src.p, comp.data(), (size_t)n);
-    dxbig::Stats st;
-    const int r = dxbig::train(src.p, n, dst.p, cap, maxIn, maxOut, G, thr, &st);
+    DxbEmuStats st;
+    const int r = dxb_emu_block(src.p, n, dst.p, cap, maxIn, maxOut, G, thr, &st);
     ++nRun;
     if (memcmp(src.p, comp.data(), (size_t)n)) wrong("source changed", caseNo, n, cap, r, 0);
-    if (r == dxbig::kUnitsDisagree) wrong("units do not meet", caseNo, n, cap, r, 0);
-    if (r == dxbig::kListOverrun || st.runs > st.room) wrong("run list beyond its reserved count", caseNo, n, cap, st.runs, st.room);
-    if (r == dxbig::kLeft) return;
+    if (r == kDxEmuUnitsDisagree) wrong("units do not meet", caseNo, n, cap, r, 0);
+    if (r == kDxEmuListOverrun || st.runs > st.room) wrong("run list beyond its reserved count", caseNo, n, cap, st.runs, st.room);
+    if (r == kDxEmuLeft) return;
     const int want = orc_decompress_safe(src.p, n, ref.p, cap);
     if (r != want) wrong("dx big", caseNo, n, cap, r, want);
     if (want > 0 && memcmp(dst.p, ref.p, (size_t)want)) wrong("dx big: bytes", caseNo, n, cap, r, want);

@@ -1,13 +1,10 @@
 // Lane-emulation harness of a LINKED decode call cut into groups of consecutive blocks (launch_decode in plz4_amd/csrc/plz4hip.hip;
 // dxl_* in plz4_amd/csrc/lz4_dx_device.inl): the call's plan (dxl_group), and per group the stage train over the group's view of the
-// call -- record prep and checksums, tables, stitch, fill, resolve, jump rounds sized by the group's output, gather -- then per
+// call -- record prep and checksums, then the stages of dx_train.h with the jump rounds sized by the group's output -- then per
 // chain the finish stage (dxl_finish, the body k_dxl_finish runs) with the window, its length and the chain's dead word carried from
 // group to group.  Test infrastructure only: built into tests/emu/_build/, never loaded by plz4_amd, not a CPU fallback.
 #define PLZ4_EMU 1
-#include "../../plz4_amd/csrc/lz4_dx_device.inl"
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
+#include "dx_train.h"
 
 int plz4_emu_descending = 0;
 
@@ -63,17 +60,9 @@ extern "C" int emu_dxlg_decode(int nb, const uint8_t* const* rec, const int32_t*
                                int group, const int32_t* forcedRounds, uint8_t* dst, int64_t dstStride, int dstCap,
                                int32_t* result, int32_t* status, int32_t* taken, int64_t* counters)
 {
-    const int64_t outB = dstCap < kDxMaxOut ? dstCap : kDxMaxOut;
-    const int64_t P = (outB + 64 + 1023) / 1024 * 1024, tStride = ((int64_t)bsz + 64 + 63) / 64 * 64;
-    const int maxSeg = dx_segments(bsz);
     const int G = group < nb ? group : nb;
-    std::vector<uint8_t> in((size_t)G * tStride, 0);
-    std::vector<uint64_t> T((size_t)G * tStride, 0);
-    std::vector<DxUnit> units((size_t)G * (maxSeg + 1));
-    std::vector<DxInfo> info(G);
-    std::vector<uint32_t> ptr((size_t)G * P);
-    std::vector<int32_t> dxLen(G), hashBad(G), first(G), chain(G);
-    std::vector<uint32_t> moved((size_t)G * (kDxlMaxRounds + 1));
+    std::vector<const uint8_t*> src(G);
+    std::vector<int32_t> dxLen(G), hashBad(G), first(G), chain(G), caps(G, dstCap);
     std::vector<int32_t> dead(nCh, 0);
     counters[0] = counters[1] = counters[2] = 0;
     for (int i = 0; i < nb; ++i) taken[i] = 0;
@@ -96,11 +85,8 @@ extern "C" int emu_dxlg_decode(int nb, const uint8_t* const* rec, const int32_t*
                 if (!(word & 0x80000000u) && sz <= bsz && (int64_t)sz + 4 + (blockChecksum ? 4 : 0) <= v.recLen[i]) n = sz;
             }
             dxLen[i] = n; hashBad[i] = 0;
-            memset(&in[(size_t)i * tStride], 0, (size_t)tStride);
-            if (n > 0) memcpy(&in[(size_t)i * tStride], v.rec[i] + 4, (size_t)n);
+            src[i] = v.rec[i] + 4;
             if (n >= 0 && blockChecksum) hashBad[i] = wave_xxh32(v.rec[i] + 4, n) != ld32u(v.rec[i] + 4 + n);
-            for (int64_t p = 0; p < P; ++p) ptr[(size_t)i * P + p] = (uint32_t)p;
-            for (int r = 0; r <= kDxlMaxRounds; ++r) moved[(size_t)i * (kDxlMaxRounds + 1) + r] = 0;
         }
         // k_dxl_link
         for (int i = 0; i < ng; ++i) {
@@ -108,51 +94,17 @@ extern "C" int emu_dxlg_decode(int nb, const uint8_t* const* rec, const int32_t*
             while (ch + 1 < nChG && dxl_chain_lo(cf, g.g0, ng, ch + 1) <= i) ++ch;
             first[i] = dxl_chain_lo(cf, g.g0, ng, ch); chain[i] = ch;
         }
-        DxlCall c;
-        c.ptr = ptr.data(); c.P = P; c.nb = ng; c.info = info.data(); c.len = dxLen.data(); c.first = first.data(); c.chain = chain.data();
+        DxlCall c{};
+        c.first = first.data(); c.chain = chain.data();
         c.hist = win; c.histStride = 131072; c.histLen = winLen; c.histLenAll = 0;
-        c.dst = v.dst; c.dstStride = dstStride;
-        // k_dx_tables, k_dx_stitch, k_dxl_fill
-        for (int b = 0; b < ng; ++b) {
-            const uint8_t* s = &in[(size_t)b * tStride]; const int n = dxLen[b];
-            const int nseg = dx_segments(n), jt = dx_tail_from(nseg);
-            DxUnit* u = &units[(size_t)b * (maxSeg + 1)];
-            info[b].bad = 1; info[b].outLen = 0; info[b].tailFrom = jt;
-            if (n <= 0) continue;
-            for (int j = nseg - 1; j >= 0; --j) dx_segment_table(s, n, j, &T[(size_t)b * tStride]);
-            if (dstCap > P - 64 || dx_stitch(s, n, dstCap, &T[(size_t)b * tStride], u, nseg) != 0) continue;
-            bool bad = false;
-            for (int j = jt; j >= 0 && !bad; --j) {
-                if (j < jt && u[j].ip < 0) continue;
-                const int64_t r = wave_dx_fill<true>(s, n, v.dst + (int64_t)b * dstStride, dstCap, &ptr[(size_t)b * P], u[j].ip, u[j].op, u[j].stop, j == jt);
-                if (r < 0) { bad = true; break; }
-                if (j == jt) info[b].outLen = (int)r;
-                else { int k = j + 1; while (k < jt && u[k].ip < 0) ++k; if (u[k].op != (int)r) return -888888; }
-            }
-            info[b].bad = bad ? 1 : 0;
-        }
-        // k_dxl_resolve over every entry of every block
-        for (int b = ng - 1; b >= 0; --b)
-            for (int64_t p0 = 0; p0 < P; p0 += 256) if (!dxl_resolve(c, b, (int)p0, (int)P)) info[b].bad = 1;
-        // the jump rounds follow the group's own output
-        int rounds = 1;
-        while (rounds < kDxlMaxRounds && ((int64_t)1 << (rounds - 1)) < (int64_t)ng * outB + kDxlHist) ++rounds;
-        if (forcedRounds && forcedRounds[gi] > 0) rounds = forcedRounds[gi];
-        const uint32_t hist0 = dxl_hist0(c);
-        for (int r = 0; r < rounds; ++r)
-            for (int b = ng - 1; b >= 0; --b) {
-                uint32_t* mv = &moved[(size_t)b * (kDxlMaxRounds + 1)];
-                if (info[b].bad || (r > 0 && !mv[r - 1])) continue;
-                const int outLen = info[b].outLen;
-                for (int p0 = outLen > 0 ? ((outLen - 1) / 256) * 256 : -1; p0 >= 0; p0 -= 256)
-                    if (dxl_jump(c.ptr, hist0, (uint32_t)((int64_t)b * P), p0, outLen)) mv[r] = 1u;
-            }
-        for (int b = 0; b < ng; ++b) {
-            if (info[b].bad) continue;
-            for (int p0 = 0; p0 < info[b].outLen; p0 += 256) dxl_gather(c, b, p0, info[b].outLen);
-        }
+        // the group's layout, as launch_decode's layout_for(ng) makes it; the jump rounds follow the group's own output
+        DxEmuTrain t;
+        dx_emu_train(DxlF{}, t, DxEmuCall{ng, src.data(), dxLen.data(), caps.data(), v.dst, dstStride}, c, G, bsz, dstCap, true, nCh, [] {},
+                     forcedRounds ? forcedRounds[gi] : 0);
+        if (t.disagree) return kDxEmuUnitsDisagree;
+        const int rounds = t.launched;
         // k_dxl_finish: one wave per chain of the group
-        DxlFin f; f.hashBad = blockChecksum ? hashBad.data() : nullptr; f.moved = moved.data(); f.rounds = rounds; f.result = v.result; f.status = v.status;
+        DxlFin f; f.hashBad = blockChecksum ? hashBad.data() : nullptr; f.moved = t.moved; f.rounds = rounds; f.result = v.result; f.status = v.status;
         RecEmu recEmu{v};
         for (int ch = nChG - 1; ch >= 0; --ch) {
             const int lo = dxl_chain_lo(cf, g.g0, ng, ch), hi = dxl_chain_lo(cf, g.g0, ng, ch + 1);

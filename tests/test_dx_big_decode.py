@@ -1,5 +1,5 @@
 """The few-block decoder's big path (raw blocks above 4 MiB + 8; dxb_* in plz4_amd/csrc/lz4_dx_device.inl) on the lane-emulated
-build, stage by stage as launch_decode enqueues it (tests/emu/dx_big_train.h): whatever it answers is LZ4_decompress_safe's result
+build, stage by stage as launch_decode enqueues it (tests/emu/dx_train.h): whatever it answers is LZ4_decompress_safe's result
 (the oracle's, same bytes and capacity), a valid block with room is ANSWERED, and what it leaves (LEFT) is the one-wave decoder's,
 whose parity is tested elsewhere.  GPU: tests/test_gpu_dx_big_decode.py."""
 import numpy as np
