@@ -99,6 +99,16 @@
  * PLZ4HIP_MX_PIECE_KIB / PLZ4HIP_MX_WARMUP_KIB and with the same workspace (about 5 bytes per input byte, kept until
  * plz4hip_ctx_trim); blocks of at most 4 KiB under a dictionary context keep their wave-wide parser.  Same bytes, results and
  * capacity verdicts; a call the path does not take, or whose workspace is refused, runs one wavefront per block.
+ * A call at levels 3..12 of at most PLZ4HIP_HB_MAX_BLOCKS (64; 0: off; read per call) blocks of at most 4 MiB -- independent ones, or blocks
+ * behind a dictionary / linked blocks on the list path (compress_batch, compress_batch_dict, encode_records, encode_records_ex,
+ * dev_compress, dev_encode_records, dev_encode_records_ex and the routes that end there; host buffers: per staging chunk) -- whose
+ * largest segment + block is above one piece has the chains and per-hash lists in front of its walk built in pieces of
+ * PLZ4HIP_HB_PIECE_KIB (64, clamped to 1..4096) KiB of positions by many workgroups per block (count, scan, fill, chain: four launches, nobody waits for
+ * anybody) instead of one wavefront per block.  The arrays are the same, and so are the searches and walks behind them: output,
+ * results and capacity verdicts are unchanged.  The workspace is two 128 KiB tables per piece (16 MiB per 4 MiB block at 64 KiB
+ * pieces), kept until plz4hip_ctx_trim; a call the path does not take -- more blocks, raw blocks above 4 MiB, the calls of 2048
+ * blocks and more that build the next group's lists beside a walk -- or whose workspace is refused keeps one wavefront per block.
+ * plz4hip_ctx_counters [17] and [18] report what the path did.
  * Other environment switches, for tests and experiments only: PLZ4HIP_HC_EXT_OFF (the one-thread HC parsers for dictionary / linked
  * calls, rounds 1-3), PLZ4HIP_HC12_LAZY (level 12 with its searches made on demand), PLZ4HIP_HC_OVERLAP_OFF / _MIN / _GROUPS (levels 3..11: a call of 2048
  * blocks or more runs in four or more groups, the list builder of the next group on a second stream of the ctx beside the walk
@@ -153,8 +163,9 @@ int         plz4hip_ctx_trim(plz4hip_ctx* ctx);                /* release stagin
  * few-block decoder (they count in [3] as well), [11] the jump rounds launched for the last call with such a block, [12] the literal
  * runs and matches that call handed to its grid-wide stage, [13] blocks encoded by the few-block level-2 path, [14] its rounds that
  * parsed something in the last such call, [15] pieces it parsed more than once ([14] and [15]: with or without history outside the block), [16] blocks with history outside
- * the block encoded by the few-block level-2 path (a subset of [13]).  Returns how many counters there are (17), or
- * PLZ4HIP_E_*. */
+ * the block encoded by the few-block level-2 path (a subset of [13]), [17] blocks of levels 3..12 whose chains and lists were built
+ * in pieces across the chip, [18] the pieces per block of the last such call (its largest segment + block, cut).  Returns how
+ * many counters there are (19), or PLZ4HIP_E_*. */
 int         plz4hip_ctx_counters(plz4hip_ctx* ctx, int64_t* out, int n);
 
 /* == clz4.CompressBound (clz4.go:27-29) -> LZ4_compressBound (lz4.h:215).  Pure host arithmetic. */

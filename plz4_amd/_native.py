@@ -436,7 +436,7 @@ class Engine:
 
     COUNTERS = ("fx_blocks", "fx_rounds_last", "fx_pieces_again", "dx_blocks", "dxl_blocks", "dxl_rounds_last", "dxl_groups_last",
                 "fxl_blocks", "l1x_blocks", "hcx_blocks", "dx_big_blocks", "dx_big_rounds_last", "dx_big_runs_last",
-                "mx_blocks", "mx_rounds_last", "mx_pieces_again", "mxl_blocks")
+                "mx_blocks", "mx_rounds_last", "mx_pieces_again", "mxl_blocks", "hb_blocks", "hb_pieces_last")
 
     def counters(self) -> dict:
         """plz4hip_ctx_counters (waits for the ctx's work): blocks encoded by the few-block level-1 path, its rounds in the last
@@ -447,7 +447,8 @@ class Engine:
         context encoded by k_hcx, raw blocks above 4 MiB + 8 of capacity answered by the few-block decoder (they count in dx_blocks
         as well), the jump rounds launched for the last call with such a block and the runs it handed to the grid-wide stage, blocks
         encoded by the few-block level-2 path, its rounds that parsed something in the last such call, pieces it parsed more than once, blocks with history outside the block
-        (dictionary, linked) encoded by the few-block level-2 path (a subset of mx_blocks)."""
+        (dictionary, linked) encoded by the few-block level-2 path (a subset of mx_blocks), blocks of levels 3..12 whose chain and
+        lists were built in pieces across the chip, the pieces per block of the last such call."""
         out = (C.c_int64 * len(self.COUNTERS))()
         rc = int(self.L.plz4hip_ctx_counters(self.h, out, len(self.COUNTERS)))
         if rc < 0:

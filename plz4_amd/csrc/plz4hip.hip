@@ -25,6 +25,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_seq_device.inl"
 #include "lz4hc_device.inl"
 #include "lz4hc12_device.inl"
+#include "lz4hc_lists_device.inl"
 #include "lz4hc_lazy_device.inl"
 #include "lz4hcx_device.inl"
 #include "lz4_dx_device.inl"
@@ -899,6 +900,94 @@ __global__ __launch_bounds__(64) void k_hc12_chain(CodecArgs a)
     }
 }
 
+// Phase 1 of a few blocks, in pieces across the chip (lz4hc_lists_device.inl): the same offsets, chain, rank and list as the two
+// kernels above, by four launches in which nobody waits for anybody.  cnt / slot: [block of the group][piece][hash].
+struct HbArgs { uint32_t* cnt; uint32_t* slot; int P, piece; unsigned long long* counters; };
+struct HbBlk { const uint8_t* src; int n, nIns, pfx, skipLo, pieces; };
+// block g of the group as the builder sees it: segment + block, the positions that are inserted, its own number of pieces
+__device__ __forceinline__ bool hb_blk(const CodecArgs& a, const HbArgs& hb, int g, HbBlk* b)
+{
+    const int i = a.blk0 + g;
+    b->pfx = hc_pfx_of(a, i);
+    if (b->pfx < 0) return false;                                          // (k_hcx's, as for k_hc12_hist)
+    b->n = b->pfx + block_len(a, i);
+    b->src = a.src + (int64_t)i * a.srcStride - b->pfx;
+    b->nIns = b->n >= 4 ? b->n - 3 : 0;
+    b->skipLo = b->pfx > 3 ? b->pfx - 3 : 0;
+    b->pieces = (b->nIns + hb.piece - 1) / hb.piece;
+    if (b->pieces > hb.P) b->pieces = hb.P;                                // (never: P is cut from the call's largest segment + block)
+    return true;
+}
+// count: one 16-wave workgroup per (piece, block), the piece's 32768 counters in LDS, then out to cnt
+__global__ __launch_bounds__(1024) void k_hb_count(CodecArgs a, HbArgs hb)
+{
+    __shared__ uint32_t hist[kHcHashEntries];
+    const int tid = (int)threadIdx.x, g = (int)blockIdx.y, k = (int)blockIdx.x;
+    HbBlk b;
+    if (!hb_blk(a, hb, g, &b) || k >= b.pieces) return;
+    for (int h = tid; h < kHcHashEntries; h += 1024) hist[h] = 0u;
+    __syncthreads();
+    const int lo = k * hb.piece, hi = lo + hb.piece;
+    hb_count(b.src, b.nIns, b.skipLo, b.pfx, lo + (tid & ~63), hi, 1024, hist);
+    __syncthreads();
+    uint32_t* const out = hb.cnt + ((size_t)g * hb.P + k) * kHcHashEntries;
+    for (int h = tid; h < kHcHashEntries; h += 1024) out[h] = hist[h];
+}
+// scan: one workgroup per block.  A thread per hash adds up the pieces (neighbouring threads, neighbouring words); the prefix over
+// the 32768 totals as in k_hc12_hist; then every piece's first slot.
+__global__ __launch_bounds__(1024) void k_hb_scan(CodecArgs a, HbArgs hb)
+{
+    __shared__ uint32_t hist[kHcHashEntries];
+    __shared__ uint32_t part[1024];
+    const int tid = (int)threadIdx.x, g = (int)blockIdx.x;
+    HbBlk b;
+    if (!hb_blk(a, hb, g, &b)) return;
+    const uint32_t* const cnt = hb.cnt + (size_t)g * hb.P * kHcHashEntries;
+    uint32_t* const slot = hb.slot + (size_t)g * hb.P * kHcHashEntries;
+    for (int h = tid; h < kHcHashEntries; h += 1024) hist[h] = hb_total(cnt, b.pieces, h);
+    __syncthreads();
+    uint32_t sum = 0;
+    for (int k = 0; k < 32; ++k) sum += hist[tid * 32 + k];
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const uint32_t v = (tid >= d) ? part[tid - d] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[tid] - sum;
+    uint32_t* const off = a.h12Offsets + (size_t)g * kHcHashEntries;
+    for (int k = 0; k < 32; ++k) { const uint32_t c = hist[tid * 32 + k]; off[tid * 32 + k] = run; hist[tid * 32 + k] = run; run += c; }
+    __syncthreads();
+    for (int h = tid; h < kHcHashEntries; h += 1024) hb_slots(cnt, slot, b.pieces, h, hist[h]);
+    if (tid == 0) { atomicAdd(&hb.counters[17], 1ull); hb.counters[18] = (unsigned long long)hb.P; }
+}
+// fill: one wave per (piece, block) around two 64 KiB tables in LDS
+__global__ __launch_bounds__(64) void k_hb_fill(CodecArgs a, HbArgs hb)
+{
+    __shared__ uint32_t lastT[kHcHashEntries / 2];
+    __shared__ uint32_t curT[kHcHashEntries / 2];
+    const int g = (int)blockIdx.y, k = (int)blockIdx.x;
+    HbBlk b;
+    if (!hb_blk(a, hb, g, &b) || k >= b.pieces) return;
+    hb_fill(b.src, b.n, a.h12Offsets + (size_t)g * kHcHashEntries, hb.slot + ((size_t)g * hb.P + k) * kHcHashEntries,
+            a.h12Rank + (int64_t)g * a.h12ChainStride, a.h12List + (int64_t)g * (a.h12ChainStride + 8) + 8,
+            k * hb.piece, (k + 1) * hb.piece, lastT, curT, b.skipLo, b.pfx);
+}
+// chain: a wave per 64 positions of [0, nPad), nPad as k_hc12_chain has it
+__global__ __launch_bounds__(256) void k_hb_chain(CodecArgs a, HbArgs hb)
+{
+    const int g = (int)blockIdx.y;
+    HbBlk b;
+    if (!hb_blk(a, hb, g, &b)) return;
+    int nPad = (b.n + 1 + 1023) & ~1023;
+    if (nPad > a.h12ChainStride) nPad = (int)a.h12ChainStride;
+    for (int base = (int)(blockIdx.x * 256u + (threadIdx.x & ~63u)); base < nPad; base += (int)gridDim.x * 256)
+        hb_chain(b.n, b.skipLo, b.pfx, a.h12Chain + (int64_t)g * a.h12ChainStride, a.h12Rank + (int64_t)g * a.h12ChainStride,
+                 a.h12List + (int64_t)g * (a.h12ChainStride + 8) + 8, base);
+}
+
 // The chain alone, for levels 3..11 (HcWork::pre): one pass per block with the whole 128 KiB table in LDS.
 __global__ __launch_bounds__(64) void k_hc_chain(CodecArgs a)
 {
@@ -1710,6 +1799,8 @@ struct plz4hip_ctx {
     hipStream_t  hcBuildStream = nullptr; hipEvent_t evHcFork = nullptr, evHcHist = nullptr, evHcChain[2] = {nullptr, nullptr}, evHcFree[2] = {nullptr, nullptr};
     // HC levels 3..12 with a dictionary / linked blocks on the list path: the blocks' segment lengths (k_hc_ext_prep), int32 each
     DeviceBuffer hcPfx;  int hcLazyExWaves = 0;
+    // levels 3..12 on a few blocks: the counts and first slots of the pieces their chains and lists are built in (HbLayout), sized per call
+    DeviceBuffer hb;
     int hcxWaves[4] = {0, 0, 0, 0};                     // resident waves of k_hcx<kRaw, kMid>, [kRaw + 2 * kMid]
     // LZ4_decompress_safe of a few blocks by the whole chip (lz4_dx_device.inl): its tables
     DeviceBuffer dx;  StreamOrder dxOrder;
@@ -1727,19 +1818,21 @@ struct plz4hip_ctx {
     // encoded by the few-block level-1 path (a subset of [0]), [8] blocks with history outside the block parsed by the bulk staged
     // route (k_l1x_parse), [9] blocks of at most 4 KiB under a dictionary context encoded by the wave-wide HC parser (k_hcx),
     // [13] blocks encoded by the few-block level-2 path, [14] its rounds that parsed something in the last such call, [15] pieces
-    // it parsed more than once
-    static constexpr int kCounters = 17;
+    // it parsed more than once, [16] blocks with history outside the block encoded by the few-block level-2 path (a subset of [13]),
+    // [17] blocks of levels 3..12 whose chain and lists were built in pieces across the chip (k_hb_count .. k_hb_chain), [18] the
+    // pieces per block of the last such call (its largest segment + block, cut)
+    static constexpr int kCounters = 19;
     unsigned long long* d_counters = nullptr;
     // plz4hip_dev_compress: the sanitised block lengths of the last call (int32 each), which that job's kernels read
     DeviceBuffer lenCopy;  StreamOrder lenOrder;
     // plz4hip_dev_decode_records_ex: the chainFirst of the last call (int32 each), which that job's kernels read
     DeviceBuffer chainCopy;  StreamOrder chainOrder;
     struct Owned { DeviceBuffer* buf; StreamOrder* order; bool trimmed; };     // trimmed: plz4hip_ctx_trim gives it back
-    std::array<Owned, 11> owned()
+    std::array<Owned, 12> owned()
     {
         return {{{&hc, &hcOrder, true}, {&h12, &hcOrder, true}, {&hcPfx, &hcOrder, false}, {&l1[0], &l1Order[0], true},
                  {&l1[1], &l1Order[1], true}, {&dx, &dxOrder, true}, {&fx, &fxOrder, true}, {&lenCopy, &lenOrder, false},
-                 {&chainCopy, &chainOrder, false}, {&xstage, &xstageOrder, true}, {&mx, &mxOrder, true}}};
+                 {&chainCopy, &chainOrder, false}, {&xstage, &xstageOrder, true}, {&mx, &mxOrder, true}, {&hb, &hcOrder, true}}};
     }
 };
 
@@ -2073,10 +2166,22 @@ int hc_ctx_blocks(const HcCall& k, const CodecArgs& a0)
     HIPCHK(c, hipGetLastError());
     return PLZ4HIP_OK;
 }
-// the histogram and / or the chain and lists of x's blocks on st
-int hc_build(plz4hip_ctx* c, hipStream_t st, CodecArgs x, bool hist, bool chain)
+// the histogram and / or the chain and lists of x's blocks on st; hb: both, in pieces (c->hb holds HbLayout of at least x.nBlocks blocks)
+int hc_build(plz4hip_ctx* c, hipStream_t st, CodecArgs x, bool hist, bool chain, const HbWant* hb = nullptr)
 {
     hipError_t e;
+    if (hb) {
+        const HbLayout L = hb_layout(x.nBlocks, hb->P);
+        const HbArgs h{(uint32_t*)(c->hb.d + L.offCnt), (uint32_t*)(c->hb.d + L.offSlot), hb->P, hb->piece, c->d_counters};
+        const int nb = x.nBlocks;
+        int cw = (int)((x.h12ChainStride + 255) / 256);                      // chain: about eight workgroups per CU over the call
+        if (cw > (c->cus * 8 + nb - 1) / nb) cw = (c->cus * 8 + nb - 1) / nb;
+        hipLaunchKernelGGL(k_hb_count, dim3(hb->P, nb), dim3(1024), 0, st, x, h);
+        hipLaunchKernelGGL(k_hb_scan, dim3(nb), dim3(1024), 0, st, x, h);
+        hipLaunchKernelGGL(k_hb_fill, dim3(hb->P, nb), dim3(64), 0, st, x, h);
+        hipLaunchKernelGGL(k_hb_chain, dim3(cw, nb), dim3(256), 0, st, x, h);
+        return PLZ4HIP_OK;
+    }
     if (hist)  { x.queue = next_queue(c, st, &e); HIPCHK(c, e); hipLaunchKernelGGL(k_hc12_hist, dim3(grid_for(x.nBlocks, c->cus)), dim3(1024), 0, st, x); }
     if (chain) { x.queue = next_queue(c, st, &e); HIPCHK(c, e); hipLaunchKernelGGL(k_hc12_chain, dim3(grid_for(x.nBlocks, c->cus)), dim3(64), 0, st, x); }
     return PLZ4HIP_OK;
@@ -2116,6 +2221,14 @@ int hc_segmented(const HcCall& k, const HcSwitches& sw, const HcPlan& p, CodecAr
     const HcGroups g = hc_groups(nb, pl.group, p.lazy, sw);
     const bool overlap = g.overlap;
     const int per = g.per, nGroups = g.nGroups;
+    // few blocks: chain and lists in pieces across the chip, when the pieces' own workspace is granted (else today's builder)
+    const HbWant hbw = hb_want(HbShape{a.level, nb, k.maxLen, k.maxLen + (p.lazyEx ? 65536 : 0), true, overlap}, sw);
+    bool hbGranted = false;
+    if (hbw.on) {
+        bool refused = false;  HIPCHK(c, c->hb.reserve(hb_layout(per, hbw.P).total, c->hcOrder, &refused));
+        hbGranted = !refused;
+    }
+    const HbWant* const hbp = hb_route(hbw, hbGranted) ? &hbw : nullptr;
     if (overlap) {
         if (!c->hcBuildStream) HIPCHK(c, hipStreamCreateWithFlags(&c->hcBuildStream, hipStreamNonBlocking));
         for (hipEvent_t* ev : {&c->evHcFork, &c->evHcHist, &c->evHcChain[0], &c->evHcChain[1], &c->evHcFree[0], &c->evHcFree[1]})
@@ -2148,7 +2261,7 @@ int hc_segmented(const HcCall& k, const HcSwitches& sw, const HcPlan& p, CodecAr
                 HIPCHK(c, hipEventRecord(c->evHcChain[(gi + 1) & 1], sb));
             }
         } else {
-            if (int rc = hc_build(c, s, a, true, true)) return rc;
+            if (int rc = hc_build(c, s, a, true, true, hbp)) return rc;
         }
         a.queue = next_queue(c, s, &e); HIPCHK(c, e);
         if (!p.lazy) hipLaunchKernelGGL(k_hc12_search, dim3(grid_for(ng, c->cus)), dim3(1024), 0, s, a);

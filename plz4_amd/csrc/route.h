@@ -90,6 +90,15 @@ inline L1Route l1_route(const L1Shape& k, const L1Switches& sw, const L1Want& w,
 }
 
 // ---------------------------------------------------------------------------------------------------- HC levels 2..12 (launch_hc)
+// PLZ4HIP_HB_MAX_BLOCKS / PLZ4HIP_HB_PIECE_KIB: chain and lists of few blocks built in pieces across the chip (hb_want below).
+// 64 blocks: the largest measured count at which the pieces beat one wave per block by more than both spreads, kernels alone and
+// through host buffers, at level 3 (profiles/hb_rate.json, 4 MiB T blocks: 38.8 against 71.3 ms kernels alone, 52.1 against 85.5
+// through host buffers; at 128 the kernels alone still win, 72.7 against 89.3, but host buffers, 99.6 against 116.8, lie inside
+// their spreads of 11.5 + 15.8; at 256 the pieces lose, 140.1 against 126.2) and do not lose at level 9 (53.9 against 86.4, 69.7
+// against 100.4).  64 KiB pieces: the fastest at 1 block (profiles/hb_rate_pieces.json, level 3, kernels alone: 16 KiB 8.60, 32 KiB
+// 6.90, 64 KiB 6.29, 128 KiB 6.41 ms) and within a fifth of the fastest at 64 blocks (38.9 against 128 KiB's 37.8).
+constexpr int kHbMaxBlocks = 64;
+constexpr int kHbPieceKiB = 64;
 struct HcSwitches {
     int  hcx = kUnset;                     // PLZ4HIP_HCX (0: no block goes to k_hcx)
     bool extOff = false, midOff = false, lazyOff = false, preOff = false, listsOff = false;   // PLZ4HIP_HC_{EXT,MID,LAZY,PRE,LISTS}_OFF
@@ -102,6 +111,8 @@ struct HcSwitches {
     int  overlapGroups = 4;                // PLZ4HIP_HC_OVERLAP_GROUPS >= 2
     long budgetGiB = 0;                    // PLZ4HIP_HC_BUDGET_GIB
     int  h12Group = 0, group = 0;          // PLZ4HIP_HC12_GROUP, PLZ4HIP_HC_GROUP
+    int  hbMax = kHbMaxBlocks;             // PLZ4HIP_HB_MAX_BLOCKS (0: off)
+    int  hbPieceKiB = kHbPieceKiB;         // PLZ4HIP_HB_PIECE_KIB, clamped to 1..4096 (tests: many pieces in small blocks)
 };
 
 // (blocks of 8 MiB and more -- raw block API only -- keep the one-thread-per-block kernel: the writer packs positions into 23 bits)
@@ -223,6 +234,29 @@ inline HcGroups hc_groups(int nb, int group, bool lazy, const HcSwitches& sw)
     return g;
 }
 
+// ---------------------------------------------------------------------------------------------------- levels 3..12, few blocks (hc_segmented)
+// HcRoute::Segmented: chain, rank and list built in pieces of the positions by many workgroups per block (lz4hc_lists_device.inl:
+// count, scan, fill, chain) instead of k_hc12_hist + k_hc12_chain's one wave per block.  The arrays are the same; everything behind
+// the builder is untouched.  The pieces cost two 128 KiB tables each in device memory and a table set-up per piece, which pays only
+// while the chip has idle CUs: at most hbMax blocks, the default following kMxMaxBlocks' rule (the largest measured count at which
+// the pieces beat one wave per block by more than both spreads, kernels alone and through host buffers).
+// maxLen: the largest block; span: the largest segment + block (the positions the lists are built over); overlap: HcGroups::overlap,
+// the builder beside the walk, which lives on the builder being one wave per CU.
+struct HbShape { int level, nb, maxLen, span; bool segmented, overlap; };
+struct HbWant { bool on; int piece, P; };                                   // pieces of `piece` positions, P per block of `span`
+inline HbWant hb_want(const HbShape& k, const HcSwitches& sw)
+{
+    HbWant w{};
+    const int piece = sw.hbPieceKiB << 10;
+    // (a call whose largest block is one piece has nothing to cut; raw blocks above 4 MiB keep today's builder)
+    w.on = k.segmented && k.level >= 3 && k.level <= 12 && !k.overlap && k.nb >= 1 && k.nb <= sw.hbMax
+        && k.maxLen > 0 && k.maxLen <= kSeqMaxBlock && k.span > piece;
+    if (w.on) { w.piece = piece; w.P = (k.span + piece - 1) / piece; }
+    return w;
+}
+// ... and given what was granted: the pieces' own workspace.  false: today's k_hc12_hist + k_hc12_chain.
+inline bool hb_route(const HbWant& w, bool granted) { return w.on && granted; }
+
 // ---------------------------------------------------------------------------------------------------- decode (launch_decode)
 constexpr int    kDxlGroupBlocks = 128;                                     // the fastest of 16 / 32 / 64 / 128 on a 256-block chain
 constexpr double kDxlMsPerBlock = 0.33, kWalkMsPerBlock = 59.0;             // t_dx, t_wave: 4 MiB blocks; both scale with the block alike
@@ -328,6 +362,8 @@ template <class Get> HcSwitches parse_hc_switches(Get&& get)
     { const int w = (int)num("PLZ4HIP_HC_OVERLAP_GROUPS", 4); sw.overlapGroups = w < 2 ? 2 : w; }
     sw.budgetGiB = num("PLZ4HIP_HC_BUDGET_GIB", 0);
     sw.h12Group = (int)num("PLZ4HIP_HC12_GROUP", 0); sw.group = (int)num("PLZ4HIP_HC_GROUP", 0);
+    { const long m = num("PLZ4HIP_HB_MAX_BLOCKS", kHbMaxBlocks); sw.hbMax = m < 0 ? 0 : (m > 65535 ? 65535 : (int)m); }   // (the blocks are the grid's y)
+    { const long p = num("PLZ4HIP_HB_PIECE_KIB", kHbPieceKiB); sw.hbPieceKiB = p < 1 ? 1 : (p > 4096 ? 4096 : (int)p); }
     return sw;
 }
 template <class Get> MxSwitches parse_mx_switches(Get&& get)

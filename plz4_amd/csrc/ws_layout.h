@@ -165,6 +165,21 @@ inline HcLayout hc_layout(int group, int maxLen, bool lazy, bool needF, int pars
     return L;
 }
 
+// ---------------------------------------------------------------------------------------------------- lists in pieces (c->hb)
+// [counts per (block, piece, hash)][first list slot per (block, piece, hash)]: 2 x 128 KiB per piece (lz4hc_lists_device.inl)
+struct HbLayout { size_t pieceStride, offCnt, offSlot, total; };            // pieceStride: entries per piece
+inline HbLayout hb_layout(int per, int P, std::vector<WsTake>* log = nullptr)
+{
+    HbLayout L{};
+    L.pieceStride = (size_t)kHcHashEntries;
+    Carver c{log};
+    const size_t nP = (size_t)per * (size_t)P;
+    L.offCnt = c.take<uint32_t>(nP * L.pieceStride);
+    L.offSlot = c.take<uint32_t>(nP * L.pieceStride);
+    L.total = c.at;
+    return L;
+}
+
 // ------------------------------------------------------------------------- HC chain / lists up front (c->h12, the one-thread parsers)
 // [error flag 256][chain 2 B per position][lists: rank 4 B][list 4 B, + 8][offsets per hash].  What is reserved is not the sum of the
 // takes but slack + per x perBlock: the flag and a 256-byte rounding of each of the four arrays.
