@@ -217,7 +217,7 @@ class WriterImpl : public Writer {
             rc = eng.EncodeRecordsEx(n, src, len, bsz, o.Level, o.BlockChecksum ? 1 : 0, o.BlockLinked ? 1 : 0, dictH,
                                      haveTail ? (const void*)lastTail.data() : nullptr, haveTail ? (int)lastTail.size() : -1, rec, rlen);
             if (o.BlockLinked && n > 0) {
-                const uint8_t* lp = (const uint8_t*)src[n - 1]; const int ll = len[n - 1]; const int k = ll < 65536 ? ll : 65536;
+                const uint8_t* lp = (const uint8_t*)src[n - 1]; const int ll = len[n - 1]; const int k = std::min(ll, 65536);   // (tail_len, lz4_block_io.inl: this layer sees the public header only)
                 lastTail.assign(lp + (ll - k), lp + ll); haveTail = true;
             }
         }

@@ -875,7 +875,7 @@ DEV void dxb_run_piece(const DxRun& r, const uint32_t c, const uint8_t* __restri
 DEV uint32_t dxb_run_pieces(const DxRun& r) { return (r.len + (uint32_t)kDxbPiece - 1u) / (uint32_t)kDxbPiece; }
 
 // ---- The stage train (the table at the head of this file): one block's view of the call, the body of every stage, the flavours.
-// DxBlk: plain pointers and numbers -- the block (dx_src / dx_len / dx_cap of plz4hip.hip), its rows of the call's tables and what
+// DxBlk: plain pointers and numbers -- the block (dx_src / dx_len / cap_of of plz4hip.hip), its rows of the call's tables and what
 // they were sized for, its DxInfo, its number in the call.
 struct DxBlk {
     const uint8_t* src; int n; uint8_t* dst; int cap;

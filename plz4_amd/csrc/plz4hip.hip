@@ -31,6 +31,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_dx_device.inl"
 #include "lz4_fx_device.inl"
 #include "lz4_mx_device.inl"
+#include "lz4_block_io.inl"
 #include "ws_layout.h"
 #include "route.h"
 
@@ -130,6 +131,36 @@ __device__ __forceinline__ int block_len(const CodecArgs& a, int i)
     const int64_t rem = a.srcBytes - (int64_t)i * a.bsz;
     return (int)(rem < a.bsz ? rem : a.bsz);
 }
+// the room of raw block i's destination
+__device__ __forceinline__ int cap_of(const CodecArgs& a, int i) { return a.dstCap ? a.dstCap[i] : a.dstCapAll; }
+
+// ---- the two rules of lz4_block_io.inl on a call's arguments ----------------------------------------------------------------------
+static_assert(kHcxMaxBlock == kCtxMaxBlock, "k_hcx serves the blocks a dictionary context serves by lookup");
+// the call as the priming rule reads it
+__device__ __forceinline__ HistView hist_view(const CodecArgs& a)
+{
+    return HistView{a.src, a.srcStride, a.srcLen, a.srcBytes, a.bsz, a.linked, a.prevTail, a.prevTailLen, a.dict, a.dictLen};
+}
+// how block i of a level-1 call is primed / of an HC call, its external segment laid in front of the block at s
+__device__ __forceinline__ DictEnc l1_prime_of(const CodecArgs& a, int i, int n, bool rawApi) { return l1_prime(hist_of(hist_view(a), i, n, rawApi), rawApi, a.dictTable); }
+__device__ __forceinline__ HcDict hc_prime_of(const CodecArgs& a, int i, int n, const uint8_t* s, bool rawApi)
+{
+    const Hist h = hist_of(hist_view(a), i, n, rawApi);
+    const HcDict d = hc_prime(h, a.hcDictHash, a.hcDictChain);
+    if (d.mode == kHcExt) lay_segment(s, h.bytes, d.len);
+    return d;
+}
+// whether block i of an HC call is one its dictionary context serves by lookup (k_hcx's blocks), nothing read or laid out
+__device__ __forceinline__ bool hc_is_ctx(const CodecArgs& a, int i, int n, bool rawApi) { return ctx_small(hist_view(a), i, n, rawApi); }
+// Block i (s, n bytes) through enc(out, cap) -> bytes written or 0.  raw: an LZ4 block at dst + i * dstStride, result[i] = enc's
+// answer.  Else blk.CompressToBlk: the payload at rec + 4 with capacity bsz (blk.go:73), the record around it, result[i] = its length.
+template <class Enc> __device__ __forceinline__ void encode_out(const CodecArgs& a, int i, const uint8_t* s, int n, bool raw, Enc enc)
+{
+    uint8_t* const out = a.dst + (int64_t)i * a.dstStride;
+    const int c = enc(raw ? out : out + 4, raw ? cap_of(a, i) : a.bsz);
+    const int r = raw ? c : wave_finish_record(out, s, n, c, a.blockChecksum != 0);
+    if ((threadIdx.x & 63u) == 0) a.result[i] = r;
+}
 
 // The level-1 encoder kernels run up to TEN independent waves per workgroup, each with its own 16 KiB table: one such
 // workgroup owns all 160 KiB of a CU's LDS, i.e. ten tables per CU, where one-wave workgroups of 16 KiB only reach nine per CU
@@ -148,10 +179,9 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_encode_raw(CodecArg
 {
     ENC_WAVE_TABLE(lds);
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
-        const int n   = block_len(a, i);
-        const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
-        const int r   = wave_encode_block(a.src + (int64_t)i * a.srcStride, n, a.dst + (int64_t)i * a.dstStride, cap, lds);
-        if ((threadIdx.x & 63u) == 0) a.result[i] = r;
+        const int      n = block_len(a, i);
+        const uint8_t* s = a.src + (int64_t)i * a.srcStride;
+        encode_out(a, i, s, n, true, [&](uint8_t* out, int cap) { return wave_encode_block(s, n, out, cap, lds); });
     }
 }
 
@@ -160,24 +190,9 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_encode_rec(CodecArg
 {
     ENC_WAVE_TABLE(lds);
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
-        const int      n   = block_len(a, i);
-        const uint8_t* s   = a.src + (int64_t)i * a.srcStride;
-        uint8_t*       rec = a.dst + (int64_t)i * a.dstStride;
-        int      c    = wave_encode_block(s, n, rec + 4, a.bsz, lds);       // capacity == bsz (blk/blk.go:73)
-        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
-        if (c == 0) {                                                        // ErrCompress -> stored raw (blk.go:78-92)
-            wave_copy(rec + 4, s, n);
-            c = n;
-            word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu);
-        }
-        int len = c + 4;
-        if (a.blockChecksum) {                                               // over the payload as stored (blk.go:98-102)
-            WAVE_FENCE();
-            const uint32_t x = wave_xxh32(rec + 4, c);
-            if ((threadIdx.x & 63u) == 0) st32u(rec + 4 + c, x);
-            len += 4;
-        }
-        if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[i] = len; }
+        const int      n = block_len(a, i);
+        const uint8_t* s = a.src + (int64_t)i * a.srcStride;
+        encode_out(a, i, s, n, false, [&](uint8_t* out, int cap) { return wave_encode_block(s, n, out, cap, lds); });
     }
 }
 
@@ -242,7 +257,7 @@ __global__ __launch_bounds__(256) void k_l1_scan(CodecArgs a)
     const int gi = a.blk0 + i;
     const int n  = block_len(a, gi);
     SeqInfo inf = a.l1Info[i];
-    const int cap = a.rawMode ? (a.dstCap ? a.dstCap[gi] : a.dstCapAll) : a.bsz;     // records: capacity == bsz (blk/blk.go:73)
+    const int cap = a.rawMode ? cap_of(a, gi) : a.bsz;     // records: capacity == bsz (blk/blk.go:73)
     int total = 0;
     const bool broken = inf.nseq == kSeqEngineFailed;                                 // (an HC search phase that gave up: no result)
     if (inf.nseq >= 0)
@@ -329,55 +344,15 @@ __global__ __launch_bounds__(64) void k_l1_finish(CodecArgs a)
     }
 }
 
-// One level-1 block under a dictionary context and/or after another linked block.  Every input block of such a call has
-// 64 KiB of scratch in front of it (host_codec lays the staging out that way): the external segment -- the previous block's
-// tail or the dictionary -- is copied there, right before the block, and the full encoder runs in its external-segment mode
-// (wave_encode_block_ext).  Only the dictionary-context lookup of blocks <= 4 KiB keeps the one-sequence-per-batch encoder.
-__device__ __forceinline__ int encode_block_primed(const uint8_t* s, int n, uint8_t* out, int cap, const DictEnc& dc, uint32_t* lds)
-{
-    if (dc.mode == kDictCtxLookup) return wave_encode_block_dict(s, n, out, cap, dc, lds);
-    int segLen = 0;
-    if (dc.mode == kDictLoad || dc.mode == kDictCtxCopy) {
-        segLen = dc.dictSize;
-        // (a segment that lies there already -- the tail of the block before in contiguous plaintext -- stays: its neighbours read it)
-        if (dc.dict != s - segLen) { wave_copy(const_cast<uint8_t*>(s) - segLen, dc.dict, segLen); WAVE_FENCE(); }
-    }
-    return wave_encode_block_ext(s, n, out, cap, dc.mode, segLen, dc.dictTable, lds);
-}
-
-// blk.CompressToBlk with a dictionary and/or linked blocks (config 5).  Which stream priming applies to a block follows
-// clz4.go:160-179 (StreamIndieCtx) and :224-248 (StreamLinkedCtx) + async/writer.go:412-437 (_genDict).
+// blk.CompressToBlk with a dictionary and/or linked blocks (config 5).
 template <int W> __global__ __launch_bounds__(64 * W) void k_encode_rec_dict(CodecArgs a)
 {
     ENC_WAVE_TABLE(lds);
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
-        const int      n   = block_len(a, i);
-        const uint8_t* s   = a.src + (int64_t)i * a.srcStride;
-        uint8_t*       rec = a.dst + (int64_t)i * a.dstStride;
-        DictEnc dc{nullptr, 0, kDictFreshPrefix, nullptr};
-        const uint8_t* tail = nullptr; int tailLen = -1;
-        if (a.linked) {
-            if (i > 0) { const int pl = block_len(a, i - 1); tailLen = pl < 65536 ? pl : 65536; tail = a.src + (int64_t)(i - 1) * a.srcStride + (pl - tailLen); }
-            else if (a.prevTailLen >= 0) { tail = a.prevTail; tailLen = a.prevTailLen; }
-        }
-        if (tailLen >= 0) {                                   // linked block after another block: LZ4_loadDict(previous tail)
-            dc.mode = tailLen >= 8 ? kDictLoad : kDictNonePrefix;
-            if (tailLen >= 8) { dc.dict = tail; dc.dictSize = tailLen; }
-        } else if (a.dict != nullptr || a.dictLen >= 0) {     // a dictionary context is attached (possibly an empty one)
-            if (a.dictLen >= 8) { dc.dict = a.dict; dc.dictSize = a.dictLen; dc.dictTable = a.dictTable; dc.mode = n > 4096 ? kDictCtxCopy : kDictCtxLookup; }
-            else dc.mode = kDictNonePrefix;
-        }                                                     // else: linked frame start without dictionary -> kDictFreshPrefix
-        int      c    = encode_block_primed(s, n, rec + 4, a.bsz, dc, lds);
-        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
-        if (c == 0) { wave_copy(rec + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
-        int len = c + 4;
-        if (a.blockChecksum) {
-            WAVE_FENCE();
-            const uint32_t x = wave_xxh32(rec + 4, c);
-            if ((threadIdx.x & 63u) == 0) st32u(rec + 4 + c, x);
-            len += 4;
-        }
-        if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[i] = len; }
+        const int      n  = block_len(a, i);
+        const uint8_t* s  = a.src + (int64_t)i * a.srcStride;
+        const DictEnc  dc = l1_prime_of(a, i, n, false);
+        encode_out(a, i, s, n, false, [&](uint8_t* out, int cap) { return encode_block_primed(s, n, out, cap, dc, lds); });
     }
 }
 
@@ -386,34 +361,13 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_encode_raw_dict(Cod
 {
     ENC_WAVE_TABLE(lds);
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
-        const int n = block_len(a, i);
-        DictEnc dc{nullptr, 0, kDictNonePrefix, nullptr};
-        if (a.dictLen >= 8) { dc.dict = a.dict; dc.dictSize = a.dictLen; dc.dictTable = a.dictTable; dc.mode = n > 4096 ? kDictCtxCopy : kDictCtxLookup; }
-        const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
-        const int r = encode_block_primed(a.src + (int64_t)i * a.srcStride, n, a.dst + (int64_t)i * a.dstStride, cap, dc, lds);
-        if ((threadIdx.x & 63u) == 0) a.result[i] = r;
+        const int      n  = block_len(a, i);
+        const uint8_t* s  = a.src + (int64_t)i * a.srcStride;
+        const DictEnc  dc = l1_prime_of(a, i, n, true);
+        encode_out(a, i, s, n, true, [&](uint8_t* out, int cap) { return encode_block_primed(s, n, out, cap, dc, lds); });
     }
 }
 
-// ---- few level-1 blocks with history outside the block cut across the chip (the kExt flavour of lz4_fx_device.inl) -----------------
-// How block i of the call is primed: what k_encode_rec_dict / k_encode_raw_dict decide, in one place for the kernels below.
-__device__ __forceinline__ DictEnc fxl_dict_of(const CodecArgs& a, int i, int n)
-{
-    DictEnc dc{nullptr, 0, a.rawMode ? kDictNonePrefix : kDictFreshPrefix, nullptr};
-    const uint8_t* tail = nullptr; int tailLen = -1;
-    if (!a.rawMode && a.linked) {
-        if (i > 0) { const int pl = block_len(a, i - 1); tailLen = pl < 65536 ? pl : 65536; tail = a.src + (int64_t)(i - 1) * a.srcStride + (pl - tailLen); }
-        else if (a.prevTailLen >= 0) { tail = a.prevTail; tailLen = a.prevTailLen; }
-    }
-    if (tailLen >= 0) {                                       // linked block after another block: LZ4_loadDict(previous tail)
-        dc.mode = tailLen >= 8 ? kDictLoad : kDictNonePrefix;
-        if (tailLen >= 8) { dc.dict = tail; dc.dictSize = tailLen; }
-    } else if (a.rawMode || a.dict != nullptr || a.dictLen >= 0) {     // a dictionary context is attached (possibly an empty one)
-        if (a.dictLen >= 8) { dc.dict = a.dict; dc.dictSize = a.dictLen; dc.dictTable = a.dictTable; dc.mode = n > 4096 ? kDictCtxCopy : kDictCtxLookup; }
-        else dc.mode = kDictNonePrefix;
-    }
-    return dc;
-}
 // ---- the parse of a few blocks cut across the chip (lz4_pieces_device.inl): grid (pieces, blocks of the group), one wave each,
 // one launch per round, then the gather into the staged path's records (l1Seq / l1Info) -- the emit kernels run unchanged behind it.
 // Workspace per piece: meta, entry state, two exit states, records (PieceLayout).  cnt: the ctx's counters (plz4hip_ctx_counters).
@@ -516,7 +470,7 @@ __global__ __launch_bounds__(64) void k_fxl_prep(CodecArgs a, PieceArgs f, FxlBl
     const int n = block_len(a, gi);
     FxlBlk b; b.pfx = -2; b.bs = 0;                                          // -2: a length the workspace was not sized for
     if (n >= 0 && n <= a.l1MaxLen) {
-        const DictEnc dc = fxl_dict_of(a, gi, n);
+        const DictEnc dc = l1_prime_of(a, gi, n, a.rawMode != 0);
         b = fxl_prep(const_cast<uint8_t*>(a.src) + (int64_t)gi * a.srcStride, n, dc.mode, dc.dict, dc.dictSize, dc.dictTable,
                      f.tabIn + (int64_t)i * f.P * kFxTab, lds);
     }
@@ -532,38 +486,22 @@ __global__ __launch_bounds__(64) void k_fxl_small(CodecArgs a)
     for (int i = blockIdx.x; i < a.nBlocks; i += gridDim.x) {
         const int gi = a.blk0 + i;
         const int n = block_len(a, gi);
-        if (n < 0 || n > 4096) continue;
-        const DictEnc dc = fxl_dict_of(a, gi, n);
+        if (n < 0 || n > kCtxMaxBlock) continue;
+        const DictEnc dc = l1_prime_of(a, gi, n, a.rawMode != 0);
         if (dc.mode != kDictCtxLookup) continue;
         const uint8_t* s = a.src + (int64_t)gi * a.srcStride;
-        if (a.rawMode) {
-            const int cap = a.dstCap ? a.dstCap[gi] : a.dstCapAll;
-            const int r = wave_encode_block_dict(s, n, a.dst + (int64_t)gi * a.dstStride, cap, dc, lds);
-            if ((threadIdx.x & 63u) == 0) a.result[gi] = r;
-            continue;
-        }
-        // records back to back (a.bodyOff): this launch runs between k_l1_scan and the scan over the records' lengths.  The block's
-        // bytes go where its records would lie (it has none; bsz + 8 <= 8 bytes per possible sequence), its length to result, and
-        // the emit stage's write and finish kernels lay it down as any other record (kSeqElsewhere).
-        uint8_t* rec = a.dst + (int64_t)gi * a.dstStride;
-        int      c    = wave_encode_block_dict(s, n, a.bodyOff ? (uint8_t*)(a.l1Seq + (int64_t)i * a.l1SeqStride) : rec + 4, a.bsz, dc, lds);
-        if (a.bodyOff) {
+        if (!a.rawMode && a.bodyOff) {
+            // records back to back: this launch runs between k_l1_scan and the scan over the records' lengths.  The block's bytes go
+            // where its records would lie (it has none; bsz + 8 <= 8 bytes per possible sequence), its length to result, and the
+            // emit stage's write and finish kernels lay it down as any other record (kSeqElsewhere).
+            const int c = wave_encode_block_dict(s, n, (uint8_t*)(a.l1Seq + (int64_t)i * a.l1SeqStride), a.bsz, dc, lds);
             if ((threadIdx.x & 63u) == 0) {
                 SeqInfo inf; inf.nseq = kSeqElsewhere; inf.lastAnchor = 0; inf.total = c; inf.stored = (c == 0); a.l1Info[i] = inf;
                 a.result[gi] = (c ? c : n) + 4 + (a.blockChecksum ? 4 : 0);
             }
             continue;
         }
-        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
-        if (c == 0) { wave_copy(rec + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
-        int len = c + 4;
-        if (a.blockChecksum) {
-            WAVE_FENCE();
-            const uint32_t x = wave_xxh32(rec + 4, c);
-            if ((threadIdx.x & 63u) == 0) st32u(rec + 4 + c, x);
-            len += 4;
-        }
-        if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[gi] = len; }
+        encode_out(a, gi, s, n, a.rawMode != 0, [&](uint8_t* out, int cap) { return wave_encode_block_dict(s, n, out, cap, dc, lds); });
     }
 }
 
@@ -585,7 +523,7 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_l1x_parse(CodecArgs
         int lastAnchor = 0, nseq = -1;                                       // -1: a block the workspace was not sized for
         FxlBlk b; b.pfx = -2; b.bs = 0;
         if (n >= 0 && n <= a.l1MaxLen) {
-            const DictEnc dc = fxl_dict_of(a, gi, n);
+            const DictEnc dc = l1_prime_of(a, gi, n, a.rawMode != 0);
             nseq = l1x_block(const_cast<uint8_t*>(a.src) + (int64_t)gi * a.srcStride, n, dc.mode, dc.dict, dc.dictSize, dc.dictTable,
                              a.l1Seq + (int64_t)i * a.l1SeqStride, (int)a.l1SeqStride - 1, &lastAnchor, &b, lds);
         }
@@ -682,7 +620,7 @@ __global__ __launch_bounds__(64) void k_decode_raw_dict(CodecArgs a)
 {
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
         if (a.dxlGood && a.dxlGood[i]) continue;                             // (answered by the few-block path)
-        const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
+        const int cap = cap_of(a, i);
         const int r = wave_decode_block(a.src + (int64_t)i * a.srcStride, a.srcLen[i], a.dst + (int64_t)i * a.dstStride, cap, a.dict, a.dictLen);
         if ((threadIdx.x & 63u) == 0) a.result[i] = r;
     }
@@ -696,29 +634,6 @@ __device__ __forceinline__ HcWork hc_work_of(const CodecArgs& a)
     w.opt = (HcOpt*)(ws + kHcHashEntries * 4 + kHcChainEntries * 2); w.pre = nullptr; w.rank = nullptr; w.list = nullptr;
     return w;
 }
-// How block i of an HC call is primed: clz4.StreamCtxHC (clz4.go:181-209, dictionary + independent blocks),
-// clz4.StreamLinkedCtxHC (:250-283) + async/writer.go:412-437 (_genDict: the previous block's last <= 64 KiB).  In the
-// dictionary / linked modes every input block has 64 KiB of scratch in front of it (host_codec lays the staging out that
-// way): an external segment is copied there so that it lies right before the block, which is what hc_compress(kHcExt) reads.
-__device__ __forceinline__ HcDict hc_dict_of(const CodecArgs& a, int i, int n, const uint8_t* s, bool rawApi)
-{
-    HcDict d; d.mode = kHcNone; d.len = 0; d.bytes = nullptr; d.hash = nullptr; d.chain = nullptr;
-    const uint8_t* seg = nullptr; int segLen = -1;
-    if (!rawApi && a.linked) {
-        if (i > 0) { const int pl = block_len(a, i - 1); segLen = pl < 65536 ? pl : 65536; seg = a.src + (int64_t)(i - 1) * a.srcStride + (pl - segLen); }
-        else if (a.prevTailLen >= 0) { seg = a.prevTail; segLen = a.prevTailLen; }
-    }
-    if (segLen < 0 && (a.dict != nullptr || a.dictLen >= 0)) {           // a dictionary context is attached (lz4hc.c:1438-1461)
-        const int dl = a.dictLen > 0 ? a.dictLen : 0;
-        if (n > 4096) { seg = a.dict; segLen = dl; }                      // its state is copied: same as LZ4_loadDictHC + setExternalDict
-        else { d.mode = kHcCtx; d.len = dl; d.bytes = a.dict; d.hash = a.hcDictHash; d.chain = a.hcDictChain; }
-    }
-    if (segLen >= 0) {
-        d.mode = kHcExt; d.len = segLen;
-        if (segLen > 0 && seg != s - segLen) { wave_copy(const_cast<uint8_t*>(s) - segLen, seg, segLen); WAVE_FENCE(); }   // (in place already: contiguous plaintext)
-    }
-    return d;
-}
 // independent block without dictionary, the i-th of its group: its chain (and lists) were built up front when the call's
 // launcher found room for them
 __device__ __forceinline__ HcWork hc_with_pre(HcWork w, const CodecArgs& a, int i)
@@ -728,57 +643,24 @@ __device__ __forceinline__ HcWork hc_with_pre(HcWork w, const CodecArgs& a, int 
     w.list = (a.h12Chain && a.h12Rank) ? a.h12List + (int64_t)i * (a.h12ChainStride + 8) + 8 : nullptr;
     return w;
 }
-// whether block i of an HC call is a block <= 4 KiB under a dictionary context (hc_dict_of's kHcCtx), without laying anything out
-__device__ __forceinline__ bool hc_is_ctx(const CodecArgs& a, int i, int n, bool rawApi)
-{
-    if (n > kHcxMaxBlock) return false;
-    if (!rawApi && a.linked && (i > 0 || a.prevTailLen >= 0)) return false;
-    return a.dict != nullptr || a.dictLen >= 0;
-}
-__global__ __launch_bounds__(64) void k_encode_raw_hc(CodecArgs a)
+// One thread of search per block: raw LZ4 blocks (kRaw) or records.  hcEx: the call has a dictionary and / or linked blocks.
+template <bool kRaw> __device__ __forceinline__ void hc_one_thread(const CodecArgs& a)
 {
     const HcWork w = hc_work_of(a);
-    const bool dictMode = a.hcEx != 0;
     for (int g = next_block(a.queue); g < a.nBlocks; g = next_block(a.queue)) {
-        const int i = a.blk0 + g;                                        // (the chain / lists workspace is the group's: index g)
-        const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
-        const int n = block_len(a, i);
+        const int      i = a.blk0 + g;                                   // (the chain / lists workspace is the group's: index g)
+        const int      n = block_len(a, i);
         const uint8_t* s = a.src + (int64_t)i * a.srcStride;
-        int r;
         if (a.hcPfx && a.hcPfx[i] >= 0) continue;                          // (done on the list path)
-        if (a.hcx && hc_is_ctx(a, i, n, true)) continue;                   // (k_hcx's)
-        if (dictMode) r = hc_compress(s, n, a.dst + (int64_t)i * a.dstStride, cap, a.level, w, hc_dict_of(a, i, n, s, true));
-        else          r = hc_compress(s, n, a.dst + (int64_t)i * a.dstStride, cap, a.level, hc_with_pre(w, a, g));
-        if ((threadIdx.x & 63u) == 0) a.result[i] = r;
+        if (a.hcx && hc_is_ctx(a, i, n, kRaw)) continue;                   // (k_hcx's)
+        encode_out(a, i, s, n, kRaw, [&](uint8_t* out, int cap) {
+            if (a.hcEx) return hc_compress(s, n, out, cap, a.level, w, hc_prime_of(a, i, n, s, kRaw));
+            return hc_compress(s, n, out, cap, a.level, hc_with_pre(w, a, g));
+        });
     }
 }
-__global__ __launch_bounds__(64) void k_encode_rec_hc(CodecArgs a)
-{
-    const HcWork w = hc_work_of(a);
-    const bool exMode = a.hcEx != 0;
-    for (int g = next_block(a.queue); g < a.nBlocks; g = next_block(a.queue)) {
-        const int      i   = a.blk0 + g;
-        const int      n   = block_len(a, i);
-        const uint8_t* s   = a.src + (int64_t)i * a.srcStride;
-        uint8_t*       rec = a.dst + (int64_t)i * a.dstStride;
-        int c;                                                           // capacity == bsz (blk.go:73); indie.go:80-88
-        if (a.hcPfx && a.hcPfx[i] >= 0) continue;                          // (done on the list path)
-        if (a.hcx && hc_is_ctx(a, i, n, false)) continue;                  // (k_hcx's)
-        if (exMode) c = hc_compress(s, n, rec + 4, a.bsz, a.level, w, hc_dict_of(a, i, n, s, false));
-        else        c = hc_compress(s, n, rec + 4, a.bsz, a.level, hc_with_pre(w, a, g));
-        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
-        WAVE_FENCE();
-        if (c == 0) { wave_copy(rec + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
-        int len = c + 4;
-        if (a.blockChecksum) {
-            WAVE_FENCE();
-            const uint32_t x = wave_xxh32(rec + 4, c);
-            if ((threadIdx.x & 63u) == 0) st32u(rec + 4 + c, x);
-            len += 4;
-        }
-        if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[i] = len; }
-    }
-}
+__global__ __launch_bounds__(64) void k_encode_raw_hc(CodecArgs a) { hc_one_thread<true>(a); }
+__global__ __launch_bounds__(64) void k_encode_rec_hc(CodecArgs a) { hc_one_thread<false>(a); }
 
 // HC levels 2..12, the blocks <= 4 KiB under a dictionary context (usingDictCtxHc) of a call: one wave per block off the block queue,
 // the block's lists in LDS (17 KiB: nine waves per CU), the dictionary's lists read-only, nothing else in device memory but the
@@ -802,38 +684,27 @@ template <bool kRaw, bool kMid> __global__ __launch_bounds__(64) void k_hcx(Code
         const uint8_t* s = a.src + (int64_t)i * a.srcStride;
         uint8_t* const out = a.dst + (int64_t)i * a.dstStride;
         ++done;
+        // (its loop body as it always was, the writer called directly and not through encode_out: the parsers in this kernel live on
+        // spilled scalars, and the body's shape decides where they are reloaded -- profiles/block_io_resources.txt)
         if (kRaw) {
-            const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
-            const int r = compress(s, n, out, cap, d);
+            const int r = compress(s, n, out, cap_of(a, i), d);
             if ((threadIdx.x & 63u) == 0) a.result[i] = r;
             continue;
         }
-        int c = compress(s, n, out + 4, a.bsz, d);          // capacity == bsz (blk.go:73)
-        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
-        WAVE_FENCE();
-        if (c == 0) { wave_copy(out + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
-        int len = c + 4;
-        if (a.blockChecksum) {
-            WAVE_FENCE();
-            const uint32_t x = wave_xxh32(out + 4, c);
-            if ((threadIdx.x & 63u) == 0) st32u(out + 4 + c, x);
-            len += 4;
-        }
-        if ((threadIdx.x & 63u) == 0) { st32u(out, word); a.result[i] = len; }
+        const int c = compress(s, n, out + 4, a.bsz, d);    // capacity == bsz (blk.go:73)
+        const int len = wave_finish_record(out, s, n, c, a.blockChecksum != 0);
+        if ((threadIdx.x & 63u) == 0) a.result[i] = len;
     }
     if (done && (threadIdx.x & 63u) == 0) atomicAdd(&cnt[9], (unsigned long long)done);
 }
 
 // HC levels 3..12 with a dictionary and/or linked blocks on the list path (round 4): how every block of the call is primed
-// (hc_dict_of: clz4.go:181-209, :250-283), its external segment copied right in front of it, its length noted.  One wave per block.
+// (hc_prime), its external segment copied right in front of it, its length noted (hc_pfx: no segment and no context -- the first
+// block of a linked frame without a dictionary -- is an empty segment).  One wave per block.
 __global__ __launch_bounds__(64) void k_hc_ext_prep(CodecArgs a)
 {
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
-        const int n = block_len(a, i);
-        const uint8_t* s = a.src + (int64_t)i * a.srcStride;
-        const HcDict d = hc_dict_of(a, i, n, s, a.rawMode != 0);
-        // (no segment and no context -- the first block of a linked frame without a dictionary -- is an empty segment)
-        const int pfx = d.mode == kHcCtx ? -1 : (d.mode == kHcExt ? d.len : 0);
+        const int pfx = hc_pfx(hc_prime_of(a, i, block_len(a, i), a.src + (int64_t)i * a.srcStride, a.rawMode != 0));
         if ((threadIdx.x & 63u) == 0) a.hcPfx[i] = pfx;
     }
 }
@@ -1182,25 +1053,7 @@ __global__ __launch_bounds__(64) void k_hc12_parse(CodecArgs a)
             if ((threadIdx.x & 63u) == 0) a.result[i] = PLZ4HIP_E_DEVICE;     // its F is not to be trusted -- an engine failure, not a result
             continue;
         }
-        if (a.rawMode) {
-            const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
-            const int r = hc12_parse(s, n, a.dst + (int64_t)i * a.dstStride, cap, F, ch, w);
-            if ((threadIdx.x & 63u) == 0) a.result[i] = r;
-            continue;
-        }
-        uint8_t* rec = a.dst + (int64_t)i * a.dstStride;
-        int c = hc12_parse(s, n, rec + 4, a.bsz, F, ch, w);              // capacity == bsz (blk.go:73); indie.go:80-88
-        uint32_t word = (uint32_t)c & 0x7FFFFFFFu;
-        WAVE_FENCE();
-        if (c == 0) { wave_copy(rec + 4, s, n); c = n; word = 0x80000000u | ((uint32_t)n & 0x7FFFFFFFu); }
-        int len = c + 4;
-        if (a.blockChecksum) {
-            WAVE_FENCE();
-            const uint32_t x = wave_xxh32(rec + 4, c);
-            if ((threadIdx.x & 63u) == 0) st32u(rec + 4 + c, x);
-            len += 4;
-        }
-        if ((threadIdx.x & 63u) == 0) { st32u(rec, word); a.result[i] = len; }
+        encode_out(a, i, s, n, a.rawMode != 0, [&](uint8_t* out, int cap) { return hc12_parse(s, n, out, cap, F, ch, w); });
     }
 }
 
@@ -1351,14 +1204,13 @@ __global__ __launch_bounds__(64) void k_hc_dict_prime(const uint8_t* dict, int l
 
 // ---- LZ4_decompress_safe of a few blocks by the whole chip (lz4_dx_device.inl).  grid (segments, blocks) for the per-segment
 // kernels, (chunks of 1024 output bytes, blocks) for the per-byte ones; a block that any stage flags is decoded by k_decode_raw behind.
-__device__ __forceinline__ int dx_cap(const CodecArgs& a, int b) { return a.dstCap ? a.dstCap[b] : a.dstCapAll; }
 __device__ __forceinline__ const uint8_t* dx_src(const CodecArgs& a, int b) { return a.src + (a.dxSrcOff ? a.dxSrcOff[b] : (int64_t)b * a.srcStride); }
 __device__ __forceinline__ int dx_len(const CodecArgs& a, int b) { return a.dxLen ? a.dxLen[b] : a.srcLen[b]; }
 // One block's view of the call for the stage bodies (dx_stage_*, lz4_dx_device.inl)
 __device__ __forceinline__ DxBlk dx_blk(const CodecArgs& a, int b)
 {
     DxBlk k;
-    k.src = dx_src(a, b); k.n = dx_len(a, b); k.dst = a.dst + (int64_t)b * a.dstStride; k.cap = dx_cap(a, b);
+    k.src = dx_src(a, b); k.n = dx_len(a, b); k.dst = a.dst + (int64_t)b * a.dstStride; k.cap = cap_of(a, b);
     k.T = a.dxT + (int64_t)b * a.dxTStride; k.ptr = a.dxPtr + (int64_t)b * a.dxPtrStride; k.units = a.dxUnits + (int64_t)b * a.dxMaxSeg;
     k.tStride = a.dxTStride; k.pStride = a.dxPtrStride; k.maxSeg = a.dxMaxSeg;
     k.info = a.dxInfo + b; k.b = b;
@@ -1398,7 +1250,7 @@ struct KDxb {                  // raw blocks above kDxMaxOut (dxb_*): the stitch
     static DEVM void verdict(const CodecArgs& a, int b, int outLen, unsigned long long* cnt)
     {
         atomicAdd(&cnt[3], 1ull);
-        if (dx_cap(a, b) > kDxMaxOut) { atomicAdd(&cnt[10], 1ull); atomicAdd(&cnt[12], (unsigned long long)min_(a.dxbInfo[b].runs, (uint32_t)a.dxbRunRoom)); }
+        if (cap_of(a, b) > kDxMaxOut) { atomicAdd(&cnt[10], 1ull); atomicAdd(&cnt[12], (unsigned long long)min_(a.dxbInfo[b].runs, (uint32_t)a.dxbRunRoom)); }
         a.result[b] = outLen;
         if (a.status) a.status[b] = PLZ4HIP_BLK_OK;
     }
@@ -1567,7 +1419,7 @@ __global__ __launch_bounds__(64) void k_decode_raw(CodecArgs a)
     for (int i = next_block(a.queue); i < a.nBlocks; i = next_block(a.queue)) {
         if (a.dxInfo && !a.dxInfo[i].bad) continue;                          // (answered by the few-block path)
         const int n   = a.srcLen[i];
-        const int cap = a.dstCap ? a.dstCap[i] : a.dstCapAll;
+        const int cap = cap_of(a, i);
         const int r   = wave_decode_block(a.src + (int64_t)i * a.srcStride, n, a.dst + (int64_t)i * a.dstStride, cap);
         if ((threadIdx.x & 63u) == 0) a.result[i] = r;
     }
@@ -3278,8 +3130,8 @@ int plz4hip_dev_encode_body_ex(plz4hip_ctx* c, const void* src, int64_t srcBytes
     if (level == 2) {
         // (a block <= 4 KiB under a dictionary context is written by the one-thread parser behind the emit stage, into a staged record)
         const int lastLen = (int)(srcBytes - (int64_t)(nBlocks - 1) * bsz);
-        // (hc_dict_of: under ANY attached dictionary, whatever its length)
-        const bool ctxSmall = dict && (linked ? (a.prevTailLen < 0 && (nBlocks == 1 ? lastLen : bsz) <= 4096) : (lastLen <= 4096 || bsz <= 4096));
+        // (hc_prime: under ANY attached dictionary, whatever its length)
+        const bool ctxSmall = dict && (linked ? (a.prevTailLen < 0 && (nBlocks == 1 ? lastLen : bsz) <= kCtxMaxBlock) : (lastLen <= kCtxMaxBlock || bsz <= kCtxMaxBlock));
         if (ctxSmall) return fail(c, PLZ4HIP_E_UNSUPPORTED, "plz4hip_dev_encode_body_ex: level 2 with a block <= 4 KiB under a dictionary context (plz4hip_dev_encode_records_ex + plz4hip_dev_compact_records)");
         return launch_hc(c, s, a, nBlocks, bsz, 0);
     }
@@ -3395,7 +3247,7 @@ static int host_codec(plz4hip_ctx* c, int mode /*0 enc raw,1 dec raw,2 enc rec,3
             a.linked = dj->linked;
             const void* pt = dj->prevTail; int ptLen = (dj->prevTail && dj->prevTailLen >= 0) ? dj->prevTailLen : -1;
             if (dj->linked && b0 > 0) {                                   // a later chunk of a linked encode
-                const int pl = srcLen[b0 - 1]; ptLen = pl < 65536 ? pl : 65536;
+                const int pl = srcLen[b0 - 1]; ptLen = tail_len(pl);
                 pt = (const uint8_t*)src[b0 - 1] + (pl - ptLen);
             }
             if (ptLen >= 0) {

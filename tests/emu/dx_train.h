@@ -26,7 +26,7 @@ namespace plz4 {
 // what the C entries answer for a block: left to the one-wave decoder; units that do not meet (a bug); a run list beyond its room
 enum : int { kDxEmuLeft = -999999, kDxEmuUnitsDisagree = -888888, kDxEmuListOverrun = -777777 };
 
-// The call as dx_src / dx_len / dx_cap give it to the kernels: block b is len[b] bytes at src[b] (exactly that many readable; < 0:
+// The call as dx_src / dx_len / cap_of give it to the kernels: block b is len[b] bytes at src[b] (exactly that many readable; < 0:
 // not a compressed block) and has cap[b] bytes at dst + b * dstStride.
 struct DxEmuCall { int nb; const uint8_t* const* src; const int32_t* len; const int32_t* cap; uint8_t* dst; int64_t dstStride; };
 

@@ -5,6 +5,7 @@
 #include "../../plz4_amd/csrc/lz4_device.inl"
 #include "../../plz4_amd/csrc/lz4_seq_device.inl"
 #include "../../plz4_amd/csrc/lz4hc_device.inl"
+#include "../../plz4_amd/csrc/lz4_block_io.inl"       // (its own harness: emu_block_io.cpp; here it is held to this build's flags)
 #include <stdlib.h>
 
 int plz4_emu_descending = 0;

@@ -6,6 +6,7 @@
 // Test infrastructure only: built into tests/emu/_build/, never loaded by plz4_amd, not a CPU fallback.
 #define PLZ4_EMU 1
 #include "../../plz4_amd/csrc/lz4_fx_device.inl"
+#include "../../plz4_amd/csrc/lz4_block_io.inl"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -19,7 +20,7 @@ extern "C" {
 void emu_l1x_set_descending(int d) { plz4_emu_descending = d; }
 
 // src: block 0 of srcBytes bytes of contiguous plaintext in blocks of bsz, 64 KiB of writable scratch in front of it.  How block i is
-// primed is fxl_dict_of's decision (plz4hip.hip), restated: after block i - 1's last <= 64 KiB, block 0 after prevTail
+// primed is the kernels' own rule (hist_of + l1_prime, lz4_block_io.inl): after block i - 1's last <= 64 KiB, block 0 after prevTail
 // (prevTailLen >= 0), else under the dictionary context (hasDict; dict / dictLen: its last <= 64 KiB, dictTable: its table), else
 // a linked frame's first block.  Block i's compressed bytes go to dst + i * dstStride (capacity bsz), its size (0: does not fit)
 // to result[i].  order: 0 first block first, 1 last block first.  Returns 0, or a negative number when a block's run failed.
@@ -32,22 +33,13 @@ int emu_l1x_encode(uint8_t* src, long long srcBytes, int bsz, const uint8_t* dic
     const int seqStride = seq_capacity(bsz) + 1;
     std::vector<uint64_t> seq((size_t)seqStride);
     std::vector<uint8_t> bk((size_t)seqStride);
+    const HistView view{src, bsz, nullptr, srcBytes, bsz, 1, prevTail, prevTailLen, hasDict ? dict : nullptr, hasDict ? dictLen : -1};
     for (int j = 0; j < nb; ++j) {
         const int i = order ? nb - 1 - j : j;
         const long long rem = srcBytes - (long long)i * bsz;
         const int n = (int)(rem < bsz ? rem : bsz);
         uint8_t* const blk = src + (long long)i * bsz;
-        DictEnc dc{nullptr, 0, kDictFreshPrefix, nullptr};
-        const uint8_t* tail = nullptr; int tailLen = -1;
-        if (i > 0) { tailLen = bsz < 65536 ? bsz : 65536; tail = blk - tailLen; }
-        else if (prevTailLen >= 0) { tail = prevTail; tailLen = prevTailLen; }
-        if (tailLen >= 0) {
-            dc.mode = tailLen >= 8 ? kDictLoad : kDictNonePrefix;
-            if (tailLen >= 8) { dc.dict = tail; dc.dictSize = tailLen; }
-        } else if (hasDict) {
-            if (dictLen >= 8) { dc.dict = dict; dc.dictSize = dictLen; dc.dictTable = dictTable; dc.mode = n > 4096 ? kDictCtxCopy : kDictCtxLookup; }
-            else dc.mode = kDictNonePrefix;
-        }
+        const DictEnc dc = l1_prime(hist_of(view, i, n, false), false, dictTable);
         int lastAnchor = 0;
         FxlBlk xb;
         const int nseq = l1x_block(blk, n, dc.mode, dc.dict, dc.dictSize, dc.dictTable, seq.data(), seqStride - 1, &lastAnchor, &xb, lds);

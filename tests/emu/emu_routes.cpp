@@ -10,6 +10,7 @@
 #include "../../plz4_amd/csrc/lz4hcx_device.inl"
 #include "../../plz4_amd/csrc/lz4_dx_device.inl"
 #include "../../plz4_amd/csrc/lz4_fx_device.inl"
+#include "../../plz4_amd/csrc/lz4_block_io.inl"
 #include "../../plz4_amd/csrc/ws_layout.h"
 #include "../../plz4_amd/csrc/route.h"
 #include <string>

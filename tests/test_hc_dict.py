@@ -28,7 +28,7 @@ def emu():
 
 
 def _emu_records(emu, orc, blocks, bsz, level, linked, dct):
-    """The kernels' per-block priming rule (plz4hip.hip hc_dict_of) on the emulation build."""
+    """The kernels' per-block priming rule (lz4_block_io.inl hc_prime) on the emulation build."""
     d = None if dct is None else np.ascontiguousarray(dct[-65536:])
     out, prev = [], None
     for b in blocks:

@@ -16,7 +16,7 @@ from plz4_amd import synth
 
 SRC = os.path.join(ROOT, "tests", "emu", "emu_l1x.cpp")
 SO = os.path.join(ROOT, "tests", "emu", "_build", "libemu_l1x.so")
-DEPS = [SRC] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in ("lz4_fx_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "wave.h")]
+DEPS = [SRC] + [os.path.join(ROOT, "plz4_amd", "csrc", f) for f in ("lz4_fx_device.inl", "lz4_seq_device.inl", "lz4_device.inl", "lz4_block_io.inl", "wave.h")]
 PAD = 65536                                                            # the scratch in front of block 0
 i32p = C.POINTER(C.c_int)
 
