@@ -371,6 +371,32 @@ func (c *Ctx) DevEncodeBodyEx(src DevPtr, srcBytes, srcStride int64, bsz, level 
 		b2i(linked), d.ptr(), prevTail, C.int(prevTailLen), body, C.int64_t(bodyCap), (*C.int64_t)(recOff), (*C.int32_t)(recLen), stream))
 }
 
+// Why DevIndexBody stopped (BodyIndex.Status, PLZ4HIP_BODY_*).
+const (
+	BodyEndMark        = int(C.PLZ4HIP_BODY_END_MARK)        // a size word of 0; End is behind it: a content checksum or the next frame
+	BodyEndOfBytes     = int(C.PLZ4HIP_BODY_END_OF_BYTES)    // a bare block section, as the Dev*Body encoders write it
+	BodyFull           = int(C.PLZ4HIP_BODY_FULL)            // more records than maxBlocks
+	BodySizeOverflow   = int(C.PLZ4HIP_BODY_SIZE_OVERFLOW)   // zerr.ErrBlockSizeOverflow
+	BodyTruncatedWord  = int(C.PLZ4HIP_BODY_TRUNCATED_WORD)  // zerr.ErrBlockSizeRead
+	BodyTruncatedBlock = int(C.PLZ4HIP_BODY_TRUNCATED_BLOCK) // zerr.ErrBlockRead
+)
+
+// BodyIndex is plz4hip_body_index: where the walk stopped, how many records it listed, and why it stopped.
+type BodyIndex struct {
+	End     int64
+	NBlocks int32
+	Status  int32
+}
+
+// DevIndexBody lists the records of a frame body that is already in device memory (plz4hip_dev_index_body): FrameReader._read's
+// size-word walk (blk/frame.go:54-98) as one wavefront.  recOff (int64 x maxBlocks + 1) and info (a BodyIndex) are device memory;
+// recOff[NBlocks .. maxBlocks] hold the end of the last listed record, so a record decode of maxBlocks records may follow on the
+// same stream before the host has read NBlocks.  Enqueued on stream; nothing is waited for.
+func (c *Ctx) DevIndexBody(body DevPtr, bodyBytes int64, bsz int, blockChecksum bool, maxBlocks int, recOff, info DevPtr, stream unsafe.Pointer) error {
+	return c.chk(C.plz4hip_dev_index_body(c.p, body, C.int64_t(bodyBytes), C.int(bsz), b2i(blockChecksum), C.int(maxBlocks),
+		(*C.int64_t)(recOff), (*C.plz4hip_body_index)(info), stream))
+}
+
 func b2i(b bool) C.int {
 	if b {
 		return 1
@@ -483,6 +509,25 @@ func (m *Multi) DecodeRecords(rec, dst [][]byte, bsz int, blockChecksum bool) ([
 		return nil, nil, m.err(rc)
 	}
 	return toInts(res), toInts(st), nil
+}
+
+// IndexFrame lists the records of a frame body on device `owner` (plz4hip_mgpu_dev_index_frame): DevIndexBody on the owner's ctx,
+// recOff (maxBlocks + 1 entries) and the verdict copied back.  Synchronous.  recOff[:NBlocks+1] is what plz4hip_mgpu_dev_decode_frame
+// takes; a damaged size word is a Status, not an error.
+func (m *Multi) IndexFrame(owner int, body DevPtr, bodyBytes int64, bsz int, blockChecksum bool, maxBlocks int) ([]int64, BodyIndex, error) {
+	if maxBlocks < 0 {
+		return nil, BodyIndex{}, ErrEngine
+	}
+	off := make([]C.int64_t, maxBlocks+1)
+	var info C.plz4hip_body_index
+	if rc := C.plz4hip_mgpu_dev_index_frame(m.p, C.int(owner), body, C.int64_t(bodyBytes), C.int(bsz), b2i(blockChecksum), C.int(maxBlocks), &off[0], &info); rc != C.PLZ4HIP_OK {
+		return nil, BodyIndex{}, m.err(rc)
+	}
+	out := make([]int64, len(off))
+	for i, x := range off {
+		out[i] = int64(x)
+	}
+	return out, BodyIndex{End: int64(info.end), NBlocks: int32(info.nBlocks), Status: int32(info.status)}, nil
 }
 
 func toInts(v []C.int32_t) []int {

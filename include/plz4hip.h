@@ -308,7 +308,8 @@ int  plz4hip_ctx_set_content_hash(plz4hip_ctx* ctx, plz4hip_xxh32_stream* h);
  *      src     plaintext, block i = src[i*bsz, min((i+1)*bsz, srcBytes))          nBlocks = ceil(srcBytes/bsz)
  *      stage   nBlocks records at stride plz4hip_dev_stage_stride(bsz)             (scratch)
  *      recLen  int32[nBlocks]   record i length (4 + payload + 4 if checksums)
- *      recOff  int64[nBlocks+1] exclusive prefix sum of recLen (recOff[nBlocks] = body bytes)
+ *      recOff  int64[nBlocks+1] exclusive prefix sum of recLen (recOff[nBlocks] = body bytes); the encoders write it, and
+ *              plz4hip_dev_index_body reads it off a body that came from elsewhere
  *      body    the records, compacted back to back: exactly the frame's block section
  *    Decode (dev_decompress, dev_decode_records*, the decode side of dev_duplex_*), whatever the input holds: a call reads no
  *    byte outside the srcLen[i] bytes of a block / the recOff[i+1] - recOff[i] bytes of a record and the dictionary or the
@@ -355,6 +356,45 @@ int plz4hip_dev_decode_records_ex(plz4hip_ctx* ctx, const void* body, const int6
                                   int bsz, int blockChecksum, int linked, const plz4hip_dict* dict,
                                   int nChains, const int32_t* chainFirst, void* windows, int32_t* windowLen,
                                   void* dst, int64_t dstStride, int dstCap, int32_t* result, int32_t* status, void* stream);
+
+/* plz4hip_dev_index_body: recOff of a frame body that is ALREADY in device memory -- a file read there, a body received from
+ * another GPU or node, the output of any other LZ4 writer -- for the record decoders above, which until here only this engine's own
+ * encoders could feed.  It is the size-word walk of FrameReader._read (blk/frame.go:54-98) with that reader's checks, in place of a
+ * host that chases the chain four bytes and one device-to-host copy per record.  The chain is serial, so the kernel is ONE wavefront
+ * (no LDS, no workspace of the ctx; it runs beside any other launch, like the streaming checksum).  At every step, in this order:
+ *     off == bodyBytes                                   PLZ4HIP_BODY_END_OF_BYTES   end = off   (a bare block section, as plz4hip_dev_encode_body writes it)
+ *     bodyBytes - off < 4                                PLZ4HIP_BODY_TRUNCATED_WORD end = off   (zerr.ErrBlockSizeRead, frame.go:57-61)
+ *     word == 0                                          PLZ4HIP_BODY_END_MARK       end = off + 4 (frame.go:71: where a content checksum or the next frame starts)
+ *     i == maxBlocks                                     PLZ4HIP_BODY_FULL           end = off   (more records than the caller has room for)
+ *     (word & 0x7FFFFFFF) > bsz                          PLZ4HIP_BODY_SIZE_OVERFLOW  end = off   (zerr.ErrBlockSizeOverflow, frame.go:79-81)
+ *     4 + size + (blockChecksum ? 4 : 0) > bodyBytes-off PLZ4HIP_BODY_TRUNCATED_BLOCK end = off  (zerr.ErrBlockRead, frame.go:91-98)
+ *     otherwise                                          recOff[i] = off; off += 4 + size (+ 4); ++i
+ * 0x80000000 is a stored record of size 0 (descriptor/data.go:12), not an end mark: it is listed.  info->nBlocks = the records listed,
+ * info->status = why the walk stopped, info->end as above; on EVERY exit recOff[nBlocks] is the end of the last listed record and
+ * recOff[nBlocks + 1 .. maxBlocks] hold the same value.
+ * Reads: the four bytes of a size word, and only where bodyBytes - off >= 4; never a payload byte, nothing outside
+ * [body, body + bodyBytes).  Offsets are 64 bits wide and no size word overflows a test.  At most maxBlocks + 1 words are read.
+ * Without a host synchronisation: the padded tail of recOff reads as zero-length records, which the record decoders answer with
+ * PLZ4HIP_BLK_SIZE_OVERFLOW, result 0, and no byte written (in a linked chain the first of them does, and the chain's later records
+ * are PLZ4HIP_BLK_CORRUPT, result 0, nothing written, as behind any bad block of a chain).  A caller that knows only an upper bound of the block count -- from the
+ * header's content size, or bodyBytes / 5 + 1 -- enqueues this call and plz4hip_dev_decode_records[_ex] of maxBlocks records one
+ * behind the other on one stream and reads info->nBlocks afterwards.
+ * Enqueued on `stream`, no synchronisation.  body, recOff (maxBlocks + 1 entries) and info are device pointers.  PLZ4HIP_E_ARG: a null
+ * pointer (body may be null when bodyBytes == 0), bodyBytes < 0, bsz <= 0, maxBlocks < 0 or > 0x7FFFFFFE.  Headers and trailers stay
+ * on the host: `body` starts at the first record. */
+enum {
+    PLZ4HIP_BODY_END_MARK        = 0,
+    PLZ4HIP_BODY_END_OF_BYTES    = 1,
+    PLZ4HIP_BODY_FULL            = 2,
+    PLZ4HIP_BODY_SIZE_OVERFLOW   = 3,
+    PLZ4HIP_BODY_TRUNCATED_WORD  = 4,
+    PLZ4HIP_BODY_TRUNCATED_BLOCK = 5
+};
+typedef struct { int64_t end; int32_t nBlocks; int32_t status; } plz4hip_body_index;
+
+int plz4hip_dev_index_body(plz4hip_ctx* ctx, const void* body, int64_t bodyBytes, int bsz, int blockChecksum,
+                           int maxBlocks, int64_t* recOff /* device, maxBlocks + 1 */,
+                           plz4hip_body_index* info /* device */, void* stream);
 
 /* plz4hip_dev_duplex_records: plz4hip_dev_encode_records (level 1) of one batch AND plz4hip_dev_decode_records of another --
  * a writer's next batch and a reader's -- enqueued as one call, with results identical to the two calls made one after the
@@ -485,6 +525,13 @@ int plz4hip_mgpu_dev_encode_frame(plz4hip_mgpu* m, int nBlocks, const void* cons
 int plz4hip_mgpu_dev_decode_frame(plz4hip_mgpu* m, int nBlocks, int owner, const void* body, const int64_t* recOff,
                                   int bsz, int blockChecksum, void* const* shardDst, int64_t dstStride, int dstCap,
                                   int32_t* result, int32_t* status);
+/* plz4hip_mgpu_dev_index_frame: plz4hip_dev_index_body of a frame body on device `owner`, for a caller that holds only the body's
+ * bytes: the walk of FrameReader._read (blk/frame.go:54-98) on the owner's ctx and stream, then one copy back each for recOff
+ * (HOST, maxBlocks + 1 entries) and info (HOST).  Synchronous.  The caller hands info->nBlocks and recOff to
+ * plz4hip_mgpu_dev_decode_frame, whose own check of every record's length stays as it is.  A damaged size word is a status in
+ * info, not an error of the call. */
+int plz4hip_mgpu_dev_index_frame(plz4hip_mgpu* m, int owner, const void* body, int64_t bodyBytes, int bsz, int blockChecksum,
+                                 int maxBlocks, int64_t* recOff /* host, maxBlocks + 1 */, plz4hip_body_index* info /* host */);
 
 #ifdef __cplusplus
 }

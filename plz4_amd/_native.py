@@ -27,10 +27,19 @@ SYMBOLS = [
     "plz4hip_mgpu_create", "plz4hip_mgpu_destroy", "plz4hip_mgpu_count", "plz4hip_mgpu_ctx", "plz4hip_mgpu_last_error",
     "plz4hip_mgpu_compress_batch", "plz4hip_mgpu_decompress_batch", "plz4hip_mgpu_encode_records", "plz4hip_mgpu_decode_records",
     "plz4hip_mgpu_dev_encode_frame", "plz4hip_mgpu_dev_decode_frame",
+    "plz4hip_dev_index_body", "plz4hip_mgpu_dev_index_frame",
 ]
 
 E_NAMES = {0: "OK", -1: "E_ARG", -2: "E_DEVICE", -3: "E_NOMEM", -4: "E_UNSUPPORTED"}
 BLK_OK, BLK_HASH_MISMATCH, BLK_SIZE_OVERFLOW, BLK_CORRUPT = 0, 1, 2, 3
+# why plz4hip_dev_index_body stopped (plz4hip_body_index.status)
+BODY_END_MARK, BODY_END_OF_BYTES, BODY_FULL, BODY_SIZE_OVERFLOW, BODY_TRUNCATED_WORD, BODY_TRUNCATED_BLOCK = 0, 1, 2, 3, 4, 5
+BODY_NAMES = {0: "END_MARK", 1: "END_OF_BYTES", 2: "FULL", 3: "SIZE_OVERFLOW", 4: "TRUNCATED_WORD", 5: "TRUNCATED_BLOCK"}
+
+
+class BodyIndex(C.Structure):
+    """plz4hip_body_index"""
+    _fields_ = [("end", C.c_int64), ("nBlocks", C.c_int32), ("status", C.c_int32)]
 
 
 class EngineError(RuntimeError):
@@ -166,6 +175,10 @@ def load():
     L.plz4hip_mgpu_dev_decode_frame.restype = C.c_int
     L.plz4hip_mgpu_dev_decode_frame.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int64), C.c_int, C.c_int, pp, C.c_int64, C.c_int,
                                                 i32p, i32p]
+    L.plz4hip_dev_index_body.restype = C.c_int
+    L.plz4hip_dev_index_body.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.plz4hip_mgpu_dev_index_frame.restype = C.c_int
+    L.plz4hip_mgpu_dev_index_frame.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(BodyIndex)]
     if L.plz4hip_abi_version() != ABI_VERSION:
         raise ImportError("plz4_amd: libplz4hip.so ABI %d != binding %d" % (L.plz4hip_abi_version(), ABI_VERSION))
     _lib = L
@@ -366,6 +379,13 @@ class Engine:
                                                        n_chains, _i32p(cf) if cf is not None else None, windows_ptr, window_len_ptr,
                                                        dst_ptr, dst_stride, dst_cap, result_ptr, status_ptr, stream))
 
+    def dev_index_body(self, body_ptr, body_bytes, bsz, block_checksum, max_blocks, recoff_ptr, info_ptr, stream=0):
+        """recOff of a frame body that is already on the device (the size-word walk of FrameReader._read, one wavefront):
+        recoff_ptr: int64[max_blocks + 1], info_ptr: 16 bytes {int64 end, int32 nBlocks, int32 status (BODY_*)}, both on the
+        device; enqueued on `stream`, no synchronisation"""
+        self._chk(self.L.plz4hip_dev_index_body(self.h, body_ptr, body_bytes, bsz, int(block_checksum), max_blocks, recoff_ptr,
+                                                info_ptr, stream))
+
     def dev_duplex_records(self, src_ptr, src_bytes, bsz, block_checksum, stage_ptr, reclen_ptr,
                            body_ptr, recoff_ptr, ndec, dec_bsz, dec_block_checksum, dst_ptr, dst_stride, dst_cap,
                            result_ptr, status_ptr, stream=0):
@@ -520,6 +540,15 @@ class MultiEngine:
         self._chk(self.L.plz4hip_mgpu_dev_encode_frame(self.h, nblocks, sp, sb, bsz, level, int(block_checksum), owner, body_ptr, body_cap,
                                                        off, C.byref(total)))
         return np.array(off[:], dtype=np.int64), int(total.value)
+
+    def index_frame(self, owner, body_ptr, body_bytes, bsz, block_checksum, max_blocks):
+        """plz4hip_mgpu_dev_index_frame: the index of a frame body on device `owner` -> (recOff as int64[max_blocks + 1], nBlocks,
+        status (BODY_*), end); recOff[:nBlocks + 1] is what dev_decode_frame takes"""
+        off = (C.c_int64 * (max_blocks + 1))()
+        info = BodyIndex()
+        self._chk(self.L.plz4hip_mgpu_dev_index_frame(self.h, owner, body_ptr, body_bytes, bsz, int(block_checksum), max_blocks,
+                                                      off, C.byref(info)))
+        return np.array(off[:], dtype=np.int64), int(info.nBlocks), int(info.status), int(info.end)
 
     def dev_decode_frame(self, nblocks, owner, body_ptr, rec_off, bsz, block_checksum, shard_dst_ptrs, dst_stride, dst_cap):
         off = (C.c_int64 * (nblocks + 1))(*[int(x) for x in rec_off])

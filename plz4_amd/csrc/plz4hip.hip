@@ -32,6 +32,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_fx_device.inl"
 #include "lz4_mx_device.inl"
 #include "lz4_block_io.inl"
+#include "lz4_body_index_device.inl"
 #include "ws_layout.h"
 #include "route.h"
 
@@ -1556,6 +1557,18 @@ __global__ __launch_bounds__(64) void k_xxh32_stream(XxhStream* st, const uint8_
     }
 }
 
+// The index of a frame body that lies in device memory (plz4hip_dev_index_body): FrameReader._read's size-word walk, one wave,
+// no LDS, no workspace (wave_index_body, lz4_body_index_device.inl).
+static_assert(kBodyEndMark == PLZ4HIP_BODY_END_MARK && kBodyEndOfBytes == PLZ4HIP_BODY_END_OF_BYTES && kBodyFull == PLZ4HIP_BODY_FULL &&
+              kBodySizeOverflow == PLZ4HIP_BODY_SIZE_OVERFLOW && kBodyTruncatedWord == PLZ4HIP_BODY_TRUNCATED_WORD &&
+              kBodyTruncatedBlock == PLZ4HIP_BODY_TRUNCATED_BLOCK, "lz4_body_index_device.inl and plz4hip.h name the same status");
+static_assert(sizeof(BodyIndex) == sizeof(plz4hip_body_index) && sizeof(BodyIndex) == 16, "plz4hip_body_index is {int64, int32, int32}");
+__global__ __launch_bounds__(64) void k_index_body(const uint8_t* body, int64_t bodyBytes, int bsz, int blockChecksum, int maxBlocks,
+                                                   int64_t* recOff, BodyIndex* info)
+{
+    wave_index_body(body, bodyBytes, bsz, blockChecksum != 0, maxBlocks, recOff, info);
+}
+
 // Exclusive prefix sum int32 -> int64, one wave, no LDS (wave_scan_lengths).
 __global__ __launch_bounds__(64) void k_scan(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n)
 {
@@ -2925,6 +2938,19 @@ int plz4hip_dev_decode_records(plz4hip_ctx* c, const void* body, const int64_t* 
     hipStream_t s = (hipStream_t)stream;
     CodecArgs a = rec_decode_args(body, recOff, nBlocks, bsz, blockChecksum, dst, dstStride, dstCap, result, status);
     return launch_decode(c, s, a, nBlocks, bsz, dstCap, true);
+}
+
+int plz4hip_dev_index_body(plz4hip_ctx* c, const void* body, int64_t bodyBytes, int bsz, int blockChecksum,
+                           int maxBlocks, int64_t* recOff, plz4hip_body_index* info, void* stream)
+{
+    if (!c || bodyBytes < 0 || (bodyBytes && !body) || bsz <= 0 || maxBlocks < 0 || maxBlocks > 0x7FFFFFFE || !recOff || !info)
+        return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_index_body: bad argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    hipLaunchKernelGGL(k_index_body, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)body, bodyBytes, bsz, blockChecksum, maxBlocks,
+                       recOff, (BodyIndex*)info);
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
 }
 
 // Linked and dictionary records from device memory.  The call's chainFirst goes to the device by value, 64 entries per launch: the

@@ -393,4 +393,27 @@ int plz4hip_mgpu_dev_decode_frame(plz4hip_mgpu* m, int nBlocks, int owner, const
     });
 }
 
+// The index of a frame body on the owner device for a caller that holds only its bytes: the walk runs on the owner's ctx and
+// stream (plz4hip_dev_index_body), recOff and info come back in one copy each.
+int plz4hip_mgpu_dev_index_frame(plz4hip_mgpu* m, int owner, const void* body, int64_t bodyBytes, int bsz, int blockChecksum,
+                                 int maxBlocks, int64_t* recOff, plz4hip_body_index* info)
+{
+    if (!m || bodyBytes < 0 || (bodyBytes && !body) || bsz <= 0 || maxBlocks < 0 || maxBlocks > 0x7FFFFFFE || !recOff || !info)
+        return mfail(m, PLZ4HIP_E_ARG, "plz4hip_mgpu_dev_index_frame: bad argument");
+    const int G = (int)m->sh.size();
+    if (owner < 0 || owner >= G) return mfail(m, PLZ4HIP_E_ARG, "plz4hip_mgpu_dev_index_frame: owner");
+    std::lock_guard<std::mutex> g(m->mu);
+    Shard& o = m->sh[(size_t)owner];
+    const size_t offBytes = ((size_t)maxBlocks + 1) * 8;
+    if (int r = grow(m, o.device, o.recOff, offBytes + sizeof(plz4hip_body_index))) return r;
+    int64_t* const dOff = (int64_t*)o.recOff.p;
+    plz4hip_body_index* const dInfo = (plz4hip_body_index*)((char*)o.recOff.p + offBytes);
+    if (int r = plz4hip_dev_index_body(o.ctx, body, bodyBytes, bsz, blockChecksum, maxBlocks, dOff, dInfo, o.stream)) { mfail(m, r, plz4hip_last_error(o.ctx)); return r; }
+    DevGuard dg(o.device);
+    MCHK(m, hipMemcpyAsync(recOff, dOff, offBytes, hipMemcpyDeviceToHost, o.stream));
+    MCHK(m, hipMemcpyAsync(info, dInfo, sizeof(plz4hip_body_index), hipMemcpyDeviceToHost, o.stream));
+    MCHK(m, hipStreamSynchronize(o.stream));
+    return PLZ4HIP_OK;
+}
+
 }  // extern "C"
