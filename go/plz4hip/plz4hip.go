@@ -397,6 +397,64 @@ func (c *Ctx) DevIndexBody(body DevPtr, bodyBytes int64, bsz int, blockChecksum 
 		(*C.int64_t)(recOff), (*C.plz4hip_body_index)(info), stream))
 }
 
+// Why DevIndexStream stopped (StreamIndex.Status, PLZ4HIP_STREAM_*).
+const (
+	StreamEnd             = int(C.PLZ4HIP_STREAM_END)               // End == nBytes where a frame would start: the reader's clean io.EOF
+	StreamFramesFull      = int(C.PLZ4HIP_STREAM_FRAMES_FULL)       // something follows, and the frame table is full
+	StreamRecordsFull     = int(C.PLZ4HIP_STREAM_RECORDS_FULL)      // a record follows, and recOff is full
+	StreamHeaderRead      = int(C.PLZ4HIP_STREAM_HEADER_READ)       // zerr.ErrHeaderRead
+	StreamMagic           = int(C.PLZ4HIP_STREAM_MAGIC)             // zerr.ErrMagic
+	StreamVersion         = int(C.PLZ4HIP_STREAM_VERSION)           // zerr.ErrVersion
+	StreamReservedBit     = int(C.PLZ4HIP_STREAM_RESERVED_BIT)      // zerr.ErrReserveBitSet
+	StreamBlockDescriptor = int(C.PLZ4HIP_STREAM_BLOCK_DESCRIPTOR)  // zerr.ErrBlockDescriptor
+	StreamHeaderHash      = int(C.PLZ4HIP_STREAM_HEADER_HASH)       // zerr.ErrHeaderHash
+	StreamSkip            = int(C.PLZ4HIP_STREAM_SKIP)              // zerr.ErrSkip
+	StreamBody            = int(C.PLZ4HIP_STREAM_BODY)              // the last listed frame's Status says why
+	StreamContentHashRead = int(C.PLZ4HIP_STREAM_CONTENT_HASH_READ) // zerr.ErrContentHashRead
+)
+
+// FrameIndex is plz4hip_frame_index, one entry of DevIndexStream's table of frames: 64 bytes, the layout of the device entry.
+type FrameIndex struct {
+	HdrOff     int64  // the magic
+	BodyOff    int64  // the first record; skippable: the payload
+	End        int64  // behind end mark and content checksum; an incomplete frame: where its walk stopped; skippable: behind the payload
+	ContentSz  uint64 // FLG bit 3, else 0; skippable: the payload's size
+	DictId     uint32
+	ContentSum uint32 // the stored content checksum, FLG bit 2
+	FirstRec   int32  // index of its first record in recOff
+	NRecs      int32
+	Bsz        int32
+	Flags      uint8
+	BlockDesc  uint8
+	Kind       uint8 // 0 LZ4 frame, 1 skippable
+	Nibble     uint8 // skippable: magic & 15
+	Status     int32 // Body* of its walk; BodyEndMark: complete
+	Reserved   int32
+}
+
+// StreamIndex is plz4hip_stream_index: 32 bytes, the layout of the device struct.
+type StreamIndex struct {
+	End        int64
+	NFrames    int32 // table entries, skippable included
+	NRecs      int32
+	Status     int32
+	NSkippable int32
+	MaxBsz     int32
+	FlagsAnd   uint8 // over the LZ4 frames listed; 0 when there is none
+	FlagsOr    uint8
+	Pad        [2]uint8
+}
+
+// DevIndexStream lists the frames and the records of a whole LZ4 stream that is already in device memory
+// (plz4hip_dev_index_stream): the reader's header-mode / body-mode walk as one wavefront.  frames (FrameIndex x maxFrames), recOff
+// (int64 x maxRecs + 1, offsets from bytes) and info (a StreamIndex) are device memory; recOff[NRecs .. maxRecs] hold the end of the
+// last listed record, so ONE record decode of maxRecs records over all frames may follow on the same stream before the host has
+// read anything.  Enqueued on stream; nothing is waited for.
+func (c *Ctx) DevIndexStream(bytes DevPtr, nBytes int64, maxFrames, maxRecs int, frames, recOff, info DevPtr, stream unsafe.Pointer) error {
+	return c.chk(C.plz4hip_dev_index_stream(c.p, bytes, C.int64_t(nBytes), C.int(maxFrames), C.int(maxRecs),
+		(*C.plz4hip_frame_index)(frames), (*C.int64_t)(recOff), (*C.plz4hip_stream_index)(info), stream))
+}
+
 func b2i(b bool) C.int {
 	if b {
 		return 1

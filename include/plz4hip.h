@@ -381,7 +381,7 @@ int plz4hip_dev_decode_records_ex(plz4hip_ctx* ctx, const void* body, const int6
  * behind the other on one stream and reads info->nBlocks afterwards.
  * Enqueued on `stream`, no synchronisation.  body, recOff (maxBlocks + 1 entries) and info are device pointers.  PLZ4HIP_E_ARG: a null
  * pointer (body may be null when bodyBytes == 0), bodyBytes < 0, bsz <= 0, maxBlocks < 0 or > 0x7FFFFFFE.  Headers and trailers stay
- * on the host: `body` starts at the first record. */
+ * on the host: `body` starts at the first record (plz4hip_dev_index_stream below takes headers, trailers and several frames). */
 enum {
     PLZ4HIP_BODY_END_MARK        = 0,
     PLZ4HIP_BODY_END_OF_BYTES    = 1,
@@ -395,6 +395,102 @@ typedef struct { int64_t end; int32_t nBlocks; int32_t status; } plz4hip_body_in
 int plz4hip_dev_index_body(plz4hip_ctx* ctx, const void* body, int64_t bodyBytes, int bsz, int blockChecksum,
                            int maxBlocks, int64_t* recOff /* device, maxBlocks + 1 */,
                            plz4hip_body_index* info /* device */, void* stream);
+
+/* plz4hip_dev_index_stream: the index of a WHOLE LZ4 stream that is already in device memory -- any number of frames back to back,
+ * skippable frames among them: an appended log, the output of `cat a.lz4 b.lz4`, a file with a seek table.  It is the reader's whole
+ * header-mode / body-mode walk (rdr/rdr.go:242-296, header/read.go:26-119, header/skip.go:38-76, blk/frame.go:54-139) as ONE
+ * wavefront (no LDS, no workspace of the ctx), in place of a host that copies every header back, calls plz4hip_dev_index_body, waits
+ * for its end and copies the trailer back, frame after frame.  It writes a table of frames with their descriptors (skippable frames
+ * listed with where their payload lies -- what the reference offers its skip callback), and ONE recOff for every record of the stream,
+ * as offsets from `bytes`.  At every frame start `off`, in this order (hdr[k]: the byte at off + k):
+ *     off == nBytes                                      PLZ4HIP_STREAM_END               end = off   (the reader's clean io.EOF)
+ *     nFrames == maxFrames                               PLZ4HIP_STREAM_FRAMES_FULL       end = off   (something follows, and the table is full)
+ *     nBytes - off < 7                                   PLZ4HIP_STREAM_HEADER_READ       end = off   (zerr.ErrHeaderRead)
+ *     LE32 hdr[0..3] is 0x184D2A50 .. 0x184D2A5F         a skippable frame, size = LE32 hdr[4..7]:
+ *         nBytes - off < 8                               PLZ4HIP_STREAM_HEADER_READ       end = off
+ *         size > nBytes - off - 8                        PLZ4HIP_STREAM_SKIP              end = off   (zerr.ErrSkip)
+ *         otherwise                                      list it: kind 1, nibble = magic & 15, bodyOff = off + 8, contentSz = size,
+ *                                                        end = off + 8 + size, firstRec = the records listed so far, nRecs 0, bsz 0,
+ *                                                        status PLZ4HIP_BODY_END_MARK; off = end; next frame
+ *     hdr[0..3] is not 04 22 4D 18                       PLZ4HIP_STREAM_MAGIC             end = off   (zerr.ErrMagic)
+ *     FLG = hdr[4]: (FLG >> 6) != 1                      PLZ4HIP_STREAM_VERSION           end = off   (zerr.ErrVersion)
+ *     FLG & 2                                            PLZ4HIP_STREAM_RESERVED_BIT      end = off   (zerr.ErrReserveBitSet)
+ *     BD = hdr[5]: id = (BD >> 4) & 7 < 4, BD & 0x80 or BD & 0x0F
+ *                                                        PLZ4HIP_STREAM_BLOCK_DESCRIPTOR  end = off   (zerr.ErrBlockDescriptor)
+ *     len = 7 + (FLG & 8 ? 8 : 0) + (FLG & 1 ? 4 : 0) > nBytes - off
+ *                                                        PLZ4HIP_STREAM_HEADER_READ       end = off
+ *     hdr[len - 1] != (xxh32 of hdr[4 .. len - 2], seed 0) >> 8 & 0xFF
+ *                                                        PLZ4HIP_STREAM_HEADER_HASH       end = off   (zerr.ErrHeaderHash)
+ *     otherwise                                          list the frame: hdrOff = off, bodyOff = off + len, flags = FLG, blockDesc = BD,
+ *                                                        bsz = 64 KiB << 2 * (id - 4), contentSz = LE64 hdr[6..13] with FLG & 8,
+ *                                                        dictId = LE32 hdr[len - 5 .. len - 2] with FLG & 1, firstRec = the records
+ *                                                        listed so far; then the walk of plz4hip_dev_index_body from bodyOff, with that
+ *                                                        bsz, block checksums = FLG & 16 and the stream's end as the body's, its checks
+ *                                                        in its order, but off == nBytes inside a frame is PLZ4HIP_BODY_TRUNCATED_WORD
+ *                                                        (the reference: zerr.ErrBlockSizeRead; a stream has no bare block section),
+ *                                                        and `full` is the stream-wide count of records reaching maxRecs.
+ *                                                        The entry's status is the walk's, its end the walk's, nRecs what it listed.
+ *       the walk stopped with PLZ4HIP_BODY_END_MARK      FLG & 4: fewer than 4 bytes behind the end mark is
+ *                                                        PLZ4HIP_STREAM_CONTENT_HASH_READ (zerr.ErrContentHashRead; the frame stays listed,
+ *                                                        status PLZ4HIP_BODY_END_MARK, end behind the end mark), end = the entry's end;
+ *                                                        else contentSum = that LE32 and the entry's end is behind it.
+ *                                                        off = the entry's end; next frame
+ *       with PLZ4HIP_BODY_FULL                           PLZ4HIP_STREAM_RECORDS_FULL      end = the entry's end (the record that found no room)
+ *       with any other status                            PLZ4HIP_STREAM_BODY              end = the entry's end
+ * On EVERY exit info is written (nFrames counts the skippable entries too, nSkippable those alone; maxBsz, flagsAnd and flagsOr run
+ * over the LZ4 frames listed, all 0 when there is none; pad is 0); frames[0 .. nFrames) are written and the entries behind them are
+ * not touched; recOff[0 .. nRecs) are the records' offsets from `bytes` and recOff[nRecs .. maxRecs] hold the end of the last listed
+ * record (0 if there is none): the padding the record decoders answer with PLZ4HIP_BLK_SIZE_OVERFLOW, result 0, nothing written.
+ * Reads: header bytes, size words and content-checksum words, each only where the remaining length holds it; never a payload byte
+ * (a skippable frame's included), nothing outside [bytes, bytes + nBytes).  Every comparison is `need > nBytes - off` in 64 bits.
+ * Without a host synchronisation: the record decoders take a record's payload size from its size word and recOff[i + 1] - recOff[i]
+ * only as an upper bound, so the global recOff decodes although a frame's last record is followed by the end mark, the trailer and the
+ * next header before the next entry.  A caller that knows the stream's options (bsz, block checksums) passes upper bounds --
+ * nBytes / 5 + 1 records; nBytes / 7 + 1 table entries (7: the shortest header; nBytes / 8 + 1 where only skippable frames are
+ * short) -- and enqueues this call and ONE plz4hip_dev_decode_records over bytes, recOff and maxRecs records for all frames on the
+ * same stream, and reads info afterwards: flagsAnd, flagsOr and maxBsz tell whether the options it assumed held for every frame.
+ * Linked frames (FLG bit 5 clear) need the entries' firstRec on the host, as chainFirst of plz4hip_dev_decode_records_ex; a dictionary
+ * id is the caller's to resolve.  Content size and content checksum are listed, not verified (plz4hip_dev_xxh32_stream_update per
+ * frame does that).
+ * Enqueued on `stream`, no synchronisation.  bytes, frames (maxFrames entries), recOff (maxRecs + 1 entries) and info are device
+ * pointers.  PLZ4HIP_E_ARG: a null pointer (bytes may be null when nBytes == 0, frames when maxFrames == 0), nBytes < 0,
+ * maxFrames < 0, maxRecs < 0 or > 0x7FFFFFFE. */
+enum {                                   /* why the stream walk stopped */
+    PLZ4HIP_STREAM_END               = 0,
+    PLZ4HIP_STREAM_FRAMES_FULL       = 1,
+    PLZ4HIP_STREAM_RECORDS_FULL      = 2,  /* the frame is listed, status PLZ4HIP_BODY_FULL */
+    PLZ4HIP_STREAM_HEADER_READ       = 3,
+    PLZ4HIP_STREAM_MAGIC             = 4,
+    PLZ4HIP_STREAM_VERSION           = 5,
+    PLZ4HIP_STREAM_RESERVED_BIT      = 6,
+    PLZ4HIP_STREAM_BLOCK_DESCRIPTOR  = 7,
+    PLZ4HIP_STREAM_HEADER_HASH       = 8,
+    PLZ4HIP_STREAM_SKIP              = 9,
+    PLZ4HIP_STREAM_BODY              = 10, /* the last listed frame's walk did not reach an end mark: its status says why */
+    PLZ4HIP_STREAM_CONTENT_HASH_READ = 11
+};
+typedef struct {                         /* 64 bytes */
+    int64_t  hdrOff;      /* the magic */
+    int64_t  bodyOff;     /* the first record; skippable: the payload */
+    int64_t  end;         /* complete frame: first byte behind end mark and content checksum; else where its walk stopped; skippable: behind the payload */
+    uint64_t contentSz;   /* FLG bit 3, else 0; skippable: the payload's size */
+    uint32_t dictId;      /* FLG bit 0, else 0 */
+    uint32_t contentSum;  /* the stored content checksum, FLG bit 2, else 0 */
+    int32_t  firstRec;    /* index of its first record in recOff */
+    int32_t  nRecs;
+    int32_t  bsz;         /* 64 KiB << 2 * (BD id - 4); skippable: 0 */
+    uint8_t  flags, blockDesc, kind /* 0 LZ4 frame, 1 skippable */, nibble /* skippable: magic & 15 */;
+    int32_t  status;      /* PLZ4HIP_BODY_* of its walk; PLZ4HIP_BODY_END_MARK: complete (skippable: always that) */
+    int32_t  reserved;    /* 0 */
+} plz4hip_frame_index;
+typedef struct {                         /* 32 bytes */
+    int64_t end; int32_t nFrames /* table entries, skippable included */; int32_t nRecs; int32_t status; int32_t nSkippable;
+    int32_t maxBsz; uint8_t flagsAnd, flagsOr /* over the LZ4 frames listed; both 0 when there is none */; uint8_t pad[2];
+} plz4hip_stream_index;
+
+int plz4hip_dev_index_stream(plz4hip_ctx* ctx, const void* bytes, int64_t nBytes, int maxFrames, int maxRecs,
+                             plz4hip_frame_index* frames /* device, maxFrames */, int64_t* recOff /* device, maxRecs + 1 */,
+                             plz4hip_stream_index* info /* device */, void* stream);
 
 /* plz4hip_dev_duplex_records: plz4hip_dev_encode_records (level 1) of one batch AND plz4hip_dev_decode_records of another --
  * a writer's next batch and a reader's -- enqueued as one call, with results identical to the two calls made one after the

@@ -27,7 +27,7 @@ SYMBOLS = [
     "plz4hip_mgpu_create", "plz4hip_mgpu_destroy", "plz4hip_mgpu_count", "plz4hip_mgpu_ctx", "plz4hip_mgpu_last_error",
     "plz4hip_mgpu_compress_batch", "plz4hip_mgpu_decompress_batch", "plz4hip_mgpu_encode_records", "plz4hip_mgpu_decode_records",
     "plz4hip_mgpu_dev_encode_frame", "plz4hip_mgpu_dev_decode_frame",
-    "plz4hip_dev_index_body", "plz4hip_mgpu_dev_index_frame",
+    "plz4hip_dev_index_body", "plz4hip_mgpu_dev_index_frame", "plz4hip_dev_index_stream",
 ]
 
 E_NAMES = {0: "OK", -1: "E_ARG", -2: "E_DEVICE", -3: "E_NOMEM", -4: "E_UNSUPPORTED"}
@@ -40,6 +40,26 @@ BODY_NAMES = {0: "END_MARK", 1: "END_OF_BYTES", 2: "FULL", 3: "SIZE_OVERFLOW", 4
 class BodyIndex(C.Structure):
     """plz4hip_body_index"""
     _fields_ = [("end", C.c_int64), ("nBlocks", C.c_int32), ("status", C.c_int32)]
+
+
+# why plz4hip_dev_index_stream stopped (plz4hip_stream_index.status)
+(STREAM_END, STREAM_FRAMES_FULL, STREAM_RECORDS_FULL, STREAM_HEADER_READ, STREAM_MAGIC, STREAM_VERSION, STREAM_RESERVED_BIT,
+ STREAM_BLOCK_DESCRIPTOR, STREAM_HEADER_HASH, STREAM_SKIP, STREAM_BODY, STREAM_CONTENT_HASH_READ) = range(12)
+STREAM_NAMES = {0: "END", 1: "FRAMES_FULL", 2: "RECORDS_FULL", 3: "HEADER_READ", 4: "MAGIC", 5: "VERSION", 6: "RESERVED_BIT",
+                7: "BLOCK_DESCRIPTOR", 8: "HEADER_HASH", 9: "SKIP", 10: "BODY", 11: "CONTENT_HASH_READ"}
+
+
+class FrameIndex(C.Structure):
+    """plz4hip_frame_index: one entry of plz4hip_dev_index_stream's table of frames (64 bytes)"""
+    _fields_ = [("hdrOff", C.c_int64), ("bodyOff", C.c_int64), ("end", C.c_int64), ("contentSz", C.c_uint64), ("dictId", C.c_uint32),
+                ("contentSum", C.c_uint32), ("firstRec", C.c_int32), ("nRecs", C.c_int32), ("bsz", C.c_int32), ("flags", C.c_uint8),
+                ("blockDesc", C.c_uint8), ("kind", C.c_uint8), ("nibble", C.c_uint8), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StreamIndex(C.Structure):
+    """plz4hip_stream_index (32 bytes)"""
+    _fields_ = [("end", C.c_int64), ("nFrames", C.c_int32), ("nRecs", C.c_int32), ("status", C.c_int32), ("nSkippable", C.c_int32),
+                ("maxBsz", C.c_int32), ("flagsAnd", C.c_uint8), ("flagsOr", C.c_uint8), ("pad", C.c_uint8 * 2)]
 
 
 class EngineError(RuntimeError):
@@ -178,6 +198,8 @@ def load():
     L.plz4hip_dev_index_body.restype = C.c_int
     L.plz4hip_dev_index_body.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.plz4hip_mgpu_dev_index_frame.restype = C.c_int
+    L.plz4hip_dev_index_stream.restype = C.c_int
+    L.plz4hip_dev_index_stream.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]
     L.plz4hip_mgpu_dev_index_frame.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(BodyIndex)]
     if L.plz4hip_abi_version() != ABI_VERSION:
         raise ImportError("plz4_amd: libplz4hip.so ABI %d != binding %d" % (L.plz4hip_abi_version(), ABI_VERSION))
@@ -385,6 +407,12 @@ class Engine:
         device; enqueued on `stream`, no synchronisation"""
         self._chk(self.L.plz4hip_dev_index_body(self.h, body_ptr, body_bytes, bsz, int(block_checksum), max_blocks, recoff_ptr,
                                                 info_ptr, stream))
+
+    def dev_index_stream(self, bytes_ptr, n_bytes, max_frames, max_recs, frames_ptr, recoff_ptr, info_ptr, stream=0):
+        """the index of a whole LZ4 stream that is already on the device (the reader's header / body walk, one wavefront):
+        frames_ptr: max_frames FrameIndex entries, recoff_ptr: int64[max_recs + 1], offsets from bytes_ptr, info_ptr: a StreamIndex
+        (status: STREAM_*), all on the device; enqueued on `stream`, no synchronisation"""
+        self._chk(self.L.plz4hip_dev_index_stream(self.h, bytes_ptr, n_bytes, max_frames, max_recs, frames_ptr, recoff_ptr, info_ptr, stream))
 
     def dev_duplex_records(self, src_ptr, src_bytes, bsz, block_checksum, stage_ptr, reclen_ptr,
                            body_ptr, recoff_ptr, ndec, dec_bsz, dec_block_checksum, dst_ptr, dst_stride, dst_cap,

@@ -16,7 +16,9 @@
 //   * offsets are 64 bits wide and every test is `need > bodyBytes - off`, never `off + need > bodyBytes`: no size word overflows it;
 //   * the walk reads the four bytes of a size word, only where bodyBytes - off >= 4, and nothing else: no payload byte, no byte
 //     outside [body, body + bodyBytes);
-//   * it ends after at most maxBlocks + 1 loads (the last one tells an end mark from a full index).
+//   * it ends after at most maxBlocks + 1 loads (the last one tells an end mark from a full index);
+//   * the walk and the padding are two functions: the stream index (lz4_stream_index_device.inl) runs the walk once per frame over
+//     one recOff, with the stream-wide record index, and the padding once behind the last frame.
 #pragma once
 #include "wave.h"
 
@@ -34,27 +36,26 @@ enum : int {
 
 struct BodyIndex { int64_t end; int32_t nBlocks; int32_t status; };      // == plz4hip_body_index
 
-// recOff: maxBlocks + 1 entries.  On every exit recOff[0 .. nBlocks) are the listed records' offsets and
-// recOff[nBlocks .. maxBlocks] the end of the last listed one.  0 <= maxBlocks <= 0x7FFFFFFE.
-DEV void wave_index_body(const uint8_t* body, const int64_t bodyBytes, const int bsz, const bool checksum, const int maxBlocks,
-                         int64_t* recOff, BodyIndex* info)
+// The walk: FrameReader._read's steps from `off` on, over [base, base + nBytes), listing records from index i on (lane (k & 63) of
+// `held` keeps record k's offset until its group of 64 is stored, so i and held may come from an earlier walk over the same recOff:
+// plz4hip_dev_index_stream runs one walk per frame).  atEnd: what off == nBytes means to the caller.  -> why the walk stopped; off is
+// left at the end of the last listed record, i behind it, end as the table in plz4hip.h says.  Stores whole groups of 64 only.
+DEV int wave_walk_records(const uint8_t* base, const int64_t nBytes, const int bsz, const bool checksum, const int maxBlocks, const int atEnd,
+                          int64_t* recOff, LVREF(int64_t, held), int64_t& off, int& i, int64_t& end)
 {
     const int64_t tail = checksum ? 8 : 4;                  // size word + block checksum
-    int64_t off = 0, end = 0;
-    int     i = 0, status;
-    LV(int64_t, held);                                      // lane (k & 63): hop k's offset, until its group of 64 is stored
-    LANES({ held[I_] = 0; })
+    int status;
     for (;;) {
         end = off;
-        if (off == bodyBytes)    { status = kBodyEndOfBytes;    break; }
-        if (bodyBytes - off < 4) { status = kBodyTruncatedWord; break; }
-        const uint32_t word = UNI(ld32u(body + off));
+        if (off == nBytes)    { status = atEnd;              break; }
+        if (nBytes - off < 4) { status = kBodyTruncatedWord; break; }
+        const uint32_t word = UNI(ld32u(base + off));
         if (word == 0)           { status = kBodyEndMark; end = off + 4; break; }
         if (i == maxBlocks)      { status = kBodyFull;          break; }
         const uint32_t size = word & 0x7FFFFFFFu;           // 0x80000000: a stored record of size 0, not an end mark (descriptor/data.go:12)
         if (size > (uint32_t)bsz) { status = kBodySizeOverflow; break; }
         const int64_t need = (int64_t)size + tail;
-        if (need > bodyBytes - off) { status = kBodyTruncatedBlock; break; }
+        if (need > nBytes - off) { status = kBodyTruncatedBlock; break; }
         WL(held, i & 63, off);
         off += need; ++i;
         if ((i & 63) == 0) {
@@ -62,19 +63,37 @@ DEV void wave_index_body(const uint8_t* body, const int64_t bodyBytes, const int
             LANES({ recOff[g + LANE] = held[I_]; })
         }
     }
-    // the partial last group and the padding up to maxBlocks, 64 entries a store
+    return status;
+}
+
+// The padding behind the walk(s): the partial last group of the i listed records, and recOff[i .. maxBlocks] = pad, 64 entries a store.
+DEV void wave_pad_rec_off(const int i, const int64_t pad, const int maxBlocks, int64_t* recOff, LVREF(int64_t, held))
+{
     const int64_t g0 = (int64_t)(i & ~63), last = (int64_t)maxBlocks;
     const int     part = i & 63;
     LANES({
         const int64_t k = g0 + LANE;
-        if (k <= last) recOff[k] = LANE < part ? held[I_] : off;
+        if (k <= last) recOff[k] = LANE < part ? held[I_] : pad;
     })
     for (int64_t g = g0 + 64; g <= last; g += 64) {
         LANES({
             const int64_t k = g + LANE;
-            if (k <= last) recOff[k] = off;
+            if (k <= last) recOff[k] = pad;
         })
     }
+}
+
+// recOff: maxBlocks + 1 entries.  On every exit recOff[0 .. nBlocks) are the listed records' offsets and
+// recOff[nBlocks .. maxBlocks] the end of the last listed one.  0 <= maxBlocks <= 0x7FFFFFFE.
+DEV void wave_index_body(const uint8_t* body, const int64_t bodyBytes, const int bsz, const bool checksum, const int maxBlocks,
+                         int64_t* recOff, BodyIndex* info)
+{
+    int64_t off = 0, end = 0;
+    int     i = 0;
+    LV(int64_t, held);
+    LANES({ held[I_] = 0; })
+    const int status = wave_walk_records(body, bodyBytes, bsz, checksum, maxBlocks, kBodyEndOfBytes, recOff, held, off, i, end);
+    wave_pad_rec_off(i, off, maxBlocks, recOff, held);
     LANES({
         if (LANE == 0) { info->end = end; info->nBlocks = i; info->status = status; }
     })

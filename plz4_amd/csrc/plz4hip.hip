@@ -33,6 +33,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_mx_device.inl"
 #include "lz4_block_io.inl"
 #include "lz4_body_index_device.inl"
+#include "lz4_stream_index_device.inl"
 #include "ws_layout.h"
 #include "route.h"
 
@@ -1569,6 +1570,24 @@ __global__ __launch_bounds__(64) void k_index_body(const uint8_t* body, int64_t 
     wave_index_body(body, bodyBytes, bsz, blockChecksum != 0, maxBlocks, recOff, info);
 }
 
+// The index of a whole stream that lies in device memory (plz4hip_dev_index_stream): the reader's header-mode / body-mode walk, one
+// wave, no LDS, no workspace (wave_index_stream, lz4_stream_index_device.inl).
+static_assert(kStreamEnd == PLZ4HIP_STREAM_END && kStreamFramesFull == PLZ4HIP_STREAM_FRAMES_FULL && kStreamRecordsFull == PLZ4HIP_STREAM_RECORDS_FULL &&
+              kStreamHeaderRead == PLZ4HIP_STREAM_HEADER_READ && kStreamMagic == PLZ4HIP_STREAM_MAGIC && kStreamVersion == PLZ4HIP_STREAM_VERSION &&
+              kStreamReservedBit == PLZ4HIP_STREAM_RESERVED_BIT && kStreamBlockDescriptor == PLZ4HIP_STREAM_BLOCK_DESCRIPTOR &&
+              kStreamHeaderHash == PLZ4HIP_STREAM_HEADER_HASH && kStreamSkip == PLZ4HIP_STREAM_SKIP && kStreamBody == PLZ4HIP_STREAM_BODY &&
+              kStreamContentHashRead == PLZ4HIP_STREAM_CONTENT_HASH_READ, "lz4_stream_index_device.inl and plz4hip.h name the same status");
+static_assert(sizeof(FrameIndex) == sizeof(plz4hip_frame_index) && sizeof(FrameIndex) == 64 && offsetof(FrameIndex, status) == 56 &&
+              offsetof(plz4hip_frame_index, status) == 56 && offsetof(plz4hip_frame_index, flags) == 52 && offsetof(plz4hip_frame_index, dictId) == 32,
+              "plz4hip_frame_index is 64 bytes, as wave_store_frame lays it out");
+static_assert(sizeof(StreamIndex) == sizeof(plz4hip_stream_index) && sizeof(StreamIndex) == 32 && offsetof(plz4hip_stream_index, flagsAnd) == 28 &&
+              offsetof(StreamIndex, flagsAnd) == 28, "plz4hip_stream_index is 32 bytes");
+__global__ __launch_bounds__(64) void k_index_stream(const uint8_t* bytes, int64_t nBytes, int maxFrames, int maxRecs, FrameIndex* frames,
+                                                     int64_t* recOff, StreamIndex* info)
+{
+    wave_index_stream(bytes, nBytes, maxFrames, maxRecs, frames, recOff, info);
+}
+
 // Exclusive prefix sum int32 -> int64, one wave, no LDS (wave_scan_lengths).
 __global__ __launch_bounds__(64) void k_scan(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n)
 {
@@ -2949,6 +2968,19 @@ int plz4hip_dev_index_body(plz4hip_ctx* c, const void* body, int64_t bodyBytes, 
     ENTER_DEVICE(c);
     hipLaunchKernelGGL(k_index_body, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)body, bodyBytes, bsz, blockChecksum, maxBlocks,
                        recOff, (BodyIndex*)info);
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
+}
+
+int plz4hip_dev_index_stream(plz4hip_ctx* c, const void* bytes, int64_t nBytes, int maxFrames, int maxRecs, plz4hip_frame_index* frames,
+                             int64_t* recOff, plz4hip_stream_index* info, void* stream)
+{
+    if (!c || nBytes < 0 || (nBytes && !bytes) || maxFrames < 0 || (maxFrames && !frames) || maxRecs < 0 || maxRecs > 0x7FFFFFFE || !recOff || !info)
+        return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_index_stream: bad argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    hipLaunchKernelGGL(k_index_stream, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)bytes, nBytes, maxFrames, maxRecs,
+                       (FrameIndex*)frames, recOff, (StreamIndex*)info);
     HIPCHK(c, hipGetLastError());
     return PLZ4HIP_OK;
 }
