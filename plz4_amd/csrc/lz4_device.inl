@@ -1347,9 +1347,9 @@ DEV int64_t read_more_len(const uint8_t* src, int* ip, int ilimit, bool initialC
 // a scalar hop follows the real token chain through the window while the sequences are "plain" (literal run < 14,
 // literals inside the window, match length in the nibble or in one extension byte); output positions come from a
 // wave prefix sum on the DPP network; matches whose source lies before this batch's output are copied together, the
-// others ("near": the source holds bytes of this very batch) follow in rounds of mutually independent copies, long and
-// overlapping ones as one cooperative copy each.  Everything else -- long literal runs, very long matches, bad offsets,
-// the ends of the block -- is left to the exact sequential step of
+// others ("near": the source holds bytes of this very batch) follow in dependency order (the memory version: rounds of mutually
+// independent copies; the LDS-staged one: one by one), long and overlapping ones as one cooperative copy each.  Everything
+// else -- long literal runs, very long matches, bad offsets, the ends of the block -- is left to the exact sequential step of
 // wave_decode_block, which also owns liblz4's accept/reject rules.
 // Caller guarantees ip0 + 160 <= iend and op0 + 1088 <= oend (the reference is in its fast loop there).
 // Two routines over one window parse: wave_decode_plain_batch copies through memory; wave_decode_lds_batch assembles the batch's
@@ -1361,9 +1361,15 @@ enum : int { kDecTail = 32, kDecDump = kDecTail + 1024 + 64, kDecLdsBytes = kDec
 unsigned long long plz4_emu_dec[8];               // test diagnostics of the LDS-staged batch: [0] batches, [1] walks of kDecHops plain tokens, [2] near rounds, [3] cooperative copies,
                                                   // [4] of those, the ones read from memory, [5] batches without members, [6] primes of the window and
                                                   // the staged tail, [7] members
+                                                  // ([2] is a diagnostic of the emulation alone: the rounds of mutually independent near
+                                                  // matches that the batch's near matches would form, see wave_decode_lds_batch)
+unsigned long long plz4_emu_steps[4];             // the near steps of the LDS-staged batch: [0] steps that copied a match, [1] steps without one,
+                                                  // [2] the most steps with a match in one batch, [3] batches with at least one
 #define EMU_DEC(i, v) (plz4_emu_dec[(i)] += (unsigned long long)(v))
+#define EMU_STEP(i, v) (plz4_emu_steps[(i)] += (unsigned long long)(v))
 #else
 #define EMU_DEC(i, v) do {} while (0)
+#define EMU_STEP(i, v) do {} while (0)
 #endif
 // The 64 hypothetical sequences of a window, one per lane, parsed from the lane's 16 bytes; returns the mask of the plain ones.
 DEV uint64_t wave_decode_parse_window(LVREF(v16u_t, win), LVREF(uint32_t, b0), LVREF(int, ll), LVREF(int, ml), LVREF(int, off),
@@ -1537,11 +1543,12 @@ DEV int wave_decode_plain_batch(const uint8_t* __restrict__ src, uint8_t* __rest
 // scripts/micro/branch.hip, execz.hip) as far as that measured faster -- profiles/df_variants.txt has every form tried.  The caller
 // has primed `win` (the 16 bytes from ip0 + lane on) and the staged tail (lb[0, kDecTail): the output bytes before op0) -- at a
 // block's start and after every sequential step -- so the batch tests neither; the token walk makes its hops without a test; the
-// chain cuts are mask arithmetic; a batch without cooperative copies is asked nothing in its dependency rounds but the loop's own
-// test.  One question is left in the middle: a batch without members (lane 0 not plain, or its first sequence must stop) leaves
-// at once and touches nothing -- passing through as an empty batch cost more than the question (818 of them per 4 MiB text block).
-// The far loads, the literal scatter and the rounds' LDS loads keep their divergent `if`: switched-off lanes that load all the same
-// cost the memory pipeline more than the `if` costs the wave.
+// chain cuts are mask arithmetic; near matches are copied one by one in sequence order, one short step each, asked nothing but the
+// loop's own test (profiles/ns_variants.txt).  One question is left in the middle: a batch without members (lane 0 not plain, or
+// its first sequence must stop) leaves at once and touches nothing -- passing through as an empty batch cost more than the
+// question (818 of them per 4 MiB text block).
+// The far loads and the literal scatter keep their divergent `if`: switched-off lanes that load all the same cost the memory
+// pipeline more than the `if` costs the wave.
 // Returns whether the next vector batch may run: this one had members, and its end leaves 160 input bytes and 1088 bytes of room.
 enum : int { kDecHops = 22 };     // a sequence is at least three bytes: 22 tokens is all a 64-byte window holds, so 22 hops finish every walk
 DEV int wave_decode_lds_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int* ipp, int64_t* opp, LVREF(v16u_t, win),
@@ -1599,12 +1606,12 @@ DEV int wave_decode_lds_batch(const uint8_t* __restrict__ src, uint8_t* __restri
     // request the next batch's window now: its latency hides behind this batch's copies (ipn + 63 + 16 < ip0 + 160 <= iend)
     LANES({ win[I_] = *(const v16u_t*)(src + ipn + LANE); })
     // Match bytes, 4..18 per member lane.  "Far" sources end before this batch's output: all of them are copied at once.
-    // A "near" source may contain bytes this batch produces; those go in dependency order below.
+    // A "near" source may contain bytes this batch produces; those go in sequence order below.
     const uint64_t coopM = mL & BALLOT(coop[I_]);
     const uint64_t far = mL & ~coopM & BALLOT((int64_t)sp[I_] + ml[I_] <= op0);
-    // A match of 4..18 bytes travels as four overlapping pieces: [0,4) and [len-4,len) always, [len-8,len-4) from 8 bytes on,
+    // A far match of 4..18 bytes travels as four overlapping pieces: [0,4) and [len-4,len) always, [len-8,len-4) from 8 bytes on,
     // [4,12) from 12 on -- together they cover every length, and where two overlap they carry the same bytes.  Every piece
-    // has a fixed place per lane and batch, so a round is four loads and four stores; a lane that is not part of the round
+    // has a fixed place per lane and batch, so the far matches are four loads and four stores; a lane that has no far match
     // (or a piece its length does not have) stores to the dump bytes behind the buffer: a divergent `if` costs this machine
     // ~45 cycles whether any lane takes it or not, a redirected store costs a select.
     LV(int, mdst); LV(int, qoff);
@@ -1644,26 +1651,49 @@ DEV int wave_decode_lds_batch(const uint8_t* __restrict__ src, uint8_t* __restri
     put_pieces(far);
     const unsigned long long td4 = STAT_NOW(); (void)td4;
     STAT(3, td4 - td3);
-    // The rest in dependency order, LDS to LDS.  Near matches: a round takes every pending one whose source ends before the first
-    // pending match's output (the first one always qualifies: offset >= length), so nothing it reads is still to be written; rounds
-    // follow each other while a near match comes first -- the loop's own test is the only question a batch without cooperative
-    // copies is asked.  Long or overlapping matches: one cooperative copy each, when they come first.
-    for (uint64_t pend = mL & ~far; ; ) {
-        while ((pend & (0 - pend)) & ~coopM) {
-            STAT(8, 1); EMU_DEC(2, 1);
-            const int lo = RL(mdst, ctz64(pend));                                       // (an offset into lb)
-            LDS_FENCE();
-            const uint64_t go = pend & ~coopM & BALLOT(qoff[I_] + ml[I_] <= lo);
-            LANES({
-                if (LANE_IN(go)) {
-                    const uint8_t* q = lb + qoff[I_]; const int len = ml[I_];
-                    g0[I_] = ld32u(q); g1[I_] = ld32u(q + len - 4); g2[I_] = ld32u(q + max_(len - 8, 0)); g3[I_] = ld64u(q + 4);
-                }
-            })
-            LDS_FENCE();
-            put_pieces(go);
-            pend &= ~go;
+    // The rest in sequence order, LDS to LDS.  A near match (4..18 bytes, offset >= length: source and destination are disjoint) is
+    // one step: its place, its source and its length come out of one packed register by one v_readlane, and lane i copies byte i.
+    // Taken in sequence order a step has no dependency question: everything before its destination -- literals, far pieces, earlier
+    // steps -- has been issued to the LDS, and the LDS executes one wave's instructions in issue order, so a step's load sees every
+    // earlier store without a wait or a fence between them; the only wait of a step is for its own load's value, and LDS_ORDER keeps
+    // the compiler from moving a step's accesses past its neighbours'.  Long or overlapping matches stay one cooperative copy
+    // each; the near matches between two of them are a run of steps, one question a step (profiles/ns_variants.txt: steps that
+    // run ahead of the question, or two to a question, measured slower).
+    LV(uint32_t, nw);
+    {
+        const uint64_t nearM = mL & ~far & ~coopM;
+        LANES({ nw[I_] = LANE_IN(nearM) ? (uint32_t)ml[I_] | ((uint32_t)mdst[I_] << 6) | ((uint32_t)qoff[I_] << 17) : 0u; })
+    }
+#if defined(PLZ4_EMU)
+    {
+        // (what plz4_emu_dec[2] counts: rounds that take every pending near match whose source ends before the first pending one's output)
+        for (uint64_t p = mL & ~far; p; ) {
+            if ((p & (0 - p)) & coopM) { p &= p - 1; continue; }
+            const int lo = mdst[ctz64(p)];
+            p &= ~(p & ~coopM & BALLOT(qoff[I_] + ml[I_] <= lo));
+            EMU_DEC(2, 1);
         }
+    }
+    unsigned long long stepsHere = 0;
+#endif
+    auto near_step = [&](uint64_t& run) {
+        const int f = ctz64(run);
+        const uint32_t w = RL(nw, f);
+        BITCLR64(run, f);
+        const int at = (int)((w >> 6) & 0x7FFu), from = (int)(w >> 17);
+        STAT(8, (w & 63u) != 0);
+#if defined(PLZ4_EMU)
+        EMU_STEP((w & 63u) != 0 ? 0 : 1, 1); stepsHere += (w & 63u) != 0;
+#endif
+        LDS_COPY_LANES(lb, at, from, w);
+        LDS_ORDER();
+    };
+    LDS_ORDER();
+    for (uint64_t pend = mL & ~far; ; ) {
+        const uint64_t c = pend & coopM;
+        uint64_t run = pend & ((c & (0 - c)) - 1);                     // the near matches in front of the first cooperative copy
+        pend ^= run;                                                   // (that copy and what follows it)
+        while (run) near_step(run);
         if (!pend) break;
         {
             const int f = ctz64(pend), lo = RL(mdst, f), len = RL(ml, f);
@@ -1672,9 +1702,14 @@ DEV int wave_decode_lds_batch(const uint8_t* __restrict__ src, uint8_t* __restri
             LDS_FENCE();
             if (s0 + len <= op0) { LANES({ for (int i = LANE; i < len; i += 64) lb[lo + i] = dst[s0 + i]; }) }   // older than the window: from memory
             else wave_copy_match(lb, lo, RL(off, f), len);
+            LDS_ORDER();
             pend &= pend - 1;
         }
     }
+#if defined(PLZ4_EMU)
+    if (stepsHere > plz4_emu_steps[2]) plz4_emu_steps[2] = stepsHere;
+    EMU_STEP(3, stepsHere != 0);
+#endif
     LDS_FENCE();
     const unsigned long long td5 = STAT_NOW(); (void)td5;
     STAT(4, td5 - td4); STAT(6, 1);

@@ -41,6 +41,9 @@
 #define SCAN_INCL64(x) SCAN_INCL(x)                      /* the same over 64-bit values */
 #define UNI_OPAQUE(x)  do {} while (0)
 #define BITSET64(m, b) do { (m) |= 1ull << ((b) & 63); } while (0)   /* set bit (b & 63) of a wave-uniform 64-bit mask */
+#define BITCLR64(m, b) do { (m) &= ~(1ull << ((b) & 63)); } while (0)   /* clear bit (b & 63) of a wave-uniform 64-bit mask */
+/* lb[at + i] = lb[from + i] for i < (lenw & 63), lane i copying byte i; source and destination disjoint */
+#define LDS_COPY_LANES(lb, at, from, lenw) do { for (int i_ = 0; i_ < (int)((lenw) & 63u); ++i_) (lb)[(at) + i_] = (lb)[(from) + i_]; } while (0)
 #define WAVE_FENCE()   do {} while (0)
 #define LDS_FENCE()    do {} while (0)
 #define LDS_ORDER()    do {} while (0)
@@ -72,6 +75,8 @@ static inline int plz4_emu_step()  { return plz4_emu_descending ? -1 : 1; }
 // set bit (b & 63) of a wave-uniform 64-bit mask: one scalar instruction (the hardware takes the low six bits of b), where the
 // compiler forms s_lshl_b64 + s_or_b64 from the shift and the or
 #define BITSET64(m, b) __asm__("s_bitset1_b64 %0, %1" : "+s"(m) : "s"(b))
+// clear bit (b & 63) of a wave-uniform 64-bit mask: one scalar instruction, where m & (m - 1) is an add with carry and an and
+#define BITCLR64(m, b) __asm__("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(b))
 // a wave-uniform 64-bit mask as a per-lane condition: the scalar register pair itself is the select / exec mask, where
 // ((mask >> LANE) & 1) costs two v_and and a 64-bit v_cmp
 #define LANE_IN(mask)  (__builtin_amdgcn_inverse_ballot_w64((uint64_t)(mask)))
@@ -89,6 +94,30 @@ static inline int plz4_emu_step()  { return plz4_emu_descending ? -1 : 1; }
 
 __device__ __forceinline__ uint32_t plz4_readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 __device__ __forceinline__ int      plz4_readlane(int v, int l)      { return __builtin_amdgcn_readlane(v, l); }
+// LDS_COPY_LANES: lb[at + i] = lb[from + i] for i < (lenw & 63), lane i copying byte i; `lb` in LDS, source and destination
+// disjoint, called with all 64 lanes on (wave-uniform code).  The lanes are switched by the exec mask itself, s_bfm_b64 of the
+// length's six bits, and switched back on behind the store: no compare, and no s_cbranch_execz -- the compiler's divergent `if`
+// keeps that branch around every LDS access (scripts/micro/execz.hip: 45-58 cycles a time).  The one wait is for the load's value;
+// the store needs none: the LDS executes a wave's instructions in issue order.
+// Two requirements on the caller, because the compiler sees neither the exec write nor its hazards: (1) exec is all ones on
+// entry -- it is set back to -1, not to a saved value; (2) no DPP instruction may follow within five wait states of the call
+// (an SALU write of exec in front of a VALU DPP): the caller's loop test, its branch and the next step's scalar unpack stand there.
+__device__ __forceinline__ void plz4_lds_copy_lanes(uint8_t* lb, int at, int from, uint32_t lenw)
+{
+    const uint32_t base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lb + (threadIdx.x & 63u);
+    uint32_t a, b, t;
+    __asm__ volatile("v_add_u32 %[a], %[from], %[base]\n\t"
+                     "v_add_u32 %[b], %[at], %[base]\n\t"
+                     "s_bfm_b64 exec, %[lenw], 0\n\t"
+                     "ds_read_u8 %[t], %[a]\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\t"
+                     "ds_write_b8 %[b], %[t]\n\t"
+                     "s_mov_b64 exec, -1"
+                     : [a] "=&v"(a), [b] "=&v"(b), [t] "=&v"(t)
+                     : [from] "s"(from), [at] "s"(at), [lenw] "s"(lenw), [base] "v"(base)
+                     : "memory");
+}
+#define LDS_COPY_LANES(lb, at, from, lenw) plz4_lds_copy_lanes((lb), (at), (from), (lenw))
 __device__ __forceinline__ uint64_t plz4_readlane(uint64_t v, int l)
 {
     uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);

@@ -38,7 +38,7 @@ print("ll>=14:",(ll>=14).mean(),"ml>=19:",(ml>=19).mean(), "ml>273", (ml>273).me
 outLen=ll+ml; outStart=np.cumsum(outLen)-outLen
 def plain(i): return ll[i]<14 and ml[i]<=273
 def rounds(lo,hi):
-    """near rounds for sequences [lo,hi) batch whose output starts at outStart[lo]; returns (#far, #near_rounds, #coop)"""
+    """near rounds for sequences [lo,hi) batch whose output starts at outStart[lo]; returns (#far, #near_rounds, #coop, #near)"""
     op0=outStart[lo]
     idx=np.arange(lo,hi)
     mst=outStart[idx]+ll[idx]      # match dst start
@@ -46,6 +46,7 @@ def rounds(lo,hi):
     coop=(ml[idx]>18)|(off[idx]<ml[idx])
     far=(~coop)&(sp+ml[idx]<=op0)
     pend=list(np.nonzero(~far)[0])
+    nnear=int((~far&~coop).sum())
     r=0;nco=0
     while pend:
         f=pend[0]
@@ -55,10 +56,11 @@ def rounds(lo,hi):
         go=[j for j in pend if (not coop[j]) and sp[j]+ml[idx][j]<=lo_]
         r+=1
         gs=set(go); pend=[j for j in pend if j not in gs]
-    return int(far.sum()), r, nco
+    return int(far.sum()), r, nco, nnear
 # current scheme: window of 64 input bytes
 def sim(mode,cap=64,maxout=1024,maxwin=6):
     i=0;nb=0;tr=0;tco=0;tw=0;tm=0;seqstep=0
+    hn=np.zeros(23,dtype=np.int64);hc=np.zeros(23,dtype=np.int64)    # batches by their near matches (one step each) / cooperative copies
     while i<len(seqs)-1:
         if not plain(i): seqstep+=1;i+=1;continue
         j=i;ip0=S[i,0];w=0
@@ -73,10 +75,17 @@ def sim(mode,cap=64,maxout=1024,maxwin=6):
                     wstart=S[j,0]; w+=1
                 j+=1
         if j==i: seqstep+=1;i+=1;continue
-        f,r,nco=rounds(i,j)
+        f,r,nco,nn=rounds(i,j)
         nb+=1;tr+=r;tco+=nco;tw+=w;tm+=j-i
+        hn[min(nn,22)]+=1;hc[min(nco,22)]+=1
         i=j
     print(f"mode {mode} cap {cap}: batches {nb} windows {tw} members/batch {tm/nb:.1f} near rounds/batch {tr/nb:.2f} coop/batch {tco/nb:.2f} seqsteps {seqstep}  | per 64B-window: rounds {tr/tw:.2f} coop {tco/tw:.2f}")
+    if mode==0:
+        # the near steps of wave_decode_lds_batch: one per simple near match, a cooperative copy ends a run of them
+        print(f"   simple near matches/batch {(hn*np.arange(23)).sum()/nb:.2f}  cooperative copies/batch {(hc*np.arange(23)).sum()/nb:.2f}")
+        print("   near matches per batch, % of batches:  "+"  ".join(f"{k}: {100*hn[k]/nb:.1f}" for k in range(23) if hn[k]))
+        print("   cumulative %:                          "+"  ".join(f"<={k}: {100*hn[:k+1].sum()/nb:.1f}" for k in (2,4,6,8,10)))
+        print("   cooperative copies per batch, %:       "+"  ".join(f"{k}: {100*hc[k]/nb:.1f}" for k in range(23) if hc[k]))
     return nb,tw,tr,tco
 sim(0)
 for cap in (32,48,64):
