@@ -455,6 +455,52 @@ func (c *Ctx) DevIndexStream(bytes DevPtr, nBytes int64, maxFrames, maxRecs int,
 		(*C.plz4hip_frame_index)(frames), (*C.int64_t)(recOff), (*C.plz4hip_stream_index)(info), stream))
 }
 
+// A frame's verdict (FrameVerdict.Status, StreamVerdict.Status).
+const (
+	FrameOk          = int(C.PLZ4HIP_FRAME_OK)
+	FrameSkippable   = int(C.PLZ4HIP_FRAME_SKIPPABLE)
+	FrameRange       = int(C.PLZ4HIP_FRAME_RANGE)        // the table or a result points outside the decode's arrays
+	FrameBlock       = int(C.PLZ4HIP_FRAME_BLOCK)        // a block did not decode: BlockStatus is its Blk* status
+	FrameIncomplete  = int(C.PLZ4HIP_FRAME_INCOMPLETE)   // the index stopped inside this frame
+	FrameContentHash = int(C.PLZ4HIP_FRAME_CONTENT_HASH) // zerr.ErrContentHash
+	FrameContentSize = int(C.PLZ4HIP_FRAME_CONTENT_SIZE) // zerr.ErrContentSize
+)
+
+// FrameVerdict is plz4hip_frame_verdict, DevVerifyFrames' answer for one entry of the table of frames: 32 bytes, the layout of the
+// device entry.
+type FrameVerdict struct {
+	ContentSz   uint64 // plaintext bytes counted
+	ContentSum  uint32 // their xxh32 where the frame is complete and stores one, else 0
+	Status      int32  // Frame*
+	FirstBad    int32  // stream-wide index of the record that stopped the walk, or -1
+	BlockStatus int32  // FrameBlock: that record's status
+	Reserved    [2]int32
+}
+
+// StreamVerdict is plz4hip_stream_verdict: 32 bytes, the layout of the device struct.
+type StreamVerdict struct {
+	ContentBytes  int64 // the plaintext a reader delivers before it errors; no bad frame: all of it
+	FirstBadFrame int32 // the lowest entry that is neither FrameOk nor FrameSkippable, or -1
+	Status        int32 // that frame's verdict, or 0
+	NFrames       int32
+	NOk           int32
+	NSkippable    int32
+	Reserved      int32
+}
+
+// DevVerifyFrames gives the verdict on every frame that DevIndexStream listed (frames, info) and ONE DevDecodeRecords[Ex] over the
+// global recOff decoded (dst, dstStride, dstCap, result, status, maxRecs: that call's) -- every block decoded, the plaintext hashes
+// to the stored content checksum, there is as much of it as the header promised (plz4hip_dev_verify_frames): what the reference's
+// reader checks before it reads the next header, for all frames at once, sixteen frames to a wavefront.  verdicts (FrameVerdict x
+// maxFrames) and sv (a StreamVerdict) are device memory, as is everything else.  Enqueued on stream behind index and decode;
+// nothing is waited for.
+func (c *Ctx) DevVerifyFrames(frames, info DevPtr, maxFrames int, dst DevPtr, dstStride int64, dstCap int, result, status DevPtr,
+	maxRecs int, verdicts, sv DevPtr, stream unsafe.Pointer) error {
+	return c.chk(C.plz4hip_dev_verify_frames(c.p, (*C.plz4hip_frame_index)(frames), (*C.plz4hip_stream_index)(info), C.int(maxFrames),
+		dst, C.int64_t(dstStride), C.int(dstCap), (*C.int32_t)(result), (*C.int32_t)(status), C.int(maxRecs),
+		(*C.plz4hip_frame_verdict)(verdicts), (*C.plz4hip_stream_verdict)(sv), stream))
+}
+
 func b2i(b bool) C.int {
 	if b {
 		return 1

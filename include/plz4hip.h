@@ -450,8 +450,8 @@ int plz4hip_dev_index_body(plz4hip_ctx* ctx, const void* body, int64_t bodyBytes
  * short) -- and enqueues this call and ONE plz4hip_dev_decode_records over bytes, recOff and maxRecs records for all frames on the
  * same stream, and reads info afterwards: flagsAnd, flagsOr and maxBsz tell whether the options it assumed held for every frame.
  * Linked frames (FLG bit 5 clear) need the entries' firstRec on the host, as chainFirst of plz4hip_dev_decode_records_ex; a dictionary
- * id is the caller's to resolve.  Content size and content checksum are listed, not verified (plz4hip_dev_xxh32_stream_update per
- * frame does that).
+ * id is the caller's to resolve.  Content size and content checksum are listed, not verified: plz4hip_dev_verify_frames below does
+ * that for all frames at once, behind the decode.
  * Enqueued on `stream`, no synchronisation.  bytes, frames (maxFrames entries), recOff (maxRecs + 1 entries) and info are device
  * pointers.  PLZ4HIP_E_ARG: a null pointer (bytes may be null when nBytes == 0, frames when maxFrames == 0), nBytes < 0,
  * maxFrames < 0, maxRecs < 0 or > 0x7FFFFFFE. */
@@ -491,6 +491,76 @@ typedef struct {                         /* 32 bytes */
 int plz4hip_dev_index_stream(plz4hip_ctx* ctx, const void* bytes, int64_t nBytes, int maxFrames, int maxRecs,
                              plz4hip_frame_index* frames /* device, maxFrames */, int64_t* recOff /* device, maxRecs + 1 */,
                              plz4hip_stream_index* info /* device */, void* stream);
+
+/* plz4hip_dev_verify_frames: the verdict on EVERY frame of a stream that plz4hip_dev_index_stream listed and one
+ * plz4hip_dev_decode_records[_ex] over the global recOff decoded -- what the reference's reader checks before it reads the next header:
+ * every block decoded, the plaintext hashes to the stored content checksum (zerr.ErrContentHash, async/reader.go:236-241,
+ * sync/reader.go:56-67), and there is as much of it as the header promised (zerr.ErrContentSize, rdr/rdr.go:91-101).  It completes
+ * index -> decode -> verify on one stream without a host in between: the host reads info, sv and, where sv names a bad frame, that
+ * frame's verdict.  dst, dstStride, dstCap, result, status and maxRecs are those of the ONE record decode (record i left result[i] bytes
+ * at dst + i * dstStride); which decoder ran does not matter.  nFrames = info->nFrames, read on the device and clamped to
+ * [0, maxFrames].  For every frame f < nFrames, in this order:
+ *     kind == 1                                          PLZ4HIP_FRAME_SKIPPABLE     all other fields 0, nothing read
+ *     firstRec < 0, nRecs < 0 or firstRec + nRecs > maxRecs (64 bits)
+ *                                                        PLZ4HIP_FRAME_RANGE         firstBad = -1, nothing read
+ *     records i = firstRec .. firstRec + nRecs - 1, in order:
+ *         status[i] != PLZ4HIP_BLK_OK                    PLZ4HIP_FRAME_BLOCK         firstBad = i, blockStatus = status[i]; stop
+ *         result[i] < 0 or > dstCap                      PLZ4HIP_FRAME_RANGE         firstBad = i; stop
+ *         otherwise                                      contentSz += result[i]; where the entry's status is PLZ4HIP_BODY_END_MARK and
+ *                                                        FLG & 4, those bytes go into the frame's hash
+ *     the entry's status != PLZ4HIP_BODY_END_MARK        PLZ4HIP_FRAME_INCOMPLETE    (the index stopped inside this frame)
+ *     FLG & 4 and the sum differs from the entry's contentSum
+ *                                                        PLZ4HIP_FRAME_CONTENT_HASH
+ *     FLG & 8 and contentSz differs from the entry's contentSz
+ *                                                        PLZ4HIP_FRAME_CONTENT_SIZE
+ *     otherwise                                          PLZ4HIP_FRAME_OK
+ * Hash before size is the reference's order (NextBlock turns the end mark into ErrContentHash before handleEndMark runs).
+ * contentSz is always the bytes counted before the walk stopped; contentSum is the xxh32 (seed 0) of exactly those bytes whenever
+ * the entry is an LZ4 frame that is complete and stores a checksum (status PLZ4HIP_BODY_END_MARK, FLG & 4), whatever the verdict
+ * -- of no bytes where the walk never started -- and 0 otherwise; firstBad = -1 and blockStatus = 0 where no record stopped the
+ * walk; reserved is 0.  verdicts[nFrames .. maxFrames) are not touched.
+ * Reads: info->nFrames; frames[0 .. nFrames); status[i] and result[i] of the listed records up to the first bad one; the first
+ * result[i] bytes at dst + i * dstStride, only for frames that are hashed and only after that result[i] passed its range check.
+ * Nothing else.
+ * The stream verdict sv is written on every exit: nFrames = the clamped count; nSkippable and nOk count over the table;
+ * firstBadFrame = the lowest f whose verdict is neither OK nor SKIPPABLE, or -1, and status = that frame's (or 0); contentBytes = the
+ * sum of contentSz over the frames before it plus its own -- the plaintext a reader delivers before it errors -- and with no bad frame
+ * the sum over all frames.  info->status of the index stays the caller's to read: a walk that stopped at a bad header is not this
+ * call's business.
+ * The kernels: sixteen frames per wavefront, four lanes a frame (a frame's xxh32 is four serial chains: there is no combine
+ * operator), one-wave workgroups that stride over the table -- at most ceil(maxFrames / 16) of them and at most
+ * plz4hip_dev_resident_waves(ctx, 1), so a loose maxFrames such as nBytes / 7 + 1 costs no empty launch -- then one wavefront that
+ * folds the verdicts into sv.  No LDS, no workspace of the ctx, no atomics.  Known limit: one frame is one chain, so a stream of few
+ * huge frames is verified at one chain's rate per frame, and the sixteen frames of a wave finish with its longest.
+ * Enqueued on `stream`, no synchronisation.  Every pointer is a device pointer.  PLZ4HIP_E_ARG: a null pointer (frames and verdicts
+ * may be null when maxFrames == 0, dst when maxFrames == 0 or maxRecs == 0), maxFrames < 0, maxRecs < 0 or > 0x7FFFFFFE, dstCap < 0,
+ * dstStride < dstCap. */
+enum {
+    PLZ4HIP_FRAME_OK           = 0,
+    PLZ4HIP_FRAME_SKIPPABLE    = 1,
+    PLZ4HIP_FRAME_RANGE        = 2,  /* the table or a result points outside the decode's arrays */
+    PLZ4HIP_FRAME_BLOCK        = 3,  /* a block did not decode: blockStatus is its PLZ4HIP_BLK_* */
+    PLZ4HIP_FRAME_INCOMPLETE   = 4,
+    PLZ4HIP_FRAME_CONTENT_HASH = 5,  /* zerr.ErrContentHash */
+    PLZ4HIP_FRAME_CONTENT_SIZE = 6   /* zerr.ErrContentSize */
+};
+typedef struct {                         /* 32 bytes */
+    uint64_t contentSz;   /* plaintext bytes counted */
+    uint32_t contentSum;  /* their xxh32 where the frame is complete and stores one, else 0 */
+    int32_t  status;      /* PLZ4HIP_FRAME_* */
+    int32_t  firstBad;    /* stream-wide index of the record that stopped the walk, or -1 */
+    int32_t  blockStatus; /* PLZ4HIP_FRAME_BLOCK: that record's status, else 0 */
+    int32_t  reserved[2]; /* 0 */
+} plz4hip_frame_verdict;
+typedef struct {                         /* 32 bytes */
+    int64_t contentBytes; int32_t firstBadFrame; int32_t status; int32_t nFrames; int32_t nOk; int32_t nSkippable; int32_t reserved;
+} plz4hip_stream_verdict;
+
+int plz4hip_dev_verify_frames(plz4hip_ctx* ctx, const plz4hip_frame_index* frames, const plz4hip_stream_index* info,
+                              int maxFrames, const void* dst, int64_t dstStride, int dstCap,
+                              const int32_t* result, const int32_t* status, int maxRecs,
+                              plz4hip_frame_verdict* verdicts /* device, maxFrames */,
+                              plz4hip_stream_verdict* sv /* device */, void* stream);
 
 /* plz4hip_dev_duplex_records: plz4hip_dev_encode_records (level 1) of one batch AND plz4hip_dev_decode_records of another --
  * a writer's next batch and a reader's -- enqueued as one call, with results identical to the two calls made one after the

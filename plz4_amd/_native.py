@@ -28,6 +28,7 @@ SYMBOLS = [
     "plz4hip_mgpu_compress_batch", "plz4hip_mgpu_decompress_batch", "plz4hip_mgpu_encode_records", "plz4hip_mgpu_decode_records",
     "plz4hip_mgpu_dev_encode_frame", "plz4hip_mgpu_dev_decode_frame",
     "plz4hip_dev_index_body", "plz4hip_mgpu_dev_index_frame", "plz4hip_dev_index_stream",
+    "plz4hip_dev_verify_frames",
 ]
 
 E_NAMES = {0: "OK", -1: "E_ARG", -2: "E_DEVICE", -3: "E_NOMEM", -4: "E_UNSUPPORTED"}
@@ -60,6 +61,23 @@ class StreamIndex(C.Structure):
     """plz4hip_stream_index (32 bytes)"""
     _fields_ = [("end", C.c_int64), ("nFrames", C.c_int32), ("nRecs", C.c_int32), ("status", C.c_int32), ("nSkippable", C.c_int32),
                 ("maxBsz", C.c_int32), ("flagsAnd", C.c_uint8), ("flagsOr", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+# a frame's verdict (plz4hip_frame_verdict.status, plz4hip_stream_verdict.status)
+FRAME_OK, FRAME_SKIPPABLE, FRAME_RANGE, FRAME_BLOCK, FRAME_INCOMPLETE, FRAME_CONTENT_HASH, FRAME_CONTENT_SIZE = range(7)
+FRAME_NAMES = {0: "OK", 1: "SKIPPABLE", 2: "RANGE", 3: "BLOCK", 4: "INCOMPLETE", 5: "CONTENT_HASH", 6: "CONTENT_SIZE"}
+
+
+class FrameVerdict(C.Structure):
+    """plz4hip_frame_verdict: plz4hip_dev_verify_frames' answer for one entry of the table of frames (32 bytes)"""
+    _fields_ = [("contentSz", C.c_uint64), ("contentSum", C.c_uint32), ("status", C.c_int32), ("firstBad", C.c_int32),
+                ("blockStatus", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class StreamVerdict(C.Structure):
+    """plz4hip_stream_verdict (32 bytes)"""
+    _fields_ = [("contentBytes", C.c_int64), ("firstBadFrame", C.c_int32), ("status", C.c_int32), ("nFrames", C.c_int32),
+                ("nOk", C.c_int32), ("nSkippable", C.c_int32), ("reserved", C.c_int32)]
 
 
 class EngineError(RuntimeError):
@@ -200,6 +218,8 @@ def load():
     L.plz4hip_mgpu_dev_index_frame.restype = C.c_int
     L.plz4hip_dev_index_stream.restype = C.c_int
     L.plz4hip_dev_index_stream.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.plz4hip_dev_verify_frames.restype = C.c_int
+    L.plz4hip_dev_verify_frames.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     L.plz4hip_mgpu_dev_index_frame.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(BodyIndex)]
     if L.plz4hip_abi_version() != ABI_VERSION:
         raise ImportError("plz4_amd: libplz4hip.so ABI %d != binding %d" % (L.plz4hip_abi_version(), ABI_VERSION))
@@ -413,6 +433,15 @@ class Engine:
         frames_ptr: max_frames FrameIndex entries, recoff_ptr: int64[max_recs + 1], offsets from bytes_ptr, info_ptr: a StreamIndex
         (status: STREAM_*), all on the device; enqueued on `stream`, no synchronisation"""
         self._chk(self.L.plz4hip_dev_index_stream(self.h, bytes_ptr, n_bytes, max_frames, max_recs, frames_ptr, recoff_ptr, info_ptr, stream))
+
+    def dev_verify_frames(self, frames_ptr, info_ptr, max_frames, dst_ptr, dst_stride, dst_cap, result_ptr, status_ptr, max_recs,
+                          verdicts_ptr, sv_ptr, stream=0):
+        """the verdict on every frame that dev_index_stream listed (frames_ptr, info_ptr) and one dev_decode_records[_ex] over the
+        global recOff decoded (dst_ptr, dst_stride, dst_cap, result_ptr, status_ptr, max_recs: that call's): blocks, content
+        checksum, content size.  verdicts_ptr: max_frames FrameVerdict entries (status: FRAME_*), sv_ptr: a StreamVerdict, both on
+        the device; enqueued on `stream`, no synchronisation"""
+        self._chk(self.L.plz4hip_dev_verify_frames(self.h, frames_ptr, info_ptr, max_frames, dst_ptr, dst_stride, dst_cap, result_ptr,
+                                                   status_ptr, max_recs, verdicts_ptr, sv_ptr, stream))
 
     def dev_duplex_records(self, src_ptr, src_bytes, bsz, block_checksum, stage_ptr, reclen_ptr,
                            body_ptr, recoff_ptr, ndec, dec_bsz, dec_block_checksum, dst_ptr, dst_stride, dst_cap,

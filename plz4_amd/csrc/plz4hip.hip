@@ -34,6 +34,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_block_io.inl"
 #include "lz4_body_index_device.inl"
 #include "lz4_stream_index_device.inl"
+#include "lz4_frame_verify_device.inl"
 #include "ws_layout.h"
 #include "route.h"
 
@@ -1588,6 +1589,27 @@ __global__ __launch_bounds__(64) void k_index_stream(const uint8_t* bytes, int64
     wave_index_stream(bytes, nBytes, maxFrames, maxRecs, frames, recOff, info);
 }
 
+// The verdict on every frame of a decoded stream (plz4hip_dev_verify_frames): sixteen frames' xxh32 chains per wave over the pieces
+// a record decode left, one-wave workgroups that stride over the table, no LDS, no workspace (wave_verify_frames,
+// lz4_frame_verify_device.inl); behind it one wave that folds the verdicts into the stream's (wave_verify_summary).
+static_assert(kFrameOk == PLZ4HIP_FRAME_OK && kFrameSkippable == PLZ4HIP_FRAME_SKIPPABLE && kFrameRange == PLZ4HIP_FRAME_RANGE &&
+              kFrameBlock == PLZ4HIP_FRAME_BLOCK && kFrameIncomplete == PLZ4HIP_FRAME_INCOMPLETE && kFrameContentHash == PLZ4HIP_FRAME_CONTENT_HASH &&
+              kFrameContentSize == PLZ4HIP_FRAME_CONTENT_SIZE && PLZ4HIP_BLK_OK == 0, "lz4_frame_verify_device.inl and plz4hip.h name the same status");
+static_assert(sizeof(FrameVerdict) == sizeof(plz4hip_frame_verdict) && sizeof(FrameVerdict) == 32 && offsetof(plz4hip_frame_verdict, status) == 12 &&
+              offsetof(FrameVerdict, status) == 12 && offsetof(plz4hip_frame_verdict, blockStatus) == 20, "plz4hip_frame_verdict is 32 bytes");
+static_assert(sizeof(StreamVerdict) == sizeof(plz4hip_stream_verdict) && sizeof(StreamVerdict) == 32 && offsetof(plz4hip_stream_verdict, nFrames) == 16 &&
+              offsetof(StreamVerdict, nFrames) == 16, "plz4hip_stream_verdict is 32 bytes");
+__global__ __launch_bounds__(64) void k_verify_frames(const FrameIndex* frames, const StreamIndex* info, int maxFrames, const uint8_t* dst,
+                                                      int64_t dstStride, int dstCap, const int32_t* result, const int32_t* status, int maxRecs,
+                                                      FrameVerdict* verdicts)
+{
+    wave_verify_frames(frames, info, maxFrames, dst, dstStride, dstCap, result, status, maxRecs, verdicts, (int)blockIdx.x, (int)gridDim.x);
+}
+__global__ __launch_bounds__(64) void k_verify_summary(const StreamIndex* info, int maxFrames, const FrameVerdict* verdicts, StreamVerdict* sv)
+{
+    wave_verify_summary(info, maxFrames, verdicts, sv);
+}
+
 // Exclusive prefix sum int32 -> int64, one wave, no LDS (wave_scan_lengths).
 __global__ __launch_bounds__(64) void k_scan(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n)
 {
@@ -2981,6 +3003,37 @@ int plz4hip_dev_index_stream(plz4hip_ctx* c, const void* bytes, int64_t nBytes, 
     ENTER_DEVICE(c);
     hipLaunchKernelGGL(k_index_stream, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)bytes, nBytes, maxFrames, maxRecs,
                        (FrameIndex*)frames, recOff, (StreamIndex*)info);
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
+}
+
+// PLZ4HIP_VERIFY_WAVES (read per call): the cap on k_verify_frames' grid, for tests of its stride loop
+static int verify_waves_cap(const plz4hip_ctx* c)
+{
+    int cap = c->decWaves > 0 ? c->decWaves : 1;
+    if (const char* v = getenv("PLZ4HIP_VERIFY_WAVES")) { const int w = atoi(v); if (w >= 1 && w <= cap) cap = w; }
+    return cap;
+}
+
+int plz4hip_dev_verify_frames(plz4hip_ctx* c, const plz4hip_frame_index* frames, const plz4hip_stream_index* info, int maxFrames,
+                              const void* dst, int64_t dstStride, int dstCap, const int32_t* result, const int32_t* status, int maxRecs,
+                              plz4hip_frame_verdict* verdicts, plz4hip_stream_verdict* sv, void* stream)
+{
+    if (!c || !info || !sv || !result || !status || maxFrames < 0 || maxRecs < 0 || maxRecs > 0x7FFFFFFE || dstCap < 0 || dstStride < dstCap ||
+        (maxFrames && (!frames || !verdicts)) || (maxFrames && maxRecs && !dst))   // (no table or no record: nothing of dst could be read)
+        return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_verify_frames: bad argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    ENTER_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (maxFrames > 0) {
+        const int64_t groups = ((int64_t)maxFrames + 15) / 16;
+        const int cap = verify_waves_cap(c);
+        const int grid = groups < cap ? (int)groups : cap;
+        hipLaunchKernelGGL(k_verify_frames, dim3(grid), dim3(64), 0, s, (const FrameIndex*)frames, (const StreamIndex*)info, maxFrames,
+                           (const uint8_t*)dst, dstStride, dstCap, result, status, maxRecs, (FrameVerdict*)verdicts);
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_verify_summary, dim3(1), dim3(64), 0, s, (const StreamIndex*)info, maxFrames, (const FrameVerdict*)verdicts, (StreamVerdict*)sv);
     HIPCHK(c, hipGetLastError());
     return PLZ4HIP_OK;
 }

@@ -54,13 +54,17 @@ def host_loop(hip, eng, base, n_bytes, max_recs, recoff_ptr, info_ptr, stream):
     return frames, recs
 
 
-def measure(name, bsz, bd_id, per_frame, want_frames):
+class Built:
+    """what build_stream leaves: d_stream (n_bytes), d_body (body_bytes: the encoder's bare block section; the caller deletes it),
+    nf frames of per_frame records, nb records, frame_at (every frame's offset), want_off (every record's), the host's pool"""
+
+
+def build_stream(eng, bsz, bd_id, per_frame, want_frames, sums=None):
+    """the stream of a shape on the device: frame f = header, records [f * per_frame, (f + 1) * per_frame), end mark, content
+    checksum.  sums(pool, nf) -> the nf content checksums (uint32) to store; None: zeros"""
     import torch
     from plz4_amd import host, synth
-    from plz4_amd._native import Engine, FrameIndex, StreamIndex, BODY_END_OF_BYTES, STREAM_END
     dev = torch.device("cuda:0")
-    hip = hip_runtime()
-    eng = Engine(0)
     free, _ = torch.cuda.mem_get_info()
     per_block = bsz + 2 * (bsz + 8) + bsz + (9 * bsz) // 4 + 64         # plaintext, body, stream, decoded output / the level-1 workspace
     nf = int(min(want_frames, (free * 7 // 10) // (per_block * per_frame)))
@@ -96,8 +100,26 @@ def measure(name, bsz, bd_id, per_frame, want_frames):
     d_at = torch.from_numpy(frame_at).to(dev)
     d_stream[(d_at[:, None] + torch.arange(HDR, device=dev)[None, :]).reshape(-1)] = torch.from_numpy(header.copy()).to(dev).repeat(nf)
     d_ends = torch.from_numpy(np.append(frame_at[1:], n_bytes) - TAIL).to(dev)
-    d_stream[(d_ends[:, None] + torch.arange(TAIL, device=dev)[None, :]).reshape(-1)] = 0
+    trailer = np.zeros((nf, TAIL), dtype=np.uint8)
+    if sums is not None:
+        trailer[:, 4:] = np.ascontiguousarray(sums(pool, nf), dtype="<u4").view(np.uint8).reshape(nf, 4)
+    d_stream[(d_ends[:, None] + torch.arange(TAIL, device=dev)[None, :]).reshape(-1)] = torch.from_numpy(trailer.reshape(-1)).to(dev)
     torch.cuda.synchronize()
+    b = Built()
+    b.d_stream, b.d_body, b.n_bytes, b.body_bytes, b.nf, b.nb, b.frame_at, b.want_off, b.pool = d_stream, d_body, n_bytes, body_bytes, nf, nb, frame_at, want_off, pool
+    return b
+
+
+def measure(name, bsz, bd_id, per_frame, want_frames):
+    import torch
+    from plz4_amd._native import Engine, FrameIndex, StreamIndex, BODY_END_OF_BYTES, STREAM_END
+    dev = torch.device("cuda:0")
+    hip = hip_runtime()
+    eng = Engine(0)
+    b = build_stream(eng, bsz, bd_id, per_frame, want_frames)
+    d_stream, d_body, n_bytes, body_bytes, nf, nb, frame_at, want_off = b.d_stream, b.d_body, b.n_bytes, b.body_bytes, b.nf, b.nb, b.frame_at, b.want_off
+    b.d_body = None
+    s = torch.cuda.current_stream().cuda_stream
     # the new call
     mf, mr = nf + 1, nb + 70
     d_tab = torch.zeros(mf * C.sizeof(FrameIndex), dtype=torch.uint8, device=dev)
