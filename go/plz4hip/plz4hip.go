@@ -501,6 +501,50 @@ func (c *Ctx) DevVerifyFrames(frames, info DevPtr, maxFrames int, dst DevPtr, ds
 		(*C.plz4hip_frame_verdict)(verdicts), (*C.plz4hip_stream_verdict)(sv), stream))
 }
 
+// DevWriteFrames' verdict (WriteInfo.Status).
+const (
+	WriteOk     = int(C.PLZ4HIP_WRITE_OK)
+	WriteNoRoom = int(C.PLZ4HIP_WRITE_NO_ROOM) // End bytes do not fit outCap: nothing was written
+	WriteRecord = int(C.PLZ4HIP_WRITE_RECORD)  // FirstBadRec is no record of the body
+)
+
+// FrameOpts is what every frame of one DevWriteFrames call has in common (plz4hip_frame_opts).
+type FrameOpts struct {
+	Bsz             int  // 64 KiB, 256 KiB, 1 MiB or 4 MiB
+	BlockChecksum   bool // what the records were encoded with
+	Linked          bool // only with blocksPerFrame == 0
+	ContentChecksum bool
+	ContentSize     bool // every header carries its own frame's plaintext length
+	HasDictID       bool
+	DictID          uint32
+}
+
+// WriteInfo is plz4hip_write_info: 32 bytes, the layout of the device struct.
+type WriteInfo struct {
+	End         int64 // bytes of the stream: what out needs; -1 where recOff[nBlocks] lies outside the body
+	NFrames     int32
+	NRecs       int32
+	Status      int32 // Write*
+	FirstBadRec int32 // or -1
+	Reserved    [2]int32
+}
+
+// DevWriteFrames turns the block section DevEncodeBody[Ex] (or DevEncodeRecords[Ex] + DevCompactRecords) left in device memory into
+// a stream of whole LZ4 frames of blocksPerFrame blocks each (0: one frame): headers, end marks and content checksums over the
+// plaintext at src (block i at src + i*srcStride), the records moved between them into out (plz4hip_dev_write_frames).  frames
+// (FrameIndex x nFrames) and outRecOff (int64 x nBlocks+1) are what DevIndexStream would list for the stream, so DevDecodeRecords and
+// DevVerifyFrames can follow without an index pass; info is a WriteInfo.  Everything but o is device memory.  Enqueued on stream
+// behind the encode; nothing is waited for.
+func (c *Ctx) DevWriteFrames(o FrameOpts, src DevPtr, srcBytes, srcStride int64, body DevPtr, bodyBytes int64, recOff DevPtr,
+	blocksPerFrame int, out DevPtr, outCap int64, frames, outRecOff, info DevPtr, stream unsafe.Pointer) error {
+	co := C.plz4hip_frame_opts{bsz: C.int32_t(o.Bsz), blockChecksum: C.int32_t(b2i(o.BlockChecksum)), linked: C.int32_t(b2i(o.Linked)),
+		contentChecksum: C.int32_t(b2i(o.ContentChecksum)), contentSize: C.int32_t(b2i(o.ContentSize)),
+		hasDictId: C.int32_t(b2i(o.HasDictID)), dictId: C.uint32_t(o.DictID)}
+	return c.chk(C.plz4hip_dev_write_frames(c.p, &co, src, C.int64_t(srcBytes), C.int64_t(srcStride), body, C.int64_t(bodyBytes),
+		(*C.int64_t)(recOff), C.int(blocksPerFrame), out, C.int64_t(outCap), (*C.plz4hip_frame_index)(frames), (*C.int64_t)(outRecOff),
+		(*C.plz4hip_write_info)(info), stream))
+}
+
 func b2i(b bool) C.int {
 	if b {
 		return 1

@@ -562,6 +562,86 @@ int plz4hip_dev_verify_frames(plz4hip_ctx* ctx, const plz4hip_frame_index* frame
                               plz4hip_frame_verdict* verdicts /* device, maxFrames */,
                               plz4hip_stream_verdict* sv /* device */, void* stream);
 
+/* plz4hip_dev_write_frames: whole LZ4 frames around the block section an encode left in device memory -- the magic, FLG / BD, content
+ * size, dictionary id and header checksum in front (header/write.go:23-73), the end mark and the content checksum behind
+ * (trailer/trailer.go, blk/frame.go): bytes that any LZ4 reader and plz4hip_dev_index_stream open.  The dual of
+ * plz4hip_dev_verify_frames.  Enqueued behind plz4hip_dev_encode_body[_ex], or behind plz4hip_dev_encode_records[_ex] +
+ * plz4hip_dev_compact_records (levels 3..12), on the same stream: no host reads recOff in between.  One call writes a STREAM of frames
+ * of blocksPerFrame blocks each: XXH32 has no combine operator, so a frame's content checksum is one serial chain, and the caller
+ * trades checksum parallelism against header bytes with k = blocksPerFrame.
+ * GEOMETRY (host arithmetic, 64 bits).  nBlocks = ceil(srcBytes / bsz) (above 0x7FFFFFFE: PLZ4HIP_E_ARG); block i is the
+ * min(bsz, srcBytes - i * bsz) bytes at src + i * srcStride, the layout of plz4hip_dev_encode_records_ex.  nFrames = k ?
+ * max(1, ceil(nBlocks / k)) : 1; frame f owns records [f * k, min((f + 1) * k, nBlocks)) (k == 0: all of them).  srcBytes == 0 is ONE
+ * empty frame: header, end mark, the checksum of no bytes (0x02CC5D05) -- what the reference's synchronous writer emits on Close
+ * (sync/writer.go:133-186); recOff is then not read and counts as recOff[0] = 0.
+ * BYTES.  H = 7 + 8 * contentSize + 4 * hasDictId, T = 4 + 4 * contentChecksum.  Frame f starts at F(f) = f * (H + T) + recOff[f * k]:
+ *     04 22 4D 18 | FLG = 0x40 | !linked << 5 | blockChecksum << 4 | contentSize << 3 | contentChecksum << 2 | hasDictId
+ *     | BD = id << 4 (bsz 64 KiB << 2 * (id - 4)) | LE64 the FRAME's plaintext length | LE32 dictId | (xxh32(FLG .. dictId, seed 0) >> 8) & 0xFF
+ *   then the frame's records unchanged, record i at outRecOff[i] = recOff[i] + (i / k + 1) * H + (i / k) * T (i / k = 0 when k == 0),
+ *   then four zero bytes, then LE32 of the xxh32 (seed 0) of the frame's plaintext where contentChecksum is set.
+ *   The stream's end E = nFrames * (H + T) + recOff[nBlocks].
+ * CHECKS (on the device; every one is `need > have` in 64 bits).  In this order:
+ *     recOff[nBlocks] outside [0, bodyBytes]                E is unknown: info.end = -1, no byte of `out` is written; the record
+ *                                                           tests below run and name a record (the last one at least is bad)
+ *     E > outCap                                            PLZ4HIP_WRITE_NO_ROOM: info.end = E, firstBadRec = -1; NO byte of out, frames
+ *                                                           or outRecOff is written and nothing but recOff[nBlocks] is read
+ *     record i, with a = recOff[i], b = recOff[i + 1]:
+ *         a < 0, b < a or b > bodyBytes                     bad
+ *         b - a < 4 + 4 * blockChecksum                     bad (a block the engine failed on takes no room; an overflowed body)
+ *         w = the size word at body + a:
+ *         (w & 0x7FFFFFFF) > bsz, or
+ *         4 + (w & 0x7FFFFFFF) + 4 * blockChecksum != b - a bad
+ *     any bad record                                        PLZ4HIP_WRITE_RECORD, firstBadRec = the lowest such i
+ *     otherwise                                             PLZ4HIP_WRITE_OK: out[0 .. E) is the stream
+ *   With PLZ4HIP_WRITE_RECORD the bytes inside [out, out + outCap) are unspecified (frames without a bad record that fit are written).
+ * TABLES, so that the reader calls need no index pass: frames[f] is, field by field, what plz4hip_dev_index_stream lists for that
+ * frame -- hdrOff = F(f), bodyOff = F(f) + H, end = F(f + 1); contentSz, dictId, contentSum each 0 where its flag is clear; firstRec,
+ * nRecs, bsz, flags, blockDesc; kind 0, nibble 0, status PLZ4HIP_BODY_END_MARK, reserved 0.  A frame that holds a bad record has
+ * status = -1 - (the index of its first bad record) instead (no PLZ4HIP_BODY_* is negative; plz4hip_dev_verify_frames answers it with
+ * PLZ4HIP_FRAME_INCOMPLETE) and contentSum 0.  outRecOff[i] as above for every i < nBlocks, whatever record i is;
+ * outRecOff[nBlocks] = the end of the last record, E - T (0 if there is none): the index's padding convention.
+ * info is written on EVERY exit: end, nFrames and nRecs = nBlocks of the geometry, status, firstBadRec or -1, reserved 0.  Its end,
+ * nFrames and nRecs lie where plz4hip_stream_index has them, so info serves as the `info` of plz4hip_dev_verify_frames (which reads
+ * nFrames alone) behind ONE plz4hip_dev_decode_records over out, outRecOff and nBlocks records.  recOff[0] need not be 0: the stream
+ * then starts at out + recOff[0], every offset above counts from `out`, and the bytes in front of it are not written.
+ * Whatever the inputs hold, the call READS only recOff[0 .. nBlocks], size words of records that passed the range tests, record bytes
+ * inside [body, body + bodyBytes) and, only when contentChecksum is set, plaintext bytes of blocks inside the srcBytes geometry (a
+ * frame's blocks up to its first bad record); it WRITES nothing outside [out, out + outCap), frames[0 .. nFrames),
+ * outRecOff[0 .. nBlocks] and info.
+ * The call frames whatever records it is given: that a linked HC frame's records obey the stored-bit rule of B' stays the caller's
+ * business, as does passing the blockChecksum, bsz and `linked` the records were encoded with.
+ * The kernels: k_frame_edges, sixteen frames per wavefront and four lanes a frame as in plz4hip_dev_verify_frames, one-wave workgroups
+ * that stride over the frames -- at most ceil(nFrames / 16) and at most plz4hip_dev_resident_waves(ctx, 1) of them; k_frame_move, one
+ * pass over the records' bytes into their places; k_frame_summary, one wavefront that writes info.  No synchronisation, no
+ * allocation, no workspace of the ctx, no LDS, no atomics, nothing on the NULL stream.  Known limit: one frame is one chain of about
+ * 1 GB/s; k = 0 with contentChecksum over a large input is that chain alone.
+ * Every pointer but opts is a device pointer.  PLZ4HIP_E_ARG: a null pointer (src may be null when contentChecksum == 0 or
+ * srcBytes == 0, body when bodyBytes == 0), a negative size, bodyBytes or outCap above 2^62, a bsz that is not one of the four, a
+ * srcStride that is neither bsz nor >= bsz + 65536, blocksPerFrame < 0, linked with blocksPerFrame != 0, reserved != 0. */
+typedef struct {                         /* host, by value: what every frame of the call has in common */
+    int32_t  bsz;             /* 65536, 262144, 1048576 or 4194304 (BD id 4 .. 7) */
+    int32_t  blockChecksum;   /* FLG bit 4: what the records were encoded with */
+    int32_t  linked;          /* FLG bit 5 CLEAR; only with blocksPerFrame == 0 */
+    int32_t  contentChecksum; /* FLG bit 2 */
+    int32_t  contentSize;     /* FLG bit 3: every header carries its own frame's plaintext length */
+    int32_t  hasDictId;       /* FLG bit 0 */
+    uint32_t dictId;
+    int32_t  reserved;        /* 0 */
+} plz4hip_frame_opts;
+enum { PLZ4HIP_WRITE_OK = 0, PLZ4HIP_WRITE_NO_ROOM = 1, PLZ4HIP_WRITE_RECORD = 2 };
+typedef struct {                         /* 32 bytes */
+    int64_t end;              /* bytes of the stream: what `out` needs; -1 where recOff[nBlocks] lies outside the body */
+    int32_t nFrames; int32_t nRecs; int32_t status /* PLZ4HIP_WRITE_* */; int32_t firstBadRec /* or -1 */;
+    int32_t reserved[2];      /* 0 */
+} plz4hip_write_info;
+
+int plz4hip_dev_write_frames(plz4hip_ctx* ctx, const plz4hip_frame_opts* opts,
+                             const void* src, int64_t srcBytes, int64_t srcStride,
+                             const void* body, int64_t bodyBytes, const int64_t* recOff /* device, nBlocks + 1 */,
+                             int blocksPerFrame, void* out, int64_t outCap,
+                             plz4hip_frame_index* frames /* device, nFrames */, int64_t* outRecOff /* device, nBlocks + 1 */,
+                             plz4hip_write_info* info /* device */, void* stream);
+
 /* plz4hip_dev_duplex_records: plz4hip_dev_encode_records (level 1) of one batch AND plz4hip_dev_decode_records of another --
  * a writer's next batch and a reader's -- enqueued as one call, with results identical to the two calls made one after the
  * other; the operands of the two sides must not overlap.  The reference runs its compress and decompress workers side by side

@@ -28,7 +28,7 @@ SYMBOLS = [
     "plz4hip_mgpu_compress_batch", "plz4hip_mgpu_decompress_batch", "plz4hip_mgpu_encode_records", "plz4hip_mgpu_decode_records",
     "plz4hip_mgpu_dev_encode_frame", "plz4hip_mgpu_dev_decode_frame",
     "plz4hip_dev_index_body", "plz4hip_mgpu_dev_index_frame", "plz4hip_dev_index_stream",
-    "plz4hip_dev_verify_frames",
+    "plz4hip_dev_verify_frames", "plz4hip_dev_write_frames",
 ]
 
 E_NAMES = {0: "OK", -1: "E_ARG", -2: "E_DEVICE", -3: "E_NOMEM", -4: "E_UNSUPPORTED"}
@@ -78,6 +78,23 @@ class StreamVerdict(C.Structure):
     """plz4hip_stream_verdict (32 bytes)"""
     _fields_ = [("contentBytes", C.c_int64), ("firstBadFrame", C.c_int32), ("status", C.c_int32), ("nFrames", C.c_int32),
                 ("nOk", C.c_int32), ("nSkippable", C.c_int32), ("reserved", C.c_int32)]
+
+
+# plz4hip_dev_write_frames' verdict (plz4hip_write_info.status)
+WRITE_OK, WRITE_NO_ROOM, WRITE_RECORD = range(3)
+WRITE_NAMES = {0: "OK", 1: "NO_ROOM", 2: "RECORD"}
+
+
+class FrameOpts(C.Structure):
+    """plz4hip_frame_opts: what every frame of one plz4hip_dev_write_frames call has in common (host, 32 bytes)"""
+    _fields_ = [("bsz", C.c_int32), ("blockChecksum", C.c_int32), ("linked", C.c_int32), ("contentChecksum", C.c_int32),
+                ("contentSize", C.c_int32), ("hasDictId", C.c_int32), ("dictId", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class WriteInfo(C.Structure):
+    """plz4hip_write_info (32 bytes)"""
+    _fields_ = [("end", C.c_int64), ("nFrames", C.c_int32), ("nRecs", C.c_int32), ("status", C.c_int32), ("firstBadRec", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class EngineError(RuntimeError):
@@ -220,6 +237,9 @@ def load():
     L.plz4hip_dev_index_stream.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]
     L.plz4hip_dev_verify_frames.restype = C.c_int
     L.plz4hip_dev_verify_frames.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.plz4hip_dev_write_frames.restype = C.c_int
+    L.plz4hip_dev_write_frames.argtypes = [vp, C.POINTER(FrameOpts), vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int, vp, C.c_int64, vp, vp,
+                                           vp, vp]
     L.plz4hip_mgpu_dev_index_frame.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(BodyIndex)]
     if L.plz4hip_abi_version() != ABI_VERSION:
         raise ImportError("plz4_amd: libplz4hip.so ABI %d != binding %d" % (L.plz4hip_abi_version(), ABI_VERSION))
@@ -442,6 +462,20 @@ class Engine:
         the device; enqueued on `stream`, no synchronisation"""
         self._chk(self.L.plz4hip_dev_verify_frames(self.h, frames_ptr, info_ptr, max_frames, dst_ptr, dst_stride, dst_cap, result_ptr,
                                                    status_ptr, max_recs, verdicts_ptr, sv_ptr, stream))
+
+    def dev_write_frames(self, src_ptr, src_bytes, body_ptr, body_bytes, recoff_ptr, blocks_per_frame, out_ptr, out_cap, frames_ptr,
+                         out_recoff_ptr, info_ptr, bsz, block_checksum=False, content_checksum=True, content_size=False, dict_id=None,
+                         linked=False, src_stride=None, stream=0, reserved=0):
+        """whole LZ4 frames of blocks_per_frame blocks each (0: one frame) around the block section dev_encode_body[_ex] or
+        dev_compact_records left (body_ptr, recoff_ptr: int64[nBlocks + 1]) of the plaintext at src_ptr (block i at
+        src_ptr + i * src_stride, default bsz): headers, end marks, content checksums, the records moved between them into
+        out_ptr[0 .. out_cap).  frames_ptr: nFrames FrameIndex entries and out_recoff_ptr: int64[nBlocks + 1], as dev_index_stream
+        would list the stream; info_ptr: a WriteInfo (status: WRITE_*), all on the device; enqueued on `stream`, no synchronisation"""
+        o = FrameOpts(bsz, int(bool(block_checksum)), int(bool(linked)), int(bool(content_checksum)), int(bool(content_size)),
+                      int(dict_id is not None), int(dict_id or 0), reserved)
+        self._chk(self.L.plz4hip_dev_write_frames(self.h, C.byref(o), src_ptr, src_bytes, bsz if src_stride is None else src_stride, body_ptr,
+                                                  body_bytes, recoff_ptr, blocks_per_frame, out_ptr, out_cap, frames_ptr, out_recoff_ptr,
+                                                  info_ptr, stream))
 
     def dev_duplex_records(self, src_ptr, src_bytes, bsz, block_checksum, stage_ptr, reclen_ptr,
                            body_ptr, recoff_ptr, ndec, dec_bsz, dec_block_checksum, dst_ptr, dst_stride, dst_cap,

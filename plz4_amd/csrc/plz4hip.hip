@@ -35,6 +35,7 @@ __device__ unsigned long long plz4_stats[24];
 #include "lz4_body_index_device.inl"
 #include "lz4_stream_index_device.inl"
 #include "lz4_frame_verify_device.inl"
+#include "lz4_frame_write_device.inl"
 #include "ws_layout.h"
 #include "route.h"
 
@@ -1610,6 +1611,31 @@ __global__ __launch_bounds__(64) void k_verify_summary(const StreamIndex* info, 
     wave_verify_summary(info, maxFrames, verdicts, sv);
 }
 
+// Whole frames around an encoded block section (plz4hip_dev_write_frames): sixteen frames' headers, trailers and content checksums per
+// wave over the plaintext the encoder read (wave_frame_edges, lz4_frame_write_device.inl), the records into their places
+// (wave_frame_move: grid (nBlocks, slices), four waves a workgroup), and one wave that writes info (wave_frame_summary).
+static_assert(kWriteOk == PLZ4HIP_WRITE_OK && kWriteNoRoom == PLZ4HIP_WRITE_NO_ROOM && kWriteRecord == PLZ4HIP_WRITE_RECORD,
+              "lz4_frame_write_device.inl and plz4hip.h name the same status");
+static_assert(sizeof(WriteInfo) == sizeof(plz4hip_write_info) && sizeof(WriteInfo) == 32 && offsetof(plz4hip_write_info, status) == 16 &&
+              offsetof(WriteInfo, status) == 16 && offsetof(plz4hip_write_info, firstBadRec) == 20 && offsetof(WriteInfo, firstBadRec) == 20,
+              "plz4hip_write_info is 32 bytes");
+static_assert(offsetof(plz4hip_write_info, end) == offsetof(plz4hip_stream_index, end) && offsetof(plz4hip_write_info, nFrames) == offsetof(plz4hip_stream_index, nFrames) &&
+              offsetof(plz4hip_write_info, nRecs) == offsetof(plz4hip_stream_index, nRecs), "plz4hip_write_info starts as plz4hip_stream_index does");
+static_assert(sizeof(plz4hip_frame_opts) == 32 && offsetof(plz4hip_frame_opts, dictId) == 24, "plz4hip_frame_opts is eight 32-bit words");
+__global__ __launch_bounds__(64) void k_frame_edges(FrameWriteGeom g, const uint8_t* src, const uint8_t* body, const int64_t* recOff, uint8_t* out,
+                                                    FrameIndex* frames, int64_t* outRecOff)
+{
+    wave_frame_edges(g, src, body, recOff, out, frames, outRecOff, (int)blockIdx.x, (int)gridDim.x);
+}
+__global__ __launch_bounds__(256) void k_frame_move(FrameWriteGeom g, const uint8_t* body, const int64_t* recOff, uint8_t* out)
+{
+    wave_frame_move(g, body, recOff, out, (int)blockIdx.x, (int)(blockIdx.y * 4 + (threadIdx.x >> 6)), (int)(gridDim.y * 4));
+}
+__global__ __launch_bounds__(64) void k_frame_summary(FrameWriteGeom g, const int64_t* recOff, const FrameIndex* frames, WriteInfo* info)
+{
+    wave_frame_summary(g, recOff, frames, info);
+}
+
 // Exclusive prefix sum int32 -> int64, one wave, no LDS (wave_scan_lengths).
 __global__ __launch_bounds__(64) void k_scan(const int32_t* __restrict__ len, int64_t* __restrict__ off, int n)
 {
@@ -3034,6 +3060,49 @@ int plz4hip_dev_verify_frames(plz4hip_ctx* c, const plz4hip_frame_index* frames,
         HIPCHK(c, hipGetLastError());
     }
     hipLaunchKernelGGL(k_verify_summary, dim3(1), dim3(64), 0, s, (const StreamIndex*)info, maxFrames, (const FrameVerdict*)verdicts, (StreamVerdict*)sv);
+    HIPCHK(c, hipGetLastError());
+    return PLZ4HIP_OK;
+}
+
+// PLZ4HIP_WRITE_WAVES (read per call): the cap on k_frame_edges' grid, for tests of its stride loop
+static int write_waves_cap(const plz4hip_ctx* c)
+{
+    int cap = c->decWaves > 0 ? c->decWaves : 1;
+    if (const char* v = getenv("PLZ4HIP_WRITE_WAVES")) { const int w = atoi(v); if (w >= 1 && w <= cap) cap = w; }
+    return cap;
+}
+
+int plz4hip_dev_write_frames(plz4hip_ctx* c, const plz4hip_frame_opts* o, const void* src, int64_t srcBytes, int64_t srcStride,
+                             const void* body, int64_t bodyBytes, const int64_t* recOff, int blocksPerFrame, void* out, int64_t outCap,
+                             plz4hip_frame_index* frames, int64_t* outRecOff, plz4hip_write_info* info, void* stream)
+{
+    constexpr int64_t kMaxBytes = (int64_t)1 << 62;
+    if (!c || !o || !recOff || !out || !frames || !outRecOff || !info || srcBytes < 0 || bodyBytes < 0 || bodyBytes > kMaxBytes || outCap < 0 ||
+        outCap > kMaxBytes || blocksPerFrame < 0 || o->reserved != 0 || (bodyBytes && !body) || (srcBytes && o->contentChecksum && !src) ||
+        (o->linked && blocksPerFrame != 0))
+        return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_write_frames: bad argument");
+    const int bsz = o->bsz;
+    int id = 0;
+    for (int j = 4; j <= 7; ++j) if (bsz == 65536 << 2 * (j - 4)) id = j;
+    if (!id) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_write_frames: bsz is none of 64 KiB, 256 KiB, 1 MiB, 4 MiB");
+    if (srcStride != bsz && srcStride < (int64_t)bsz + 65536) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_write_frames: srcStride");
+    const int64_t nb64 = srcBytes / bsz + (srcBytes % bsz != 0);
+    if (nb64 > 0x7FFFFFFE) return fail(c, PLZ4HIP_E_ARG, "plz4hip_dev_write_frames: too many blocks");
+    const FrameWriteGeom g = frame_write_geom(bsz, o->blockChecksum != 0, o->linked != 0, o->contentChecksum != 0, o->contentSize != 0,
+                                              o->hasDictId != 0, o->dictId, srcBytes, srcStride, bodyBytes, blocksPerFrame, outCap);
+    std::lock_guard<std::mutex> lk(c->mu);
+    ENTER_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t groups = ((int64_t)g.nFrames + 15) / 16;
+    const int cap = write_waves_cap(c);
+    hipLaunchKernelGGL(k_frame_edges, dim3(groups < cap ? (int)groups : cap), dim3(64), 0, s, g, (const uint8_t*)src, (const uint8_t*)body, recOff,
+                       (uint8_t*)out, (FrameIndex*)frames, outRecOff);
+    HIPCHK(c, hipGetLastError());
+    if (g.nBlocks > 0) {
+        hipLaunchKernelGGL(k_frame_move, dim3(g.nBlocks, move_slices(bsz + 8)), dim3(256), 0, s, g, (const uint8_t*)body, recOff, (uint8_t*)out);
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_frame_summary, dim3(1), dim3(64), 0, s, g, recOff, (const FrameIndex*)frames, (WriteInfo*)info);
     HIPCHK(c, hipGetLastError());
     return PLZ4HIP_OK;
 }
